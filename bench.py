@@ -7,14 +7,20 @@ independent u64 range proofs that share one generator set, split contiguously by
 of the exact per-proof verify pipeline over the whole batch, inputs already resident in HBM, followed by the single
 accept-reduce: one 4-byte all-reduce of the reject count over RCCL (a no-op at N = 1).  There is no data-path collective.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs W untimed and K timed steps, checks the accept bits and the
+reject count of the last step, and prints ONE JSON line on rank 0: metric, value, unit, ms_per_step (wall time of one timed step),
+higher_is_better, dtype, config, accept_bits_ok, ranks, setup_s.  `--dump-outputs DIR` also writes what the last timed step
+computed -- accept.npy, status.npy (per proof of the rank's shard) and reject_count.npy -- before the line is printed.
+
+`--full` measures everything else on top, after the same timed steps, and adds it to the line:
   roofline     -- dominant kernel: algorithmic bytes per launch (559 B/verify, SURVEY.md 8d, x the proofs one launch
-                  processes) / its average launch duration, measured with HIP events on the launch stream inside the timed
-                  region, against 8 TB/s; `traffic` = measured HBM bytes per launch from the committed PMC passes.
+                  processes) / its average launch duration, measured with HIP events on the launch stream in a second pass
+                  of the same steps (timing_pass, kernels_ms_per_step), against 8 TB/s; `traffic` = measured HBM bytes per
+                  launch from the committed PMC passes; roofline_valu against tools/ratebench's issue rates, measured by the same run.
   cpu_baseline -- the reference-shaped C restatement (oracle/, kind "port": the Rust reference cannot be built here)
                   timed on this box's host cores on a bounded sample of the same workload (rank 0, N = 1 only).
-Secondary objects (never `value`): configs[1] (2^16 proofs on one GPU), the optional RLC batch mode, the host-buffer
-(PCIe-inclusive) entry point.
+Secondary objects (never `value`; --no-secondary leaves them out): configs[1] (2^16 proofs on one GPU), the shares of an
+N-GPU split, the optional RLC batch mode, the host-buffer (PCIe-inclusive) entry point, the table sweep.
 
 Other workloads, each printing its own JSON line with `roofline` and `cpu_baseline`:
   --workload prove     BASELINE configs[3]: batch-prove 2^14 u64 values on one GPU (2262 algorithmic B/prove)
@@ -22,7 +28,8 @@ Other workloads, each printing its own JSON line with `roofline` and `cpu_baseli
                        split over the N GPUs like the headline metric (823 algorithmic B/verify)
   --workload wnla      the crate's generic `wnla::verify` (wnla.rs:75-121): 2^16 instances of N = 16 / 32, device-resident
   --workload circuit   the crate's generic `circuit::verify` (circuit.rs:154-256): 2^16 instances of --statement mixed_k2 | ac_works
-The default line carries reduced-size runs of both as the secondary objects `prove_2pow14` and `recip256_2pow15`.
+Under --full the default line also carries reduced-size runs of prove, recip256, wnla and circuit as secondary objects
+(`prove_2pow14`, `recip256_2pow15`, `wnla_16_32_2pow16`, `circuit_mixed_k2_2pow16`).
 """
 import argparse
 import json
@@ -402,6 +409,15 @@ def make_resident_batch(torch, proto, workload, lo, hi, corrupt_every=1024, slic
     return dV, dP, expect, t_prove
 
 
+def dump_outputs(out_dir, rank, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy (float32 / float64; rank r > 0 of a multi-GPU run adds _rank<r> to the name)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a))
+
+
 def host_summary():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import hostinfo
@@ -517,22 +533,6 @@ def run_verify(args):
     fence()
     elapsed = time.perf_counter() - t_start
     plan_shipping = proto.last_plan()
-    # Pass 2 -- diagnostics only: the same steps with per-kernel HIP events on the launch stream (the C0 halves then run back to back so
-    # that the kernel times add up; below 2^17 proofs the plan also loses its side-by-side kernels).  kernels_ms_per_step, roofline
-    # and roofline_valu come from here; its wall time is reported beside pass 1's and must agree with it when the plans are the same.
-    proto.enable_timing(True)
-    proto.timings(reset=True)
-    fence()
-    t_start = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
-    elapsed_timed = time.perf_counter() - t_start
-    kernel_times = proto.timings(reset=True)
-    plan_timed = proto.last_plan()
-    proto.enable_timing(False)
-    global SHARED_INV
-    SHARED_INV = shared_inv_of(plan_shipping)
 
     # correctness of what was just timed (untimed): accept bits == expectation, global reject count == corrupted proofs
     acc = dA.cpu().numpy()
@@ -540,6 +540,31 @@ def run_verify(args):
     ok_local = bool((acc == expect).all() and not st.any())
     rejects = int(dR.item())
     expected_rejects = len(range(0, total, 1024))
+    if args.dump_outputs:
+        # what a caller of verify_batch_device receives from the last timed step: accept bit and status word per proof of this rank's
+        # shard, and the all-reduced reject count
+        dump_outputs(args.dump_outputs, rank, {"accept": acc.astype(np.float32), "status": st.astype(np.float64),
+                                               "reject_count": np.array([rejects], dtype=np.float64)})
+
+    kernel_times, elapsed_timed, plan_timed = {}, None, None
+    if args.full:
+        # Pass 2 -- diagnostics only: the same steps with per-kernel HIP events on the launch stream (the C0 halves then run back to back so
+        # that the kernel times add up; below 2^17 proofs the plan also loses its side-by-side kernels).  kernels_ms_per_step, roofline
+        # and roofline_valu come from here; its wall time is reported beside pass 1's and must agree with it when the plans are the same.
+        proto.enable_timing(True)
+        proto.timings(reset=True)
+        fence()
+        t_start = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        elapsed_timed = time.perf_counter() - t_start
+        kernel_times = proto.timings(reset=True)
+        plan_timed = proto.last_plan()
+        proto.enable_timing(False)
+        ok_local = ok_local and bool((dA.cpu().numpy() == expect).all() and not dS.any().item()) and int(dR.item()) == rejects
+    global SHARED_INV
+    SHARED_INV = shared_inv_of(plan_shipping)
 
     def max_over_ranks(x):
         t = torch.tensor([x], dtype=torch.float64, device="cuda")
@@ -567,12 +592,13 @@ def run_verify(args):
 
     # BENCH_LITE=1 (diagnostic): the headline passes, configs[1] and the shares only
     lite = bool(os.environ.get("BENCH_LITE"))
+    secondary = args.full and not args.no_secondary
     # ---- secondary measurements, reported separately and never as `value`
     cfg1 = rlc = host_path = None
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         m = min(n, 1 << 16)
         cfg1 = timed_share(m, f"BASELINE configs[1]: the first {m} proofs of the same resident batch on one GPU")
-    if world == 1 and not args.no_secondary and not lite:
+    if world == 1 and secondary and not lite:
         m = min(n, 1 << 16)
         V16, P16 = dV[:m].cpu().numpy(), dP[:m].cpu().numpy()
         proto.verify_batch(V16, P16, workload.LABEL)
@@ -622,7 +648,7 @@ def run_verify(args):
     # one GPU's share of the same batch when it is split over 8 / 4 / 2 GPUs (shard_range: contiguous, so the first 2^20 / N proofs ARE
     # rank 0's share), on the shipping plan: the only measurable determinant of the N-GPU number on a one-GPU box
     shares = {}
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondary:
         for lg in (17, 18, 19):
             if n >= (1 << lg):
                 shares[lg] = timed_share(1 << lg, f"one GPU's share of BASELINE configs[2]'s {total >> lg}-GPU split: the first {1 << lg} proofs of the same resident batch")
@@ -630,14 +656,14 @@ def run_verify(args):
     # the reference's WIRE form resident on the device (reciprocal.rs:37-59: 33-byte SEC1 points -- 525 B per proof + 33 B per commitment):
     # the same proofs, written in that form by the product's prover, decompressed on the device (14 square roots per proof) and verified
     sec1_dev = None
-    if world == 1 and not args.no_secondary and not lite:
+    if world == 1 and secondary and not lite:
         sec1_dev = measure_sec1_device(torch, proto, workload, n, expect, max(3, min(args.steps, 5)), stream)
     callers = None
-    if world == 1 and not args.no_secondary and not under_profiler() and not lite:
+    if world == 1 and secondary and not under_profiler() and not lite:
         m = min(n, 4096)
         callers = concurrent_callers(proto, workload.LABEL, dV[:m].cpu().numpy(), dP[:m].cpu().numpy(), expect[:m])
     call_latency = None
-    if world == 1 and not args.no_secondary and not lite:
+    if world == 1 and secondary and not lite:
         # one call of a few proofs, host buffers in and out (the reference's own usage is one verify / prove at a time: BASELINE
         # configs[0], benches/range_proof.rs): what a caller waits for, not a throughput
         call_latency = {"unit": "ms per call, host buffers", "note": "bppp_u64_verify_batch / bppp_u64_prove_batch on n proofs, median of 7 calls; "
@@ -658,7 +684,7 @@ def run_verify(args):
             a_m, _ = proto.verify_batch(cc, pp, workload.LABEL)          # what the small prove calls made verifies
             okm &= bool(a_m.all())
             call_latency[f"n{m}"] = {"verify_ms": float(np.median(tv[1:]) * 1e3), "prove_ms": float(np.median(tp[1:]) * 1e3), "ok": okm}
-    if not args.no_secondary and not lite:
+    if secondary and not lite:
         dA2 = torch.zeros(n, dtype=torch.uint8, device="cuda")
         dR2 = torch.zeros(1, dtype=torch.int32, device="cuda")
         seed = os.urandom(32)
@@ -719,7 +745,7 @@ def run_verify(args):
     # --workload prove, --workload recip256).  Same measurement code as those workloads, reduced cpu_baseline samples.
     prove14 = recip15 = None
     ok_extra = True
-    if world == 1 and not args.no_secondary and not lite:
+    if world == 1 and secondary and not lite:
         import bench_other
         keep = ("metric", "value", "unit", "ms_per_step", "timing_pass_ms_per_step", "steps", "config", "roofline", "kernels_ms_per_step", "cpu_baseline", "ct_prover")
         r, okp = bench_other.measure_prove(args, proto, gens, 1 << 14, cpu_baseline=not args.no_cpu_baseline, cpu_sample=2048)
@@ -737,30 +763,72 @@ def run_verify(args):
     ranks = {"backend": (dist.get_backend() if dist_on else None), "rccl_nranks": (world if dist_on and dist.get_backend() == "nccl" else 0),
              "per_rank_ms": [round(x, 3) for x in per_rank_ms], "max_ms": round(max(per_rank_ms), 3), "one_device_dry_run": bool(os.environ.get("BENCH_ONE_DEVICE"))}
     elapsed = max_over_ranks(elapsed)
-    elapsed_timed = max_over_ranks(elapsed_timed)
     ok_all = torch.tensor([1 if ok_local else 0], dtype=torch.int32, device="cuda")
     if dist_on:
         dist.all_reduce(ok_all, op=dist.ReduceOp.MIN)
     ok = bool(ok_all.item()) and rejects == expected_rejects
 
-    # the two passes must tell the same story when they ran the same plan: more than 2 % apart fails the run
-    ms_ship, ms_timed = elapsed / args.steps * 1e3, elapsed_timed / args.steps * 1e3
-    same_plan = plan_shipping == plan_timed
-    timing_pass = {"ms_per_step": ms_timed, "plan": plan_timed, "same_plan_as_value": same_plan, "ratio_to_value_pass": ms_timed / ms_ship,
-                   # (checked where it means something: the same plan, steps of 50 ms or more -- the ~25 event pairs of a timed step are noise
-                   # there --, and every rank on a GPU of its own: the one-device dry run's ranks take turns on one chip)
-                   "agrees_within_2pct": (abs(ms_timed / ms_ship - 1.0) <= 0.02) if (same_plan and ms_ship >= 50.0 and not os.environ.get("BENCH_ONE_DEVICE")) else None,
-                   "note": "second pass of the same steps with per-kernel HIP events (C0's halves back to back): the source of kernels_ms_per_step, "
-                           "roofline and roofline_valu, never of `value`; a plan that differs (below 2^17 proofs per GPU the timed pass has no "
-                           "side-by-side kernels, at 2^17 .. 2^18 no twin chains) or a step under 50 ms (the events themselves show), or ranks sharing one device, is not "
-                           "comparable and not checked"}
-    ok_timing = timing_pass["agrees_within_2pct"] is not False
+    ok_timing = True
+    timing_pass = None
+    if args.full:
+        # the two passes must tell the same story when they ran the same plan: more than 2 % apart fails the run
+        elapsed_timed = max_over_ranks(elapsed_timed)
+        ms_ship, ms_timed = elapsed / args.steps * 1e3, elapsed_timed / args.steps * 1e3
+        same_plan = plan_shipping == plan_timed
+        timing_pass = {"ms_per_step": ms_timed, "plan": plan_timed, "same_plan_as_value": same_plan, "ratio_to_value_pass": ms_timed / ms_ship,
+                       # (checked where it means something: the same plan, steps of 50 ms or more -- the ~25 event pairs of a timed step are noise
+                       # there --, and every rank on a GPU of its own: the one-device dry run's ranks take turns on one chip)
+                       "agrees_within_2pct": (abs(ms_timed / ms_ship - 1.0) <= 0.02) if (same_plan and ms_ship >= 50.0 and not os.environ.get("BENCH_ONE_DEVICE")) else None,
+                       "note": "second pass of the same steps with per-kernel HIP events (C0's halves back to back): the source of kernels_ms_per_step, "
+                               "roofline and roofline_valu, never of `value`; a plan that differs (below 2^17 proofs per GPU the timed pass has no "
+                               "side-by-side kernels, at 2^17 .. 2^18 no twin chains) or a step under 50 ms (the events themselves show), or ranks sharing one device, is not "
+                               "comparable and not checked"}
+        ok_timing = timing_pass["agrees_within_2pct"] is not False
     if rank == 0:
         value = total * args.steps / elapsed
-        dom_name, dom_t = max(kernel_times.items(), key=lambda kv: kv[1]["total_ms"])
-        avg_ms = dom_t["total_ms"] / max(1, dom_t["launches"])
-        achieved = ALGO_BYTES_PER_VERIFY * n / (avg_ms * 1e-3) / 1e9
-        traffic_step = pmc_traffic_per_step(kernel_times, args.steps, n)
+        diagnostics = secondaries = {}
+        if args.full:
+            dom_name, dom_t = max(kernel_times.items(), key=lambda kv: kv[1]["total_ms"])
+            avg_ms = dom_t["total_ms"] / max(1, dom_t["launches"])
+            achieved = ALGO_BYTES_PER_VERIFY * n / (avg_ms * 1e-3) / 1e9
+            traffic_step = pmc_traffic_per_step(kernel_times, args.steps, n)
+            diagnostics = {
+                "roofline": {
+                    "bound": "hbm",
+                    "kernel": dom_name,
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": pmc_traffic(dom_name, n),
+                    "avg_launch_ms": avg_ms,
+                    "launches_per_step": dom_t["launches"] / args.steps,
+                    "algorithmic_bytes_per_launch": ALGO_BYTES_PER_VERIFY * n,
+                    "traffic_all_kernels_per_step": traffic_step,
+                    "traffic_all_kernels_over_algorithmic": (traffic_step / (ALGO_BYTES_PER_VERIFY * n)) if traffic_step else None,
+                    "note": "256-bit modular integer path: VALU issue bound, HBM fraction is small by construction "
+                            "(SURVEY.md 8d); roofline_valu is the ceiling that binds.  traffic* come from the committed rocprofv3 --pmc "
+                            "summaries and are null unless those were collected on the device code this run loaded (pmc_matches_build)",
+                },
+                "pmc_matches_build": pmc_matches_build(),
+                "roofline_valu": valu_roofline(dom_name, avg_ms, n, 8 if dom_name in FB_KERNELS else 1),
+                "kernels_ms_per_step": {k: v["total_ms"] / args.steps for k, v in kernel_times.items() if v["launches"]},
+                "timing_pass": timing_pass,
+            }
+            secondaries = {
+                "configs1_2pow16": cfg1,
+                "shard_2pow17": shard17,
+                "shard_2pow18": shares.get(18),
+                "shard_2pow19": shares.get(19),
+                "predicted_scaling": predicted_scaling(total, elapsed / args.steps * 1e3, shares) if world == 1 else None,
+                "concurrent_callers": callers,
+                "rlc_mode": rlc,
+                "host_buffer_path": host_path,
+                "sec1_device": sec1_dev,
+                "call_latency": call_latency,
+                "prove_2pow14": prove14,
+                "recip256_2pow15": recip15,
+            }
         result = {
             "metric": "u64 range-proof batch verifies/sec",
             "value": value,
@@ -789,60 +857,30 @@ def run_verify(args):
                 "parallelism": f"shard{world}" if world > 1 else "single",
                 "plan": plan_shipping,               # the launch plan of the timed steps (include/bppp.h: "last_verify_plan")
                 "kernel_timing_during_value": False,
+                "full": args.full,                   # --full: the diagnostics and secondary objects below were measured too
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": dom_name,
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": pmc_traffic(dom_name, n),
-                "avg_launch_ms": avg_ms,
-                "launches_per_step": dom_t["launches"] / args.steps,
-                "algorithmic_bytes_per_launch": ALGO_BYTES_PER_VERIFY * n,
-                "traffic_all_kernels_per_step": traffic_step,
-                "traffic_all_kernels_over_algorithmic": (traffic_step / (ALGO_BYTES_PER_VERIFY * n)) if traffic_step else None,
-                "note": "256-bit modular integer path: VALU issue bound, HBM fraction is small by construction "
-                        "(SURVEY.md 8d); roofline_valu is the ceiling that binds.  traffic* come from the committed rocprofv3 --pmc "
-                        "summaries and are null unless those were collected on the device code this run loaded (pmc_matches_build)",
-            },
-            "pmc_matches_build": pmc_matches_build(),
-            "roofline_valu": valu_roofline(dom_name, avg_ms, n, 8 if dom_name in FB_KERNELS else 1),
-            "kernels_ms_per_step": {k: v["total_ms"] / args.steps for k, v in kernel_times.items() if v["launches"]},
-            "timing_pass": timing_pass,
+            **diagnostics,
             "accept_bits_ok": ok,
             "reject_count_all_reduced": rejects,
             "ranks": ranks,
-            "configs1_2pow16": cfg1,
-            "shard_2pow17": shard17,
-            "shard_2pow18": shares.get(18),
-            "shard_2pow19": shares.get(19),
-            "predicted_scaling": predicted_scaling(total, elapsed / args.steps * 1e3, shares) if world == 1 else None,
-            "concurrent_callers": callers,
-            "rlc_mode": rlc,
-            "host_buffer_path": host_path,
-            "sec1_device": sec1_dev,
-            "call_latency": call_latency,
-            "prove_2pow14": prove14,
-            "recip256_2pow15": recip15,
+            **secondaries,
             "setup_s": {"context_tables": t_ctx, "inputs_and_gpu_batch_prove": t_setup, "gpu_batch_prove_only": t_prove},
             "prover": {"proofs_per_s_device_buffers": n / t_prove, "note": "setup only; see --workload prove for BASELINE configs[3]"},
             "device_bytes": proto.device_bytes(),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             m = min(args.cpu_sample, n)
             result["cpu_baseline"] = cpu_baseline_verify(gens, workload.LABEL, dV[:m].cpu().numpy(), dP[:m].cpu().numpy(), acc,
                                                          f"first {m} proofs of the same batch")
     proto.close()
     if rank == 0:
-        if world == 1 and not args.no_secondary and not lite and n >= (1 << 17):
+        if world == 1 and secondary and not lite and n >= (1 << 17):
             # what the fixed-base tables buy: the same resident batch through contexts of 13, 12 and 11 windows per scalar (window codes
             # 1119 / 621 / 523, include/bppp.h) created one after the other on this box -- table bytes, what the context costs to create,
             # ms per batch.  The library takes 11 windows (210 GB) on an empty MI355X unless the caller gives it a table budget
             # (bppp_wnla_ctx_create_budget); this is the price list that decision is made from.  Secondary, never `value`.
             result["table_sweep"] = table_sweep(torch, U64RangeProofProtocol, workload, g, gv, hv, dV, dP, dA, dS, expect, n, max(3, min(args.steps, 5)))
-        if world == 1 and not args.no_secondary and not lite:
+        if world == 1 and secondary and not lite:
             # configs[4]'s shape needs tables of its own (769 generators: 97 GB at the 18 bits the library picks on a free device): measured
             # after the u64 context -- 152 GB of tables since round 5 -- has been released, so that the width it gets is the one a caller
             # who only runs this protocol gets
@@ -889,14 +927,20 @@ def main():
     ap.add_argument("--fb-window-bits", type=int, default=0)
     ap.add_argument("--cpu-sample", type=int, default=8192, help="proofs verified by the CPU baseline (rank 0, N=1): ~10-20 s of host work")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (configs[1], RLC mode, host-buffer path)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements (configs[1], RLC mode, host-buffer path)")
     ap.add_argument("--no-session-rates", action="store_true", help="do not run tools/ratebench (the profiler command lines pass this)")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: also the kernel-timing pass, rooflines, session issue rates, the secondary objects and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default workload: write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "verify":
+        ap.error("--dump-outputs is implemented for the default workload (--workload verify) only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     # the chip's issue rates and clock, measured by a child process NOW: nothing in this process has touched the GPU yet (torch is
-    # not even imported), and the GPU is idle
-    if int(os.environ.get("RANK", "0")) == 0 and not args.no_session_rates and not under_profiler():
+    # not even imported), and the GPU is idle.  Only roofline_valu uses them: the default workload measures them under --full alone.
+    if int(os.environ.get("RANK", "0")) == 0 and not args.no_session_rates and not under_profiler() and (args.full or args.workload != "verify"):
         session_rates(measure=True)
     if args.workload == "verify":
         args.total_proofs = args.total_proofs or (1 << 20)

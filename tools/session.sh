@@ -4,7 +4,7 @@
 # Steps (any order, each bounded by its own timeout):
 #   box        rocminfo / host summary (always run first)
 #   tests      python -m pytest tests -m gpu          smoke      __graft_entry__.smoke()
-#   bench      python bench.py (the default line)      shard17    one GPU's share of the 8-GPU split (2^17 proofs)
+#   bench      python bench.py --full (the default line) shard17    one GPU's share of the 8-GPU split (2^17 proofs)
 #   prove      --workload prove                        recip      --workload recip256
 #   prof       rocprofv3 --kernel-trace --stats of the default bench command (no secondaries), plus prove / recip256 (prof_prove, prof_recip)
 #   pmc        FETCH_SIZE / WRITE_SIZE passes (separate runs, --kernel-trace only) + the calibration stream -> pmc/pmc_traffic.json
@@ -29,12 +29,12 @@ for STEP in "$@"; do
     box) ;;
     tests) timeout 3000 python -m pytest tests -m gpu -x -q --durations=8 > $OUT/pytest_gpu.txt 2>&1; echo "pytest rc=$?" >> $LOG; tail -5 $OUT/pytest_gpu.txt ;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; echo "smoke rc=$?" >> $LOG; tail -2 $OUT/smoke.txt ;;
-    bench) timeout 1500 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" >> $LOG; python tools/show_bench.py $OUT/bench.json; tail -3 $OUT/bench.err ;;
-    shard17) timeout 600 python bench.py --total-proofs 131072 --no-cpu-baseline --no-secondary > $OUT/bench_shard17.json 2> $OUT/bench_shard17.err; echo "shard17 rc=$?" >> $LOG; python tools/show_bench.py $OUT/bench_shard17.json ;;
+    bench) timeout 1500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" >> $LOG; python tools/show_bench.py $OUT/bench.json; tail -3 $OUT/bench.err ;;
+    shard17) timeout 600 python bench.py --full --total-proofs 131072 --no-cpu-baseline --no-secondary > $OUT/bench_shard17.json 2> $OUT/bench_shard17.err; echo "shard17 rc=$?" >> $LOG; python tools/show_bench.py $OUT/bench_shard17.json ;;
     prove) timeout 600 python bench.py --workload prove > $OUT/prove.json 2> $OUT/prove.err; echo "prove rc=$?" >> $LOG; head -c 500 $OUT/prove.json; echo ;;
     recip) timeout 1200 python bench.py --workload recip256 > $OUT/recip256.json 2> $OUT/recip256.err; echo "recip rc=$?" >> $LOG; python tools/show_bench.py $OUT/recip256.json | head -5 ;;
     prof)
-      (cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $REPO/bench.py --no-cpu-baseline --no-secondary --no-session-rates > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof rc=$?" >> $LOG)
+      (cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $REPO/bench.py --full --no-cpu-baseline --no-secondary --no-session-rates > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof rc=$?" >> $LOG)
       find $OUT -name "*kernel_trace*" -size +4M -delete ;;
     prof_prove) (cd /tmp; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_prove -- python3 $REPO/bench.py --workload prove --no-cpu-baseline --no-session-rates > /dev/null 2> $OUT/prof_prove.err; echo "rocprof prove rc=$?" >> $LOG); find $OUT -name "*kernel_trace*" -size +4M -delete ;;
     prof_recip) (cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_recip -- python3 $REPO/bench.py --workload recip256 --total-proofs 32768 --no-cpu-baseline --no-session-rates > /dev/null 2> $OUT/prof_recip.err; echo "rocprof recip rc=$?" >> $LOG); find $OUT -name "*kernel_trace*" -size +4M -delete ;;
