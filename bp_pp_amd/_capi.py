@@ -34,6 +34,9 @@ EXPORTS = [
     "bppp_u64_prove_batch_sec1", "bppp_u64_prove_batch_sec1_device",
     "bppp_u64_verify_one", "bppp_u64_verify_one_transcript", "bppp_u64_prove_one", "bppp_u64_prove_one_transcript",
     "bppp_ctx_get_coalesce_stats", "bppp_ctx_get_option", "bppp_u64_plan", "bppp_plan_describe", "bppp_reciprocal_verify_one", "bppp_reciprocal_verify_one_transcript",
+    "bppp_reciprocal_verify_batch_sec1", "bppp_reciprocal_verify_batch_sec1_device", "bppp_circuit_verify_batch_sec1",
+    "bppp_circuit_verify_batch_sec1_device", "bppp_wnla_verify_batch_sec1", "bppp_wnla_verify_batch_sec1_device",
+    "bppp_reciprocal_prove_batch_sec1", "bppp_circuit_prove_batch_sec1", "bppp_wnla_prove_batch_sec1",
 ]
 
 _lib = None
@@ -181,6 +184,19 @@ def lib():
     L.bppp_ctx_get_coalesce_stats.argtypes = [vp, i32, C.POINTER(C.c_uint64)]
     L.bppp_reciprocal_verify_one.argtypes = [vp, u8p, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp]
     L.bppp_reciprocal_verify_one_transcript.argtypes = [vp, vp, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+    # the generic proofs' wire form (SEC1): the twins' argument lists over 33-byte points
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_wnla_verify_batch_sec1"):
+        L.bppp_reciprocal_verify_batch_sec1.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        L.bppp_reciprocal_verify_batch_sec1_device.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        L.bppp_circuit_verify_batch_sec1.argtypes = [vp, vp, u8p, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        L.bppp_circuit_verify_batch_sec1_device.argtypes = [vp, vp, u8p, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        L.bppp_wnla_verify_batch_sec1.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp]
+        L.bppp_wnla_verify_batch_sec1_device.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp]
+        L.bppp_reciprocal_prove_batch_sec1.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bppp_circuit_prove_batch_sec1.argtypes = [vp, vp, u8p, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.bppp_wnla_prove_batch_sec1.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp]
+        for name in EXPORTS[-9:]:
+            getattr(L, name).restype = i32
     L.bppp_strerror.argtypes = [i32]
     L.bppp_strerror.restype = C.c_char_p
     L.bppp_last_error.restype = C.c_char_p

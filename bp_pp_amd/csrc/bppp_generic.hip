@@ -122,6 +122,29 @@ static void launch_wnla_final_scalars(const bppp_ctx* c, const WnlaWs& w, unsign
     } else k_wnla_final_scalars<<<blocks, BPPP_BLOCK, 0, s>>>(w);
     (void)n;
 }
+// the wire form of the generic proofs (the *_sec1 entry points at the end of this file): conversion launches over a WireMap (wire_core.h)
+static int wire_launch(WireMap m, bool expand, hipStream_t s) {
+    const u64 lanes = wire_map_finish(m);
+    if (lanes == 0) return BPPP_OK;
+    const unsigned blocks = (unsigned)((lanes + 255) / 256);
+    if (expand) k_wire_expand<<<blocks, 256, 0, s>>>(m);
+    else k_wire_compress<<<blocks, 256, 0, s>>>(m);
+    HIP_TRY(hipGetLastError());
+    return BPPP_OK;
+}
+// one contiguous proof of P points and S scalars per instance: 33 P + 32 S bytes <-> 64 P + 32 S bytes, field order unchanged
+static void wire_add_proof(WireMap& m, const uint8_t* src33, uint8_t* dst64, size_t P, size_t S) {
+    const size_t b33 = 33 * P + 32 * S, b64 = 64 * P + 32 * S;
+    wire_map_add(m, false, src33, b33, dst64, b64, P);
+    wire_map_add(m, true, src33 + 33 * P, b33, dst64 + 64 * P, b64, S);
+}
+static size_t wire_proof_bytes(size_t P, size_t S) { return 33 * P + 32 * S; }
+// a failed host-buffer call leaves nothing running behind it (the staging is reused by the next call); after the final sync it costs nothing
+struct WireQuiesce {
+    bppp_ctx* c = nullptr;
+    ~WireQuiesce() { if (c) quiesce(c); }
+};
+
 // ---- generic WeightNormLinearArgument entry points (host pointers; one device blob per call)
 // (the context's grow-only buffer: no allocator round trip per call.  Whatever way the call ends, nothing of it is still running
 // when the blob goes out of scope -- on the success path the stream has just been waited for and this costs nothing)
@@ -914,7 +937,8 @@ static int ct_setup(bppp_ctx* c, FbTable& fb_ct, int& ct, size_t n) {
 }
 static int wnla_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, const HostTranscripts* tx, size_t n, const uint8_t* commitments,
                            const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, const uint8_t* l, size_t nl, const uint8_t* nvec, size_t nn,
-                           uint8_t* proof_r, uint8_t* proof_x, uint8_t* proof_l, uint8_t* proof_n, int32_t* status) {
+                           uint8_t* proof_r, uint8_t* proof_x, uint8_t* proof_l, uint8_t* proof_n, int32_t* status, bool sec1 = false) {
+    // sec1 (bppp_wnla_prove_batch_sec1): commitments n x 33 in, proof_r / proof_x n x rounds x 33 out (SEC1, converted on the device)
     if (!c || !label_ok(label, label_len) || !commitments || !cvec || !rho || !mu || (!l && nl) || (!nvec && nn) || nl > 65536 || nn > 65536)
         return BPPP_ERR_INVALID_ARG;
     size_t rounds, nl_f, nn_f;
@@ -935,7 +959,16 @@ static int wnla_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, 
     { const int rc_b = blob.take(c, off); if (rc_b != BPPP_OK) return rc_b; }
     uint8_t* d = blob.d;
     hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * 64, hipMemcpyHostToDevice, s));
+    const size_t o_wout = align16(n * 33), o_wout_x = o_wout + align16(n * rounds * 33);
+    if (sec1) {
+        { const int rc_w = ensure_buffer(c, c->d_wire, c->wire_bytes, o_wout_x + n * rounds * 33 + 16); if (rc_w != BPPP_OK) return rc_w; }
+        HIP_TRY(hipMemcpyAsync(c->d_wire, commitments, n * 33, hipMemcpyHostToDevice, s));
+        WireMap wm;
+        wire_map_init(wm, n);
+        wire_map_add(wm, false, c->d_wire, 33, d + o_com, 64, 1);
+        const int rc_e = wire_launch(wm, true, s);
+        if (rc_e != BPPP_OK) return rc_e;
+    } else HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * 64, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_c, cvec, n * nh * 32, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_rho, rho, n * 32, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_mu, mu, n * 32, hipMemcpyHostToDevice, s));
@@ -970,7 +1003,16 @@ static int wnla_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, 
     }
     k_wprove_finish<<<blocks, BPPP_BLOCK, 0, s>>>(w);
     HIP_TRY(hipGetLastError());
-    if (rounds) {
+    if (rounds && sec1) {
+        WireMap wm;
+        wire_map_init(wm, n);
+        wire_map_add(wm, false, d + o_pr, rounds * 64, c->d_wire + o_wout, rounds * 33, rounds);
+        wire_map_add(wm, false, d + o_px, rounds * 64, c->d_wire + o_wout_x, rounds * 33, rounds);
+        rc = wire_launch(wm, false, s);
+        if (rc != BPPP_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(proof_r, c->d_wire + o_wout, n * rounds * 33, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(proof_x, c->d_wire + o_wout_x, n * rounds * 33, hipMemcpyDeviceToHost, s));
+    } else if (rounds) {
         HIP_TRY(hipMemcpyAsync(proof_r, d + o_pr, n * rounds * 64, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(proof_x, d + o_px, n * rounds * 64, hipMemcpyDeviceToHost, s));
     }
@@ -1001,7 +1043,8 @@ int bppp_wnla_prove_batch_transcript(bppp_ctx* c, size_t n, const uint8_t* state
 // ArithmeticCircuit::prove (circuit.rs:260-556) for n instances of a shared circuit.
 static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, const HostTranscripts* tx, size_t n,
                               const uint8_t* v_commitments, const uint8_t* v, const uint8_t* s_v, const uint8_t* w_l, const uint8_t* w_r,
-                              const uint8_t* w_o, const uint8_t* rnd, uint8_t* proofs, int32_t* status) {
+                              const uint8_t* w_o, const uint8_t* rnd, uint8_t* proofs, int32_t* status, bool sec1 = false) {
+    // sec1 (bppp_circuit_prove_batch_sec1): v_commitments n x k x 33 in, proofs in the 33-byte form out (converted on the device)
     if (!c || !q || !label_ok(label, label_len) || !v_commitments || !v || !s_v || !w_l || !w_r || !rnd || !proofs) return BPPP_ERR_INVALID_ARG;
     const CircuitDev& cd = q->cd;
     if ((cd.no && !w_o) || cd.nm > c->ng || cd.nv + 9 > c->nh) return BPPP_ERR_INVALID_ARG;
@@ -1028,7 +1071,16 @@ static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t*
     { const int rc_b = blob.take(c, off); if (rc_b != BPPP_OK) return rc_b; }
     uint8_t* d = blob.d;
     hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_vp, v_commitments, n * k * 64, hipMemcpyHostToDevice, s));
+    const size_t wP = 4 + 2 * rounds, wS = nl_f + nn_f, o_wout = align16(n * k * 33);
+    if (sec1) {
+        { const int rc_w = ensure_buffer(c, c->d_wire, c->wire_bytes, o_wout + n * wire_proof_bytes(wP, wS) + 16); if (rc_w != BPPP_OK) return rc_w; }
+        HIP_TRY(hipMemcpyAsync(c->d_wire, v_commitments, n * k * 33, hipMemcpyHostToDevice, s));
+        WireMap wm;
+        wire_map_init(wm, n);
+        wire_map_add(wm, false, c->d_wire, 33 * k, d + o_vp, 64 * k, k);
+        const int rc_e = wire_launch(wm, true, s);
+        if (rc_e != BPPP_OK) return rc_e;
+    } else HIP_TRY(hipMemcpyAsync(d + o_vp, v_commitments, n * k * 64, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_v, v, n * k * nv * 32, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_sv, s_v, n * k * 32, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_wl, w_l, n * nm * 32, hipMemcpyHostToDevice, s));
@@ -1087,6 +1139,27 @@ static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t*
     }
     k_wprove_finish<<<blocks, BPPP_BLOCK, 0, s>>>(w);
     HIP_TRY(hipGetLastError());
+    if (sec1) {
+        // the proofs assembled and compressed on the device, head | r | x | l | n; a flagged instance comes out as zero bytes
+        const size_t pb = wire_proof_bytes(wP, wS);
+        uint8_t* out = c->d_wire + o_wout;
+        WireMap wm;
+        wire_map_init(wm, n);
+        wm.zero_if = p.status;
+        wire_map_add(wm, false, d + o_head, 256, out, pb, 4);
+        wire_map_add(wm, false, d + o_pr, rounds * 64, out + 33 * 4, pb, rounds);
+        wire_map_add(wm, false, d + o_px, rounds * 64, out + 33 * (4 + rounds), pb, rounds);
+        wire_map_add(wm, true, d + o_pl, nl_f * 32, out + 33 * wP, pb, nl_f);
+        wire_map_add(wm, true, d + o_pn, nn_f * 32, out + 33 * wP + 32 * nl_f, pb, nn_f);
+        rc = wire_launch(wm, false, s);
+        if (rc != BPPP_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(proofs, out, n * pb, hipMemcpyDeviceToHost, s));
+        if (status) HIP_TRY(hipMemcpyAsync(status, p.status, n * 4, hipMemcpyDeviceToHost, s));
+        rc = txd.finish(tx, p.tio, p.base, p.tstate, n, p.status, s);
+        if (rc != BPPP_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+        return BPPP_OK;
+    }
     // assemble the proofs on the host side of the copy: head | r | x | l | n per instance
     std::vector<uint8_t> head(n * 256), pr(n * rounds * 64), px(n * rounds * 64), pl(n * nl_f * 32), pn(n * nn_f * 32);
     std::vector<int32_t> st(n);
@@ -1133,7 +1206,8 @@ int bppp_circuit_prove_batch_transcript(bppp_ctx* c, const bppp_circuit* q, size
 // ReciprocalRangeProofProtocol::prove (reciprocal.rs:110-146) for runtime dim_nd / dim_np.
 static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, const HostTranscripts* tx, size_t n, size_t dim_nd, size_t dim_np,
                             const uint8_t* commitments, const uint8_t* x, const uint8_t* sblind, const uint8_t* digits, const uint8_t* m,
-                            const uint8_t* rnd, uint8_t* proofs, int32_t* status) {
+                            const uint8_t* rnd, uint8_t* proofs, int32_t* status, bool sec1 = false) {
+    // sec1 (bppp_reciprocal_prove_batch_sec1): commitments n x 33 in, proofs in the 33-byte form out (converted on the device)
     if (!c || !label_ok(label, label_len) || !commitments || !x || !sblind || !digits || !m || !rnd || !proofs) return BPPP_ERR_INVALID_ARG;
     if (dim_nd == 0 || dim_np == 0 || dim_nd > (size_t)c->ng || dim_nd + 10 > (size_t)c->nh || dim_np > dim_nd + 1 || dim_nd > 4096)
         return BPPP_ERR_INVALID_ARG;
@@ -1178,7 +1252,17 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     HIP_TRY(up(o_cmp, hd.colmap.data(), hd.colmap.size() * 4)); HIP_TRY(up(o_al, hd.al.data(), hd.al.size() * 4)); HIP_TRY(up(o_am, hd.am.data(), hd.am.size() * 4));
     HIP_TRY(up(o_il, P.inst_l.data(), P.inst_l.size() * 4)); HIP_TRY(up(o_im, P.inst_m.data(), P.inst_m.size() * 4));
     HIP_TRY(up(o_part, P.parts.data(), P.parts.size() * 4));
-    HIP_TRY(up(o_com, commitments, n * 64)); HIP_TRY(up(o_x, x, n * 32)); HIP_TRY(up(o_s, sblind, n * 32));
+    const size_t wP = 5 + 2 * rounds, wS = nl_f + nn_f, o_wout = align16(n * 33);
+    if (sec1) {
+        { const int rc_w = ensure_buffer(c, c->d_wire, c->wire_bytes, o_wout + n * wire_proof_bytes(wP, wS) + 16); if (rc_w != BPPP_OK) return rc_w; }
+        HIP_TRY(hipMemcpyAsync(c->d_wire, commitments, n * 33, hipMemcpyHostToDevice, s));
+        WireMap wm;
+        wire_map_init(wm, n);
+        wire_map_add(wm, false, c->d_wire, 33, d + o_com, 64, 1);
+        const int rc_e = wire_launch(wm, true, s);
+        if (rc_e != BPPP_OK) return rc_e;
+    } else HIP_TRY(up(o_com, commitments, n * 64));
+    HIP_TRY(up(o_x, x, n * 32)); HIP_TRY(up(o_s, sblind, n * 32));
     HIP_TRY(up(o_dig, digits, n * nd * 32)); HIP_TRY(up(o_m, m, n * np * 32)); HIP_TRY(up(o_rnd, rnd, n * n_rnd * 32));
     HIP_TRY(hipStreamSynchronize(s));                      // the pattern vectors live on this stack frame
     RecipProveWs r;
@@ -1253,6 +1337,28 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     }
     k_wprove_finish<<<blocks, BPPP_BLOCK, 0, s>>>(w);
     HIP_TRY(hipGetLastError());
+    if (sec1) {
+        // the proofs assembled and compressed on the device, head | r | x | reciprocal r | l | n; a flagged instance comes out as zero bytes
+        const size_t pb = wire_proof_bytes(wP, wS);
+        uint8_t* out = c->d_wire + o_wout;
+        WireMap wm;
+        wire_map_init(wm, n);
+        wm.zero_if = r.status;
+        wire_map_add(wm, false, d + o_head, 256, out, pb, 4);
+        wire_map_add(wm, false, d + o_pr, rounds * 64, out + 33 * 4, pb, rounds);
+        wire_map_add(wm, false, d + o_px, rounds * 64, out + 33 * (4 + rounds), pb, rounds);
+        wire_map_add(wm, false, d + o_prr, 64, out + 33 * (4 + 2 * rounds), pb, 1);
+        wire_map_add(wm, true, d + o_pl, nl_f * 32, out + 33 * wP, pb, nl_f);
+        wire_map_add(wm, true, d + o_pn, nn_f * 32, out + 33 * wP + 32 * nl_f, pb, nn_f);
+        rc = wire_launch(wm, false, s);
+        if (rc != BPPP_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(proofs, out, n * pb, hipMemcpyDeviceToHost, s));
+        if (status) HIP_TRY(hipMemcpyAsync(status, r.status, n * 4, hipMemcpyDeviceToHost, s));
+        rc = txd.finish(tx, r.tio, r.base, r.tstate, n, r.status, s);
+        if (rc != BPPP_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+        return BPPP_OK;
+    }
     std::vector<uint8_t> head(n * 256), prr(n * 64), pr(n * rounds * 64 + 1), px(n * rounds * 64 + 1), pl(n * nl_f * 32 + 1), pn(n * nn_f * 32 + 1);
     std::vector<int32_t> st(n);
     HIP_TRY(hipMemcpyAsync(head.data(), d + o_head, n * 256, hipMemcpyDeviceToHost, s));
@@ -1293,6 +1399,241 @@ int bppp_reciprocal_prove_batch_transcript(bppp_ctx* c, size_t n, const uint8_t*
     if (!states) return BPPP_ERR_INVALID_ARG;
     HostTranscripts tx = {states, n_states, states_out};
     return recip_prove_impl(c, nullptr, 0, &tx, n, dim_nd, dim_np, commitments, x, sblind, digits, m, rnd, proofs, status);
+}
+
+
+// ---------------------------------------------------------------- the wire form of the generic proofs (SEC1, the crate's serialised types)
+// reciprocal::SerializableProof, circuit::SerializableProof, wnla::SerializableProof (reciprocal.rs:37-41, circuit.rs:36-46, wnla.rs:33-38):
+// the C-ABI layouts above with every point 33-byte SEC1-compressed in place and the scalars as they are.  The verifiers expand the
+// inputs on the device (k_wire_expand, one lane per point) into the context's wire buffer and run the 64-byte path on it; an undecodable
+// point becomes the off-curve (1, 0), which phase 1 flags BPPP_ST_BAD_ENCODING -- the status the 64-byte form gets for that point.  The
+// provers decompress their input commitments the same way and compress their proofs on the device (k_wire_compress) before the copy
+// back.  The host-buffer forms stage the 33-byte bytes in the same buffer, in front of the expanded form.
+// ---- reciprocal
+static size_t recip_sec1_exp_bytes(size_t n, size_t rounds, size_t nl, size_t nn) {
+    return align16(n * 64) + n * (64 * (5 + 2 * rounds) + 32 * (nl + nn));
+}
+// arguments checked; d_exp: recip_sec1_exp_bytes in the wire buffer
+static int recip_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np, const uint8_t* d_com33,
+                          const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status, uint8_t* d_exp) {
+    const size_t P = 5 + 2 * rounds, S = nl + nn, o_p = align16(n * 64);
+    WireMap m;
+    wire_map_init(m, n);
+    wire_map_add(m, false, d_com33, 33, d_exp, 64, 1);
+    wire_add_proof(m, d_proofs33, d_exp + o_p, P, S);
+    // on c->stream: a call split into parts forks them from c->stream behind this (ev_twin_fork in recip_verify_device_entry)
+    int rc = wire_launch(m, true, c->stream);
+    if (rc != BPPP_OK) return rc;
+    return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, nullptr, nullptr);
+}
+int bppp_reciprocal_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                             const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                                             void* d_accept, void* d_status) {
+    CtxLock lock_(c);
+    if (!c || !label_ok(label, label_len) || !d_commitments33 || !d_proofs33 || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
+    int rc = recip_verify_check_args(c, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (recip_is_u64_shape(c, dim_nd, dim_np, rounds, nl, nn))      // the u64 wire form is the same 33 + 525 bytes: its own expand kernel
+        return verify_sec1_device_impl(c, label, label_len, n, d_commitments33, d_proofs33, d_accept, d_status, nullptr, nullptr);
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, recip_sec1_exp_bytes(n, rounds, nl, nn));
+    if (rc != BPPP_OK) return rc;
+    return recip_sec1_run(c, label, label_len, n, dim_nd, dim_np, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, rounds, nl, nn,
+                          d_accept, d_status, c->d_wire);
+}
+int bppp_reciprocal_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                      const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                      int32_t* status) {
+    CtxLock lock_(c);
+    if (!c || !label_ok(label, label_len) || !commitments33 || !proofs33 || !accept) return BPPP_ERR_INVALID_ARG;
+    int rc = recip_verify_check_args(c, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (n == 0) return BPPP_OK;
+    if (recip_is_u64_shape(c, dim_nd, dim_np, rounds, nl, nn))
+        return bppp_u64_verify_batch_sec1(c, label, label_len, n, commitments33, proofs33, accept, status);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t pb = wire_proof_bytes(5 + 2 * rounds, nl + nn);
+    const size_t o_c = 0, o_p = align16(n * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_e = align16(o_s + n * 4),
+                 total = o_e + recip_sec1_exp_bytes(n, rounds, nl, nn);
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
+    if (rc != BPPP_OK) return rc;
+    WireQuiesce guard{c};
+    uint8_t* d = c->d_wire;
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * 33, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
+    rc = recip_sec1_run(c, label, label_len, n, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, d + o_e);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPPP_OK;
+}
+
+// ---- circuit
+static int circuit_sec1_check(const bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, const void* commitments,
+                              const void* proofs, const void* accept, size_t rounds, size_t nl, size_t nn) {
+    if (!c || !q || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
+    const CircuitDev& cd = q->cd;
+    if (cd.nm > c->ng || cd.nv + 9 > c->nh || rounds > 12 || nl > 4096 || nn > 4096) return BPPP_ERR_INVALID_ARG;
+    return BPPP_OK;
+}
+static size_t circuit_sec1_exp_bytes(size_t n, size_t k, size_t rounds, size_t nl, size_t nn) {
+    return align16(n * k * 64) + n * (64 * (4 + 2 * rounds) + 32 * (nl + nn));
+}
+static int circuit_sec1_run(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n, const uint8_t* d_com33,
+                            const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* d_accept, int32_t* d_status, uint8_t* d_exp) {
+    const size_t k = (size_t)q->cd.k, P = 4 + 2 * rounds, S = nl + nn, o_p = align16(n * k * 64);
+    WireMap m;
+    wire_map_init(m, n);
+    wire_map_add(m, false, d_com33, 33 * k, d_exp, 64 * k, k);
+    wire_add_proof(m, d_proofs33, d_exp + o_p, P, S);
+    int rc = wire_launch(m, true, c->stream);
+    if (rc != BPPP_OK) return rc;
+    return circuit_verify_host_impl(c, q, label, label_len, n, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, nullptr, true);
+}
+int bppp_circuit_verify_batch_sec1_device(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                          const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                                          void* d_accept, void* d_status) {
+    CtxLock lock_(c);
+    int rc = circuit_sec1_check(c, q, label, label_len, d_commitments33, d_proofs33, d_accept, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, circuit_sec1_exp_bytes(n, (size_t)q->cd.k, rounds, nl, nn));
+    if (rc != BPPP_OK) return rc;
+    return circuit_sec1_run(c, q, label, label_len, n, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, rounds, nl, nn,
+                            (uint8_t*)d_accept, (int32_t*)d_status, c->d_wire);
+}
+int bppp_circuit_verify_batch_sec1(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                   const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                   int32_t* status) {
+    CtxLock lock_(c);
+    int rc = circuit_sec1_check(c, q, label, label_len, commitments33, proofs33, accept, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t k = (size_t)q->cd.k, pb = wire_proof_bytes(4 + 2 * rounds, nl + nn);
+    const size_t o_c = 0, o_p = align16(n * k * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_e = align16(o_s + n * 4),
+                 total = o_e + circuit_sec1_exp_bytes(n, k, rounds, nl, nn);
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
+    if (rc != BPPP_OK) return rc;
+    WireQuiesce guard{c};
+    uint8_t* d = c->d_wire;
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * k * 33, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
+    rc = circuit_sec1_run(c, q, label, label_len, n, d + o_c, d + o_p, rounds, nl, nn, d + o_a, (int32_t*)(d + o_s), d + o_e);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPPP_OK;
+}
+
+// ---- WeightNormLinearArgument (the commitment and proof.r / proof.x are points; proof.l / proof.n scalars, taken as they are)
+static int wnla_sec1_check(const bppp_ctx* c, const uint8_t* label, size_t label_len, const void* commitments, const void* cvec, const void* rho,
+                           const void* mu, size_t rounds, const void* proof_r, const void* proof_x, const void* proof_l, size_t nl,
+                           const void* proof_n, size_t nn, const void* accept) {
+    if (!c || !label_ok(label, label_len) || !commitments || !cvec || !rho || !mu || (rounds && (!proof_r || !proof_x)) || (!proof_l && nl) ||
+        (!proof_n && nn) || !accept)
+        return BPPP_ERR_INVALID_ARG;
+    if (rounds > 12 || nl > 4096 || nn > 4096) return BPPP_ERR_INVALID_ARG;      // (wnla_run's own check, before anything is sized by them)
+    return BPPP_OK;
+}
+static size_t wnla_sec1_exp_bytes(size_t n, size_t rounds) { return align16(n * 64) + 2 * align16(n * rounds * 64); }
+static int wnla_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* d_com33, const uint8_t* d_c,
+                         const uint8_t* d_rho, const uint8_t* d_mu, size_t rounds, const uint8_t* d_r33, const uint8_t* d_x33, const uint8_t* d_l,
+                         size_t nl, const uint8_t* d_n, size_t nn, uint8_t* d_accept, int32_t* d_status, uint8_t* d_exp) {
+    const size_t o_r = align16(n * 64), o_x = o_r + align16(n * rounds * 64);
+    WireMap m;
+    wire_map_init(m, n);
+    wire_map_add(m, false, d_com33, 33, d_exp, 64, 1);
+    if (rounds) {
+        wire_map_add(m, false, d_r33, 33 * rounds, d_exp + o_r, 64 * rounds, rounds);
+        wire_map_add(m, false, d_x33, 33 * rounds, d_exp + o_x, 64 * rounds, rounds);
+    }
+    int rc = wire_launch(m, true, c->stream);
+    if (rc != BPPP_OK) return rc;
+    return wnla_run(c, false, label, label_len, n, d_exp, d_c, d_rho, d_mu, rounds, d_exp + o_r, d_exp + o_x, d_l, nl, d_n, nn, nullptr,
+                    d_accept, d_status, nullptr, true);
+}
+int bppp_wnla_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33,
+                                       const void* d_c, const void* d_rho, const void* d_mu, size_t rounds, const void* d_proof_r33,
+                                       const void* d_proof_x33, const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn,
+                                       void* d_accept, void* d_status) {
+    CtxLock lock_(c);
+    int rc = wnla_sec1_check(c, label, label_len, d_commitments33, d_c, d_rho, d_mu, rounds, d_proof_r33, d_proof_x33, d_proof_l, nl, d_proof_n,
+                             nn, d_accept);
+    if (rc != BPPP_OK) return rc;
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, wnla_sec1_exp_bytes(n, rounds));
+    if (rc != BPPP_OK) return rc;
+    return wnla_sec1_run(c, label, label_len, n, (const uint8_t*)d_commitments33, (const uint8_t*)d_c, (const uint8_t*)d_rho, (const uint8_t*)d_mu,
+                         rounds, (const uint8_t*)d_proof_r33, (const uint8_t*)d_proof_x33, (const uint8_t*)d_proof_l, nl, (const uint8_t*)d_proof_n,
+                         nn, (uint8_t*)d_accept, (int32_t*)d_status, c->d_wire);
+}
+int bppp_wnla_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
+                                const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r33,
+                                const uint8_t* proof_x33, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
+                                uint8_t* accept, int32_t* status) {
+    CtxLock lock_(c);
+    int rc = wnla_sec1_check(c, label, label_len, commitments33, cvec, rho, mu, rounds, proof_r33, proof_x33, proof_l, nl, proof_n, nn, accept);
+    if (rc != BPPP_OK) return rc;
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t NH = (size_t)c->nh;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align16(off + bytes); return o; };
+    const size_t o_com = take(n * 33), o_c = take(n * NH * 32), o_rho = take(n * 32), o_mu = take(n * 32), o_r = take(n * rounds * 33),
+                 o_x = take(n * rounds * 33), o_l = take(n * nl * 32), o_n = take(n * nn * 32), o_a = take(n), o_s = take(n * 4),
+                 o_e = take(wnla_sec1_exp_bytes(n, rounds));
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, off);
+    if (rc != BPPP_OK) return rc;
+    WireQuiesce guard{c};
+    uint8_t* d = c->d_wire;
+    hipStream_t s = c->stream;
+    auto up = [&](size_t o, const uint8_t* src, size_t bytes) -> hipError_t {
+        return (src && bytes) ? hipMemcpyAsync(d + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIP_TRY(up(o_com, commitments33, n * 33));
+    HIP_TRY(up(o_c, cvec, n * NH * 32));
+    HIP_TRY(up(o_rho, rho, n * 32));
+    HIP_TRY(up(o_mu, mu, n * 32));
+    HIP_TRY(up(o_r, proof_r33, n * rounds * 33));
+    HIP_TRY(up(o_x, proof_x33, n * rounds * 33));
+    HIP_TRY(up(o_l, proof_l, n * nl * 32));
+    HIP_TRY(up(o_n, proof_n, n * nn * 32));
+    rc = wnla_sec1_run(c, label, label_len, n, d + o_com, d + o_c, d + o_rho, d + o_mu, rounds, d + o_r, d + o_x, d + o_l, nl, d + o_n, nn,
+                       d + o_a, (int32_t*)(d + o_s), d + o_e);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPPP_OK;
+}
+
+// ---- provers: the 64-byte provers' impls with sec1 = true (33-byte commitments in, 33-byte proof points out)
+int bppp_reciprocal_prove_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                     const uint8_t* commitments33, const uint8_t* x, const uint8_t* sblind, const uint8_t* digits,
+                                     const uint8_t* m, const uint8_t* rnd, uint8_t* proofs33, int32_t* status) {
+    CtxLock lock_(c);
+    return recip_prove_impl(c, label, label_len, nullptr, n, dim_nd, dim_np, commitments33, x, sblind, digits, m, rnd, proofs33, status, true);
+}
+int bppp_circuit_prove_batch_sec1(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                  const uint8_t* v_commitments33, const uint8_t* v, const uint8_t* s_v, const uint8_t* w_l, const uint8_t* w_r,
+                                  const uint8_t* w_o, const uint8_t* rnd, uint8_t* proofs33, int32_t* status) {
+    CtxLock lock_(c);
+    return circuit_prove_impl(c, q, label, label_len, nullptr, n, v_commitments33, v, s_v, w_l, w_r, w_o, rnd, proofs33, status, true);
+}
+int bppp_wnla_prove_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33, const uint8_t* cvec,
+                               const uint8_t* rho, const uint8_t* mu, const uint8_t* l, size_t nl, const uint8_t* nvec, size_t nn,
+                               uint8_t* proof_r33, uint8_t* proof_x33, uint8_t* proof_l, uint8_t* proof_n, int32_t* status) {
+    CtxLock lock_(c);
+    return wnla_prove_impl(c, label, label_len, nullptr, n, commitments33, cvec, rho, mu, l, nl, nvec, nn, proof_r33, proof_x33, proof_l, proof_n,
+                           status, true);
 }
 
 

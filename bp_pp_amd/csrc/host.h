@@ -134,6 +134,10 @@ struct bppp_ctx {
     // expanded (64-byte) form of SEC1-compressed inputs
     uint8_t* d_expand = nullptr;
     size_t expand_bytes = 0;
+    // the generic proofs' wire form (bppp_generic.hip: *_sec1 entry points): 33-byte staging and the expanded 64-byte inputs / the
+    // prover's compressed output
+    uint8_t* d_wire = nullptr;
+    size_t wire_bytes = 0;
     int* d_flags = nullptr;
     int n_simds = 1024;            // CUs x 4 (device property), decides between the small-batch and the 2-waves/SIMD lane kernels
     bool borrows_tables = false;   // d_gens / d_table belong to another context (bppp_ctx_create_shared)

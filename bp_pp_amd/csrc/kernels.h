@@ -12,6 +12,7 @@
 #include "rlc_core.h"
 #include "wnla_rlc_core.h"
 #include "wnla_prove_core.h"
+#include "wire_core.h"
 
 #define BPPP_BLOCK 64
 // One-lane-per-proof kernels of the u64 verifier: minimum waves per SIMD the register allocator must leave room for
@@ -134,6 +135,9 @@ __global__ __launch_bounds__(BPPP_BLOCK) void k_commit_value(bppp::VerifyWs ws, 
 __global__ __launch_bounds__(256) void k_sec1_expand(uint8_t* commitments64, uint8_t* proofs928, const uint8_t* commitments33, const uint8_t* proofs525, size_t n);
 __global__ __launch_bounds__(256) void k_sec1_compress(uint8_t* commitments33, uint8_t* proofs525, const uint8_t* commitments64,
                                                        const uint8_t* proofs928, size_t n);
+// the generic proofs' wire form (k_wire.hip): expand / compress over a layout descriptor
+__global__ __launch_bounds__(256) void k_wire_expand(bppp::WireMap m);
+__global__ __launch_bounds__(256) void k_wire_compress(bppp::WireMap m);
 // the u64 prover's stages that touch the transcript run once per distinct sponge position in the wavefront (for_each_position_group
 // above; one trip unless the caller passed per-proof pre-loaded transcripts of different lengths) -- shared by k_prove.hip and k_prove_w2.hip
 #if defined(__HIPCC__)

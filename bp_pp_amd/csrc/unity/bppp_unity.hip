@@ -16,3 +16,4 @@
 #include "../k_prove_w2.hip"
 #include "../k_generic.hip"
 #include "../k_gprove.hip"
+#include "../k_wire.hip"

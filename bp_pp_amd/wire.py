@@ -147,3 +147,83 @@ def doc_to_circuit_proof(doc: Dict) -> bytes:
     if reciprocal:
         out += pt(doc["r"])
     return out + b"".join(sc(h) for h in cp["l"]) + b"".join(sc(h) for h in cp["n"])
+
+
+# ---------------------------------------------------------------- generic proofs in the wire form (any shape)
+# The byte form of the serializable mirrors above: the generic C-ABI layout with every point SEC1-compressed in place (33 bytes) and
+# the scalars as they are, field order unchanged -- what bppp_{reciprocal,circuit,wnla}_{verify,prove}_batch_sec1 take and give
+# (include/bppp.h).  A proof of P points and S scalars: 64 P + 32 S bytes in the ABI form, 33 P + 32 S in the wire form.
+KINDS = ("reciprocal", "circuit", "wnla")
+
+
+def proof_points(kind: str, rounds: int) -> int:
+    """Points of one proof: c_l, c_r, c_o, c_s | r | x (| reciprocal r); for "wnla" the points of ONE of the r / x arrays."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}")
+    return {"reciprocal": 5 + 2 * rounds, "circuit": 4 + 2 * rounds, "wnla": rounds}[kind]
+
+
+def abi_proof_bytes(kind: str, rounds: int, nl: int = 0, nn: int = 0) -> int:
+    """Bytes of one proof in the 64-byte C-ABI form ("wnla": one r / x array; its l / n arrays are 32-byte scalars either way)."""
+    return 64 * proof_points(kind, rounds) + (0 if kind == "wnla" else 32 * (nl + nn))
+
+
+def sec1_proof_bytes(kind: str, rounds: int, nl: int = 0, nn: int = 0) -> int:
+    """Bytes of one proof in the wire form: 33 P + 32 S ("wnla": one r / x array, 33 rounds)."""
+    return 33 * proof_points(kind, rounds) + (0 if kind == "wnla" else 32 * (nl + nn))
+
+
+def generic_abi_to_sec1(proof: bytes, n_points: int) -> bytes:
+    """The first n_points 64-byte points compressed in place, the rest (scalars) copied: a proof, a commitment or a row of them."""
+    proof = bytes(proof)
+    if len(proof) < 64 * n_points or (len(proof) - 64 * n_points) % 32:
+        raise ValueError(f"{len(proof)} bytes do not hold {n_points} points followed by 32-byte scalars")
+    return b"".join(compress_point(proof[64 * i:64 * i + 64]) for i in range(n_points)) + proof[64 * n_points:]
+
+
+def generic_sec1_to_abi(proof33: bytes, n_points: int, n_scalars: int) -> bytes:
+    """Inverse of generic_abi_to_sec1 (ValueError on a wrong length or an undecodable point)."""
+    proof33 = bytes(proof33)
+    if len(proof33) != 33 * n_points + 32 * n_scalars:
+        raise ValueError(f"{len(proof33)} bytes, the shape needs {33 * n_points + 32 * n_scalars}")
+    return b"".join(decompress_point(proof33[33 * i:33 * i + 33]) for i in range(n_points)) + proof33[33 * n_points:]
+
+
+def sec1_proof_to_doc(proof33: bytes, rounds: int, nl: int, nn: int, reciprocal: bool = False) -> Dict:
+    """One reciprocal / circuit proof in the wire form -> its serializable document (circuit_proof_to_doc's shapes)."""
+    kind = "reciprocal" if reciprocal else "circuit"
+    abi = generic_sec1_to_abi(proof33, proof_points(kind, rounds), nl + nn)
+    return circuit_proof_to_doc(abi, rounds, nl, nn, reciprocal)
+
+
+def doc_to_sec1_proof(doc: Dict) -> bytes:
+    """Inverse of sec1_proof_to_doc (either shape, told apart as doc_to_circuit_proof does)."""
+    cp = doc["circuit_proof"] if "circuit_proof" in doc else doc
+    kind = "reciprocal" if "circuit_proof" in doc else "circuit"
+    return generic_abi_to_sec1(doc_to_circuit_proof(doc), proof_points(kind, len(cp["r"])))
+
+
+def wnla_sec1_to_doc(proof_r33: bytes, proof_x33: bytes, proof_l: bytes, proof_n: bytes) -> Dict:
+    """The four arrays of bppp_wnla_{prove,verify}_batch_sec1 for ONE instance -> wnla::SerializableProof document."""
+    rounds = len(proof_r33) // 33
+    if len(proof_r33) != 33 * rounds or len(proof_x33) != 33 * rounds:
+        raise ValueError("proof_r and proof_x must hold the same number of 33-byte points")
+    return wnla_proof_to_doc(generic_sec1_to_abi(proof_r33, rounds, 0), generic_sec1_to_abi(proof_x33, rounds, 0), proof_l, proof_n)
+
+
+def doc_to_wnla_sec1(doc: Dict):
+    """wnla::SerializableProof document -> (proof_r33, proof_x33, proof_l, proof_n) bytes for one instance (points checked: ValueError)."""
+    if len(doc["r"]) != len(doc["x"]):
+        raise ValueError("r and x must have the same length")
+    pt = lambda h: compress_point(decompress_point(hex_to_point(h)))
+    sc = lambda h: bytes.fromhex(h).rjust(32, b"\0")
+    return (b"".join(pt(h) for h in doc["r"]), b"".join(pt(h) for h in doc["x"]), b"".join(sc(h) for h in doc["l"]),
+            b"".join(sc(h) for h in doc["n"]))
+
+
+def generic_sec1_to_json(proof33: bytes, rounds: int, nl: int, nn: int, reciprocal: bool = False) -> str:
+    return json.dumps(sec1_proof_to_doc(proof33, rounds, nl, nn, reciprocal), indent=2)
+
+
+def json_to_generic_sec1(text: str) -> bytes:
+    return doc_to_sec1_proof(json.loads(text))

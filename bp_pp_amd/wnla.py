@@ -151,6 +151,53 @@ class WeightNormLinearArgument:
                                                        proof_n.shape[1], acc.ctypes.data, st.ctypes.data))
         return acc, st
 
+    # ---- the wire form (SEC1-compressed points: wnla::SerializableProof, wnla.rs:33-38; bp_pp_amd/wire.py)
+    def verify_batch_sec1(self, label: bytes, commitments33, c, rho, mu, proof_r33, proof_x33, proof_l, proof_n):
+        """verify_batch over 33-byte points: commitments [B, 33], proof_r / proof_x [B, rounds, 33] -> (accept, status); the points are
+        decompressed on the device (bppp_wnla_verify_batch_sec1)."""
+        commitments33 = _u8(commitments33, (-1, 33))
+        B = commitments33.shape[0]
+        c = _u8(c, (B, self.nh, 32))
+        rho, mu = _u8(rho, (B, 32)), _u8(mu, (B, 32))
+        proof_r33, proof_x33 = _u8(proof_r33, (B, -1, 33)), _u8(proof_x33, (B, -1, 33))
+        if proof_r33.shape[1] != proof_x33.shape[1]:
+            return np.zeros(B, np.uint8), np.zeros(B, np.int32)          # wnla.rs:76-78
+        proof_l, proof_n = _u8(proof_l, (B, -1, 32)), _u8(proof_n, (B, -1, 32))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.lib().bppp_wnla_verify_batch_sec1(self._ctx, label, len(label), B, commitments33.ctypes.data, c.ctypes.data,
+                                                            rho.ctypes.data, mu.ctypes.data, proof_r33.shape[1], proof_r33.ctypes.data,
+                                                            proof_x33.ctypes.data, proof_l.ctypes.data, proof_l.shape[1], proof_n.ctypes.data,
+                                                            proof_n.shape[1], acc.ctypes.data, st.ctypes.data))
+        return acc, st
+
+    def verify_batch_sec1_device(self, label: bytes, n: int, d_commitments33: int, d_c: int, d_rho: int, d_mu: int, rounds: int,
+                                 d_proof_r33: int, d_proof_x33: int, d_proof_l: int, nl: int, d_proof_n: int, nn: int, d_accept: int,
+                                 d_status: int = 0) -> None:
+        """verify_batch_device over 33-byte points (raw device pointers), asynchronous on the context's stream."""
+        _capi.check(_capi.lib().bppp_wnla_verify_batch_sec1_device(self._ctx, label, len(label), n, d_commitments33, d_c, d_rho, d_mu, rounds,
+                                                                   d_proof_r33, d_proof_x33, d_proof_l, nl, d_proof_n, nn, d_accept,
+                                                                   d_status or None))
+
+    def prove_batch_sec1(self, label: bytes, commitments33, c, rho, mu, l, n):
+        """prove_batch with 33-byte points in and out: commitments [B, 33] -> (proof_r [B, rounds, 33], proof_x, proof_l, proof_n,
+        status); an undecodable commitment gives BPPP_ST_BAD_ENCODING and a zeroed proof."""
+        import ctypes as C
+        commitments33 = _u8(commitments33, (-1, 33))
+        B = commitments33.shape[0]
+        c = _u8(c, (B, self.nh, 32))
+        rho, mu = _u8(rho, (B, 32)), _u8(mu, (B, 32))
+        l, n = _u8(l, (B, -1, 32)), _u8(n, (B, -1, 32))
+        rounds, nl_f, nn_f = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _capi.lib().bppp_wnla_proof_shape(l.shape[1], n.shape[1], C.byref(rounds), C.byref(nl_f), C.byref(nn_f))
+        pr, px = np.zeros((B, rounds.value, 33), np.uint8), np.zeros((B, rounds.value, 33), np.uint8)
+        pl, pn = np.zeros((B, nl_f.value, 32), np.uint8), np.zeros((B, nn_f.value, 32), np.uint8)
+        st = np.zeros(B, np.int32)
+        _capi.check(_capi.lib().bppp_wnla_prove_batch_sec1(self._ctx, label, len(label), B, commitments33.ctypes.data, c.ctypes.data,
+                                                           rho.ctypes.data, mu.ctypes.data, l.ctypes.data, l.shape[1], n.ctypes.data,
+                                                           n.shape[1], pr.ctypes.data, px.ctypes.data, pl.ctypes.data, pn.ctypes.data,
+                                                           st.ctypes.data))
+        return pr, px, pl, pn, st
+
 
 class ReciprocalRangeProofProtocol:
     """Mirror of `range_proof::reciprocal::ReciprocalRangeProofProtocol` (reciprocal.rs:64-107) for runtime dim_nd / dim_np,
@@ -227,6 +274,42 @@ class ReciprocalRangeProofProtocol:
                                                              acc.ctypes.data, st.ctypes.data))
         return acc, st
 
+    # ---- the wire form (SEC1-compressed points: reciprocal::SerializableProof, reciprocal.rs:37-41; bp_pp_amd/wire.py)
+    def verify_batch_sec1(self, label: bytes, commitments33, proofs33, rounds: int, nl: int, nn: int):
+        """verify_batch over 33-byte points: commitments [B, 33], proofs [B, 33 (5 + 2 rounds) + 32 (nl + nn)] -> (accept, status);
+        decompressed on the device (bppp_reciprocal_verify_batch_sec1)."""
+        commitments33 = _u8(commitments33, (-1, 33))
+        B = commitments33.shape[0]
+        proofs33 = _u8(proofs33, (B, 33 * (5 + 2 * rounds) + 32 * (nl + nn)))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.lib().bppp_reciprocal_verify_batch_sec1(self._w._ctx, label, len(label), B, self.dim_nd, self.dim_np,
+                                                                  commitments33.ctypes.data, proofs33.ctypes.data, rounds, nl, nn,
+                                                                  acc.ctypes.data, st.ctypes.data))
+        return acc, st
+
+    def verify_batch_sec1_device(self, label: bytes, n: int, d_commitments33: int, d_proofs33: int, rounds: int, nl: int, nn: int,
+                                 d_accept: int, d_status: int) -> None:
+        """verify_batch_device over 33-byte points (raw device addresses); asynchronous on the context's stream."""
+        _capi.check(_capi.lib().bppp_reciprocal_verify_batch_sec1_device(self._w._ctx, label, len(label), n, self.dim_nd, self.dim_np,
+                                                                         d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status))
+
+    def prove_batch_sec1(self, label: bytes, commitments33, x, s, digits, m, rnd):
+        """prove_batch with 33-byte points in and out: commitments [B, 33] -> (proofs [B, 33 (5 + 2 rounds) + 32 (nl + nn)], status,
+        (rounds, nl, nn)); an undecodable commitment gives BPPP_ST_BAD_ENCODING and a zeroed proof."""
+        import ctypes as C
+        commitments33 = _u8(commitments33, (-1, 33))
+        B = commitments33.shape[0]
+        x, s = _u8(x, (B, 32)), _u8(s, (B, 32))
+        digits, m = _u8(digits, (B, self.dim_nd, 32)), _u8(m, (B, self.dim_np, 32))
+        rnd = _u8(rnd, (B, 20 + 2 * self.dim_nd, 32))
+        rounds, nl, nn = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _capi.lib().bppp_wnla_proof_shape(self._w.nh, self._w.ng, C.byref(rounds), C.byref(nl), C.byref(nn))
+        proofs = np.zeros((B, 33 * (5 + 2 * rounds.value) + 32 * (nl.value + nn.value)), np.uint8)
+        st = np.zeros(B, np.int32)
+        _capi.check(_capi.lib().bppp_reciprocal_prove_batch_sec1(self._w._ctx, label, len(label), B, self.dim_nd, self.dim_np,
+                                                                 commitments33.ctypes.data, x.ctypes.data, s.ctypes.data, digits.ctypes.data,
+                                                                 m.ctypes.data, rnd.ctypes.data, proofs.ctypes.data, st.ctypes.data))
+        return proofs, st, (rounds.value, nl.value, nn.value)
 
     def verify_one(self, commitment: bytes, proof: bytes, rounds: int, nl: int, nn: int, transcript):
         """`ReciprocalRangeProofProtocol::verify(&self, commitment, proof, t)` (reciprocal.rs:98-107) for ONE instance, from any number
@@ -405,3 +488,40 @@ class ArithmeticCircuit:
         _capi.check(_capi.lib().bppp_circuit_verify_batch(self._w._ctx, self._circuit, label, len(label), B, commitments.ctypes.data,
                                                           proofs.ctypes.data, rounds, nl, nn, acc.ctypes.data, st.ctypes.data))
         return acc, st
+
+    # ---- the wire form (SEC1-compressed points: circuit::SerializableProof, circuit.rs:36-46; bp_pp_amd/wire.py)
+    def verify_batch_sec1(self, label: bytes, commitments33, proofs33, rounds: int, nl: int, nn: int):
+        """verify_batch over 33-byte points: commitments [B, k, 33], proofs [B, 33 (4 + 2 rounds) + 32 (nl + nn)] -> (accept, status);
+        decompressed on the device (bppp_circuit_verify_batch_sec1)."""
+        commitments33 = _u8(commitments33, (-1, self.k, 33))
+        B = commitments33.shape[0]
+        proofs33 = _u8(proofs33, (B, 33 * (4 + 2 * rounds) + 32 * (nl + nn)))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.lib().bppp_circuit_verify_batch_sec1(self._w._ctx, self._circuit, label, len(label), B, commitments33.ctypes.data,
+                                                               proofs33.ctypes.data, rounds, nl, nn, acc.ctypes.data, st.ctypes.data))
+        return acc, st
+
+    def verify_batch_sec1_device(self, label: bytes, n: int, d_commitments33: int, d_proofs33: int, rounds: int, nl: int, nn: int,
+                                 d_accept: int, d_status: int = 0) -> None:
+        """verify_batch_device over 33-byte points (raw device pointers), asynchronous on the context's stream."""
+        _capi.check(_capi.lib().bppp_circuit_verify_batch_sec1_device(self._w._ctx, self._circuit, label, len(label), n, d_commitments33,
+                                                                      d_proofs33, rounds, nl, nn, d_accept, d_status or None))
+
+    def prove_batch_sec1(self, label: bytes, v_commitments33, v, s_v, w_l, w_r, w_o, rnd):
+        """prove_batch with 33-byte points in and out: v_commitments [B, k, 33] -> (proofs [B, 33 (4 + 2 rounds) + 32 (nl + nn)],
+        status, (rounds, nl, nn)); an undecodable commitment gives BPPP_ST_BAD_ENCODING and a zeroed proof."""
+        import ctypes as C
+        v_commitments33 = _u8(v_commitments33, (-1, self.k, 33))
+        B = v_commitments33.shape[0]
+        v, s_v = _u8(v, (B, self.k, self.dim_nv, 32)), _u8(s_v, (B, self.k, 32))
+        w_l, w_r = _u8(w_l, (B, self.dim_nm, 32)), _u8(w_r, (B, self.dim_nm, 32))
+        w_o = _u8(w_o, (B, self.dim_no, 32))
+        rnd = _u8(rnd, (B, 18 + self.dim_nv + self.dim_nm, 32))
+        rounds, nl, nn = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _capi.lib().bppp_wnla_proof_shape(self._w.nh, self._w.ng, C.byref(rounds), C.byref(nl), C.byref(nn))
+        proofs = np.zeros((B, 33 * (4 + 2 * rounds.value) + 32 * (nl.value + nn.value)), np.uint8)
+        st = np.zeros(B, np.int32)
+        _capi.check(_capi.lib().bppp_circuit_prove_batch_sec1(self._w._ctx, self._circuit, label, len(label), B, v_commitments33.ctypes.data,
+                                                              v.ctypes.data, s_v.ctypes.data, w_l.ctypes.data, w_r.ctypes.data, w_o.ctypes.data,
+                                                              rnd.ctypes.data, proofs.ctypes.data, st.ctypes.data))
+        return proofs, st, (rounds.value, nl.value, nn.value)

@@ -65,6 +65,15 @@ extern "C" {
     pub fn bppp_wnla_proof_shape(nl: usize, nn: usize, rounds: *mut usize, nl_out: *mut usize, nn_out: *mut usize);
     pub fn bppp_wnla_prove_batch(ctx: *mut BpppCtx, label: *const u8, label_len: usize, n: usize, commitments: *const u8, c: *const u8, rho: *const u8, mu: *const u8, l: *const u8, nl: usize, n_vec: *const u8, nn: usize, proof_r: *mut u8, proof_x: *mut u8, proof_l: *mut u8, proof_n: *mut u8, status: *mut i32) -> c_int;
     pub fn bppp_reciprocal_verify_batch(ctx: *mut BpppCtx, label: *const u8, label_len: usize, n: usize, dim_nd: usize, dim_np: usize, commitments: *const u8, proofs: *const u8, rounds: usize, nl: usize, nn: usize, accept: *mut u8, status: *mut i32) -> c_int;
+    pub fn bppp_reciprocal_verify_batch_sec1(ctx: *mut BpppCtx, label: *const u8, label_len: usize, n: usize, dim_nd: usize, dim_np: usize, commitments33: *const u8, proofs33: *const u8, rounds: usize, nl: usize, nn: usize, accept: *mut u8, status: *mut i32) -> c_int;
+    pub fn bppp_reciprocal_verify_batch_sec1_device(ctx: *mut BpppCtx, label: *const u8, label_len: usize, n: usize, dim_nd: usize, dim_np: usize, d_commitments33: *const c_void, d_proofs33: *const c_void, rounds: usize, nl: usize, nn: usize, d_accept: *mut c_void, d_status: *mut c_void) -> c_int;
+    pub fn bppp_circuit_verify_batch_sec1(ctx: *mut BpppCtx, circuit: *const BpppCircuit, label: *const u8, label_len: usize, n: usize, commitments33: *const u8, proofs33: *const u8, rounds: usize, nl: usize, nn: usize, accept: *mut u8, status: *mut i32) -> c_int;
+    pub fn bppp_circuit_verify_batch_sec1_device(ctx: *mut BpppCtx, circuit: *const BpppCircuit, label: *const u8, label_len: usize, n: usize, d_commitments33: *const c_void, d_proofs33: *const c_void, rounds: usize, nl: usize, nn: usize, d_accept: *mut c_void, d_status: *mut c_void) -> c_int;
+    pub fn bppp_wnla_verify_batch_sec1(ctx: *mut BpppCtx, label: *const u8, label_len: usize, n: usize, commitments33: *const u8, c: *const u8, rho: *const u8, mu: *const u8, rounds: usize, proof_r33: *const u8, proof_x33: *const u8, proof_l: *const u8, nl: usize, proof_n: *const u8, nn: usize, accept: *mut u8, status: *mut i32) -> c_int;
+    pub fn bppp_wnla_verify_batch_sec1_device(ctx: *mut BpppCtx, label: *const u8, label_len: usize, n: usize, d_commitments33: *const c_void, d_c: *const c_void, d_rho: *const c_void, d_mu: *const c_void, rounds: usize, d_proof_r33: *const c_void, d_proof_x33: *const c_void, d_proof_l: *const c_void, nl: usize, d_proof_n: *const c_void, nn: usize, d_accept: *mut c_void, d_status: *mut c_void) -> c_int;
+    pub fn bppp_reciprocal_prove_batch_sec1(ctx: *mut BpppCtx, label: *const u8, label_len: usize, n: usize, dim_nd: usize, dim_np: usize, commitments33: *const u8, x: *const u8, s: *const u8, digits: *const u8, m: *const u8, rnd: *const u8, proofs33: *mut u8, status: *mut i32) -> c_int;
+    pub fn bppp_circuit_prove_batch_sec1(ctx: *mut BpppCtx, circuit: *const BpppCircuit, label: *const u8, label_len: usize, n: usize, v_commitments33: *const u8, v: *const u8, s_v: *const u8, w_l: *const u8, w_r: *const u8, w_o: *const u8, rnd: *const u8, proofs33: *mut u8, status: *mut i32) -> c_int;
+    pub fn bppp_wnla_prove_batch_sec1(ctx: *mut BpppCtx, label: *const u8, label_len: usize, n: usize, commitments33: *const u8, c: *const u8, rho: *const u8, mu: *const u8, l: *const u8, nl: usize, n_vec: *const u8, nn: usize, proof_r33: *mut u8, proof_x33: *mut u8, proof_l: *mut u8, proof_n: *mut u8, status: *mut i32) -> c_int;
     pub fn bppp_derive_generators(seed: *const u8, seed_len: usize, first_index: usize, n: usize, out: *mut u8) -> c_int;
     pub fn bppp_ctx_save_tables(ctx: *mut BpppCtx, path: *const c_char) -> c_int;
     pub fn bppp_ctx_create_from_tables(out: *mut *mut BpppCtx, path: *const c_char, device: c_int) -> c_int;

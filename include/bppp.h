@@ -388,6 +388,54 @@ BPPP_API int bppp_reciprocal_verify_batch(bppp_ctx* ctx, const uint8_t* label, s
                                           const uint8_t* commitments /* n x 64 */, const uint8_t* proofs, size_t rounds, size_t nl,
                                           size_t nn, uint8_t* accept /* n */, int32_t* status /* n or NULL */);
 
+/* ---- the wire form of the generic proofs: SEC1-compressed points (reciprocal.rs:37-41, circuit.rs:36-46, wnla.rs:33-38) ----
+ * The crate's SerializableProof types hold k256 `AffinePoint`s: the byte form is the 64-byte layout of the twin entry point with every
+ * point compressed in place to 33 bytes (02 | 03 by the parity of y, then x; the identity is 33 zero bytes) and the 32-byte scalars
+ * as they are, field order unchanged.  A proof of P points and S scalars is 33 P + 32 S bytes:
+ *   reciprocal  c_l, c_r, c_o, c_s | r[rounds] | x[rounds] | reciprocal r | l[nl] | n[nn]    P = 5 + 2 rounds, S = nl + nn
+ *   circuit     c_l, c_r, c_o, c_s | r[rounds] | x[rounds] | l[nl] | n[nn]                   P = 4 + 2 rounds, S = nl + nn
+ *   WNLA        proof_r, proof_x: n x rounds x 33 (proof_l / proof_n stay 32-byte scalars)
+ * commitments are n x 33 (reciprocal, WNLA) or n x k x 33 (circuit).  Each entry point takes the arguments of its 64-byte twin and gives
+ * exactly the twin's error codes, accept bits and statuses for the expanded input; the points are decompressed on the device.  An
+ * undecodable point (tag other than 02 / 03 in a non-zero encoding, x >= p, x^3 + 7 not a square) flags its instance
+ * BPPP_ST_BAD_ENCODING.  The _device forms are asynchronous on the context's stream, like their twins; the reciprocal (16, 16) u64
+ * shape runs on bppp_u64_verify_batch_sec1's path (the same 33 + 525 bytes). */
+BPPP_API int bppp_reciprocal_verify_batch_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                               const uint8_t* commitments33 /* n x 33 */, const uint8_t* proofs33, size_t rounds, size_t nl,
+                                               size_t nn, uint8_t* accept /* n */, int32_t* status /* n or NULL */);
+BPPP_API int bppp_reciprocal_verify_batch_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
+                                                      size_t dim_np, const void* d_commitments33, const void* d_proofs33, size_t rounds,
+                                                      size_t nl, size_t nn, void* d_accept, void* d_status);
+BPPP_API int bppp_circuit_verify_batch_sec1(bppp_ctx* ctx, const bppp_circuit* circuit, const uint8_t* label, size_t label_len, size_t n,
+                                            const uint8_t* commitments33 /* n x k x 33 */, const uint8_t* proofs33, size_t rounds, size_t nl,
+                                            size_t nn, uint8_t* accept /* n */, int32_t* status /* n or NULL */);
+BPPP_API int bppp_circuit_verify_batch_sec1_device(bppp_ctx* ctx, const bppp_circuit* circuit, const uint8_t* label, size_t label_len,
+                                                   size_t n, const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl,
+                                                   size_t nn, void* d_accept, void* d_status);
+BPPP_API int bppp_wnla_verify_batch_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                         const uint8_t* commitments33 /* n x 33 */, const uint8_t* c /* n x nh x 32 */,
+                                         const uint8_t* rho /* n x 32 */, const uint8_t* mu /* n x 32 */, size_t rounds,
+                                         const uint8_t* proof_r33 /* n x rounds x 33 */, const uint8_t* proof_x33 /* n x rounds x 33 */,
+                                         const uint8_t* proof_l /* n x nl x 32 */, size_t nl, const uint8_t* proof_n /* n x nn x 32 */,
+                                         size_t nn, uint8_t* accept /* n */, int32_t* status /* n or NULL */);
+BPPP_API int bppp_wnla_verify_batch_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33,
+                                                const void* d_c, const void* d_rho, const void* d_mu, size_t rounds, const void* d_proof_r33,
+                                                const void* d_proof_x33, const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn,
+                                                void* d_accept, void* d_status);
+/* The provers' wire form: input commitments 33-byte (decompressed on the device; an undecodable one gives that instance
+ * BPPP_ST_BAD_ENCODING and a zeroed proof), output proof points 33-byte (compressed on the device before the copy back). */
+BPPP_API int bppp_reciprocal_prove_batch_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                              const uint8_t* commitments33, const uint8_t* x, const uint8_t* s, const uint8_t* digits,
+                                              const uint8_t* m, const uint8_t* rnd, uint8_t* proofs33, int32_t* status /* n or NULL */);
+BPPP_API int bppp_circuit_prove_batch_sec1(bppp_ctx* ctx, const bppp_circuit* circuit, const uint8_t* label, size_t label_len, size_t n,
+                                           const uint8_t* v_commitments33, const uint8_t* v, const uint8_t* s_v, const uint8_t* w_l,
+                                           const uint8_t* w_r, const uint8_t* w_o, const uint8_t* rnd, uint8_t* proofs33,
+                                           int32_t* status /* n or NULL */);
+BPPP_API int bppp_wnla_prove_batch_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
+                                        const uint8_t* c, const uint8_t* rho, const uint8_t* mu, const uint8_t* l, size_t nl,
+                                        const uint8_t* n_vec, size_t nn, uint8_t* proof_r33, uint8_t* proof_x33, uint8_t* proof_l,
+                                        uint8_t* proof_n, int32_t* status /* n or NULL */);
+
 /* ---- setup: the step before the path (benches/range_proof.rs:18-20, u64_proof.rs:37) ----
  * bppp_derive_generators: n reproducible generators with unknown discrete logarithms, indices first_index .. first_index + n - 1 of
  * the stream defined by `seed` (try-and-increment: x = SHAKE256(seed || "bppp-gen" || u32le(index) || u32le(counter)) as a
