@@ -37,6 +37,8 @@ EXPORTS = [
     "bppp_reciprocal_verify_batch_sec1", "bppp_reciprocal_verify_batch_sec1_device", "bppp_circuit_verify_batch_sec1",
     "bppp_circuit_verify_batch_sec1_device", "bppp_wnla_verify_batch_sec1", "bppp_wnla_verify_batch_sec1_device",
     "bppp_reciprocal_prove_batch_sec1", "bppp_circuit_prove_batch_sec1", "bppp_wnla_prove_batch_sec1",
+    "bppp_draw_scalars", "bppp_draw_scalars_device", "bppp_u64_prove_batch_seeded", "bppp_u64_prove_batch_seeded_device",
+    "bppp_u64_prove_batch_seeded_sharded", "bppp_reciprocal_prove_batch_seeded", "bppp_circuit_prove_batch_seeded",
 ]
 
 _lib = None
@@ -195,7 +197,19 @@ def lib():
         L.bppp_reciprocal_prove_batch_sec1.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bppp_circuit_prove_batch_sec1.argtypes = [vp, vp, u8p, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bppp_wnla_prove_batch_sec1.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp]
-        for name in EXPORTS[-9:]:
+        for name in EXPORTS[-16:-7]:
+            getattr(L, name).restype = i32
+    # the seeded provers: (seed, stream_base) in place of rnd
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_draw_scalars"):
+        u64 = C.c_uint64
+        L.bppp_draw_scalars.argtypes = [u8p, u64, sz, sz, vp]
+        L.bppp_draw_scalars_device.argtypes = [vp, u8p, u64, sz, sz, vp]
+        L.bppp_u64_prove_batch_seeded.argtypes = [vp, u8p, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        L.bppp_u64_prove_batch_seeded_device.argtypes = [vp, u8p, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        L.bppp_u64_prove_batch_seeded_sharded.argtypes = [vp, u8p, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        L.bppp_reciprocal_prove_batch_seeded.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, vp, vp, vp, u8p, u64, vp, vp]
+        L.bppp_circuit_prove_batch_seeded.argtypes = [vp, vp, u8p, sz, sz, vp, vp, vp, vp, vp, vp, u8p, u64, vp, vp]
+        for name in EXPORTS[-7:]:
             getattr(L, name).restype = i32
     L.bppp_strerror.argtypes = [i32]
     L.bppp_strerror.restype = C.c_char_p

@@ -331,6 +331,7 @@ void bppp_ctx_destroy(bppp_ctx* c) {
     if (c->d_gtab) (void)hipFree(c->d_gtab);
     if (c->d_expand) (void)hipFree(c->d_expand);
     if (c->d_wire) (void)hipFree(c->d_wire);
+    if (c->d_draw) (void)hipFree(c->d_draw);
     if (c->d_flags) (void)hipFree(c->d_flags);
     if (c->d_rlc_hist) (void)hipFree(c->d_rlc_hist);
     if (c->h_rlc_hist) (void)hipHostFree(c->h_rlc_hist);
@@ -502,7 +503,7 @@ int bppp_ctx_synchronize(bppp_ctx* c) {
 
 size_t bppp_ctx_device_bytes(const bppp_ctx* c) {
     if (!c) return 0;
-    return c->table_bytes + c->table_hi_bytes + (c->borrows_table_ct ? 0 : c->table_ct_bytes) + c->ws_bytes + c->straus_bytes + c->vtab_bytes + c->rlc_bytes + c->bkt_bytes + c->pws_bytes + c->stage_bytes + c->io_bytes + c->blob_bytes + c->txio_bytes + c->gws_bytes + c->gtab_bytes + c->wire_bytes + (size_t)c->nbases * sizeof(apt);
+    return c->table_bytes + c->table_hi_bytes + (c->borrows_table_ct ? 0 : c->table_ct_bytes) + c->ws_bytes + c->straus_bytes + c->vtab_bytes + c->rlc_bytes + c->bkt_bytes + c->pws_bytes + c->stage_bytes + c->io_bytes + c->blob_bytes + c->txio_bytes + c->gws_bytes + c->gtab_bytes + c->wire_bytes + c->draw_bytes + (size_t)c->nbases * sizeof(apt);
 }
 
 int bppp_ctx_enable_timing(bppp_ctx* c, int enable) {

@@ -1043,15 +1043,18 @@ int bppp_wnla_prove_batch_transcript(bppp_ctx* c, size_t n, const uint8_t* state
 // ArithmeticCircuit::prove (circuit.rs:260-556) for n instances of a shared circuit.
 static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, const HostTranscripts* tx, size_t n,
                               const uint8_t* v_commitments, const uint8_t* v, const uint8_t* s_v, const uint8_t* w_l, const uint8_t* w_r,
-                              const uint8_t* w_o, const uint8_t* rnd, uint8_t* proofs, int32_t* status, bool sec1 = false) {
+                              const uint8_t* w_o, const uint8_t* rnd, uint8_t* proofs, int32_t* status, bool sec1 = false,
+                              const uint8_t* seed = nullptr, uint64_t stream_base = 0) {
     // sec1 (bppp_circuit_prove_batch_sec1): v_commitments n x k x 33 in, proofs in the 33-byte form out (converted on the device)
-    if (!c || !q || !label_ok(label, label_len) || !v_commitments || !v || !s_v || !w_l || !w_r || !rnd || !proofs) return BPPP_ERR_INVALID_ARG;
+    if (!c || !q || !label_ok(label, label_len) || !v_commitments || !v || !s_v || !w_l || !w_r || (!rnd && !seed) || !proofs) return BPPP_ERR_INVALID_ARG;
     const CircuitDev& cd = q->cd;
     if ((cd.no && !w_o) || cd.nm > c->ng || cd.nv + 9 > c->nh) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t NB = (size_t)c->nbases, NG = (size_t)c->ng, NH = (size_t)c->nh, k = (size_t)cd.k, nm = (size_t)cd.nm, nv = (size_t)cd.nv,
                  no = (size_t)cd.no, nl = (size_t)cd.nl, n_rnd = 18 + nv + nm;
+    // seeded (bppp_*_prove_batch_seeded): the draws are made on the device below instead of uploaded
+    if (seed && !draw_args_ok(seed, stream_base, n, n_rnd)) return BPPP_ERR_INVALID_ARG;
     size_t rounds, nl_f, nn_f;
     wnla_proof_shape(NH, NG, rounds, nl_f, nn_f);
     const size_t proof_bytes = 64 * (4 + 2 * rounds) + 32 * (nl_f + nn_f);
@@ -1086,7 +1089,9 @@ static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t*
     HIP_TRY(hipMemcpyAsync(d + o_wl, w_l, n * nm * 32, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_wr, w_r, n * nm * 32, hipMemcpyHostToDevice, s));
     if (no) HIP_TRY(hipMemcpyAsync(d + o_wo, w_o, n * no * 32, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_rnd, rnd, n * n_rnd * 32, hipMemcpyHostToDevice, s));
+    DrawWipe wipe = {seed ? d + o_rnd : nullptr, n * n_rnd * 32, s};
+    if (seed) { const int rc_d = draw_enqueue(s, seed, stream_base, n, n_rnd, d + o_rnd); if (rc_d != BPPP_OK) return rc_d; }
+    else HIP_TRY(hipMemcpyAsync(d + o_rnd, rnd, n * n_rnd * 32, hipMemcpyHostToDevice, s));
     CircuitProveWs p;
     std::memset(&p, 0, sizeof p);
     p.N = n; p.cd = cd; p.NG = c->ng; p.NH = c->nh; p.n_rnd = (int)n_rnd; p.rnd_stride = n_rnd * 32; p.part = q->d_part;
@@ -1157,6 +1162,7 @@ static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t*
         if (status) HIP_TRY(hipMemcpyAsync(status, p.status, n * 4, hipMemcpyDeviceToHost, s));
         rc = txd.finish(tx, p.tio, p.base, p.tstate, n, p.status, s);
         if (rc != BPPP_OK) return rc;
+        HIP_TRY(wipe.now());
         HIP_TRY(hipStreamSynchronize(s));
         return BPPP_OK;
     }
@@ -1173,6 +1179,7 @@ static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t*
     HIP_TRY(hipMemcpyAsync(st.data(), d + o_st, n * 4, hipMemcpyDeviceToHost, s));
     rc = txd.finish(tx, p.tio, p.base, p.tstate, n, p.status, s);
     if (rc != BPPP_OK) return rc;
+    HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
     HIP_TRY(hipStreamSynchronize(s));
     for (size_t i = 0; i < n; i++) {
         uint8_t* o = proofs + i * proof_bytes;
@@ -1206,9 +1213,10 @@ int bppp_circuit_prove_batch_transcript(bppp_ctx* c, const bppp_circuit* q, size
 // ReciprocalRangeProofProtocol::prove (reciprocal.rs:110-146) for runtime dim_nd / dim_np.
 static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, const HostTranscripts* tx, size_t n, size_t dim_nd, size_t dim_np,
                             const uint8_t* commitments, const uint8_t* x, const uint8_t* sblind, const uint8_t* digits, const uint8_t* m,
-                            const uint8_t* rnd, uint8_t* proofs, int32_t* status, bool sec1 = false) {
+                            const uint8_t* rnd, uint8_t* proofs, int32_t* status, bool sec1 = false,
+                            const uint8_t* seed = nullptr, uint64_t stream_base = 0) {
     // sec1 (bppp_reciprocal_prove_batch_sec1): commitments n x 33 in, proofs in the 33-byte form out (converted on the device)
-    if (!c || !label_ok(label, label_len) || !commitments || !x || !sblind || !digits || !m || !rnd || !proofs) return BPPP_ERR_INVALID_ARG;
+    if (!c || !label_ok(label, label_len) || !commitments || !x || !sblind || !digits || !m || (!rnd && !seed) || !proofs) return BPPP_ERR_INVALID_ARG;
     if (dim_nd == 0 || dim_np == 0 || dim_nd > (size_t)c->ng || dim_nd + 10 > (size_t)c->nh || dim_np > dim_nd + 1 || dim_nd > 4096)
         return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
@@ -1217,6 +1225,8 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     recip_pattern_build(P, dim_nd, dim_np);
     const size_t NB = (size_t)c->nbases, NG = (size_t)c->ng, NH = (size_t)c->nh, nd = dim_nd, np = dim_np, nm = nd, nv = nd + 1, nl = nv,
                  n_rnd = 20 + 2 * nd;
+    // seeded (bppp_*_prove_batch_seeded): the draws are made on the device below instead of uploaded
+    if (seed && !draw_args_ok(seed, stream_base, n, n_rnd)) return BPPP_ERR_INVALID_ARG;
     size_t rounds, nl_f, nn_f;
     wnla_proof_shape(NH, NG, rounds, nl_f, nn_f);
     const size_t proof_bytes = 64 * (5 + 2 * rounds) + 32 * (nl_f + nn_f);
@@ -1263,7 +1273,10 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
         if (rc_e != BPPP_OK) return rc_e;
     } else HIP_TRY(up(o_com, commitments, n * 64));
     HIP_TRY(up(o_x, x, n * 32)); HIP_TRY(up(o_s, sblind, n * 32));
-    HIP_TRY(up(o_dig, digits, n * nd * 32)); HIP_TRY(up(o_m, m, n * np * 32)); HIP_TRY(up(o_rnd, rnd, n * n_rnd * 32));
+    HIP_TRY(up(o_dig, digits, n * nd * 32)); HIP_TRY(up(o_m, m, n * np * 32));
+    DrawWipe wipe = {seed ? d + o_rnd : nullptr, n * n_rnd * 32, s};
+    if (seed) { const int rc_d = draw_enqueue(s, seed, stream_base, n, n_rnd, d + o_rnd); if (rc_d != BPPP_OK) return rc_d; }
+    else HIP_TRY(up(o_rnd, rnd, n * n_rnd * 32));
     HIP_TRY(hipStreamSynchronize(s));                      // the pattern vectors live on this stack frame
     RecipProveWs r;
     std::memset(&r, 0, sizeof r);
@@ -1356,6 +1369,7 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
         if (status) HIP_TRY(hipMemcpyAsync(status, r.status, n * 4, hipMemcpyDeviceToHost, s));
         rc = txd.finish(tx, r.tio, r.base, r.tstate, n, r.status, s);
         if (rc != BPPP_OK) return rc;
+        HIP_TRY(wipe.now());
         HIP_TRY(hipStreamSynchronize(s));
         return BPPP_OK;
     }
@@ -1372,6 +1386,7 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     HIP_TRY(hipMemcpyAsync(st.data(), d + o_st, n * 4, hipMemcpyDeviceToHost, s));
     rc = txd.finish(tx, r.tio, r.base, r.tstate, n, r.status, s);
     if (rc != BPPP_OK) return rc;
+    HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
     HIP_TRY(hipStreamSynchronize(s));
     for (size_t i = 0; i < n; i++) {
         uint8_t* o = proofs + i * proof_bytes;
@@ -1636,5 +1651,24 @@ int bppp_wnla_prove_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_l
                            status, true);
 }
 
+
+// ---- seeded provers (include/bppp.h: "Seeded provers"): the rnd twins with the draws made on the device into the rnd region of the
+//      call's staging, which is cleared after the call
+int bppp_reciprocal_prove_batch_seeded(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                       const uint8_t* commitments, const uint8_t* x, const uint8_t* sblind, const uint8_t* digits,
+                                       const uint8_t* m, const uint8_t seed[32], uint64_t stream_base, uint8_t* proofs, int32_t* status) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return recip_prove_impl(c, label, label_len, nullptr, n, dim_nd, dim_np, commitments, x, sblind, digits, m, nullptr, proofs, status, false,
+                            seed, stream_base);
+}
+int bppp_circuit_prove_batch_seeded(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                    const uint8_t* v_commitments, const uint8_t* v, const uint8_t* s_v, const uint8_t* w_l, const uint8_t* w_r,
+                                    const uint8_t* w_o, const uint8_t seed[32], uint64_t stream_base, uint8_t* proofs, int32_t* status) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return circuit_prove_impl(c, q, label, label_len, nullptr, n, v_commitments, v, s_v, w_l, w_r, w_o, nullptr, proofs, status, false,
+                              seed, stream_base);
+}
 
 }  // extern "C"

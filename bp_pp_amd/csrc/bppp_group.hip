@@ -520,4 +520,24 @@ int bppp_u64_prove_batch_sharded_device(bppp_group* grp, const uint8_t* label, s
     return run_call(call);
 }
 
+// ---- the seeded prover, sharded: rank r draws with stream_base + lo_r (its shard's first proof), so every proof's draws -- and so its
+//      bytes -- are those of one single-context bppp_u64_prove_batch_seeded call over the whole batch
+int bppp_u64_prove_batch_seeded_sharded(bppp_group* grp, const uint8_t* label, size_t label_len, size_t n, const uint64_t* x,
+                                        const uint8_t* s, const uint8_t seed[32], uint64_t stream_base, uint8_t* proofs,
+                                        uint8_t* commitments, int32_t* status) {
+    if (!grp || !label_ok(label, label_len) || !x || !s || !proofs || !commitments || !u64_shape(grp) || !draw_args_ok(seed, stream_base, n, 52))
+        return BPPP_ERR_INVALID_ARG;
+    if (n == 0) return BPPP_OK;
+    const int G = (int)grp->devices.size();
+    ShardedCall call;
+    call.grp = grp; call.n = n; call.exchange = false;
+    call.arrays = {host_in(x, 8), host_in(s, 32), host_out(proofs, BPPP_U64_PROOF_BYTES), host_out(commitments, 64), host_out(status, 4)};
+    call.enqueue = [=](int r, bppp_ctx* c, size_t m, void* const* p, void*) {
+        size_t lo, hi;
+        bppp_shard_range(n, r, G, &lo, &hi);
+        return prove_seeded_device_impl(c, label, label_len, m, p[0], p[1], seed, stream_base + lo, p[2], p[3], p[4]);
+    };
+    return run_call(call);
+}
+
 }  // extern "C"

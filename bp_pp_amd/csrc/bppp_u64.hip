@@ -889,4 +889,77 @@ int bppp_u64_prove_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_le
     return rc;
 }
 
+// ---- seeded provers (include/bppp.h: "Seeded provers"): the prover's random scalars drawn on the device from a ChaCha20 seed
+//      (draw_core.h), so that they never pass through host memory or over the bus
+int bppp_draw_scalars(const uint8_t* seed, uint64_t stream_base, size_t n, size_t k, uint8_t* out) {
+    if (!out || !draw_args_ok(seed, stream_base, n, k)) return BPPP_ERR_INVALID_ARG;
+    u32 key[8];
+    chacha_key(key, seed);
+    for (size_t i = 0; i < n; i++)
+        for (size_t j = 0; j < k; j++) {
+            u32 w[8];
+            draw_scalar_words(w, key, stream_base + i, j);
+            std::memcpy(out + (i * k + j) * 32, w, 32);
+        }
+    return BPPP_OK;
+}
+int bppp_draw_scalars_device(bppp_ctx* c, const uint8_t* seed, uint64_t stream_base, size_t n, size_t k, void* d_out) {
+    CtxLock lock_(c);
+    if (!c || !d_out || ((uintptr_t)d_out & 15) || !draw_args_ok(seed, stream_base, n, k)) return BPPP_ERR_INVALID_ARG;
+    if (n == 0 || k == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return draw_enqueue(c->stream, seed, stream_base, n, k, (uint8_t*)d_out);
+}
+int prove_seeded_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_x, const void* d_s,
+                             const uint8_t* seed, uint64_t stream_base, void* d_proofs, void* d_commitments, void* d_status) {
+    if (!c || !label_ok(label, label_len) || !d_x || !d_s || !d_proofs || !d_commitments || !draw_args_ok(seed, stream_base, n, 52))
+        return BPPP_ERR_INVALID_ARG;
+    if (c->ng != 16 || c->nh != 32) return BPPP_ERR_INVALID_ARG;
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = n * 52 * 32;
+    int rc = ensure_buffer(c, c->d_draw, c->draw_bytes, bytes);
+    if (rc != BPPP_OK) return rc;
+    DrawWipe wipe = {c->d_draw, bytes, c->stream};
+    rc = draw_enqueue(c->stream, seed, stream_base, n, 52, c->d_draw);
+    if (rc != BPPP_OK) return rc;
+    rc = prove_device_impl(c, label, label_len, n, d_x, d_s, c->d_draw, d_proofs, d_commitments, d_status, nullptr);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(wipe.now());      // behind the prover's last kernel: its helper stream has joined c->stream by then
+    return BPPP_OK;
+}
+int bppp_u64_prove_batch_seeded_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_x, const void* d_s,
+                                       const uint8_t seed[32], uint64_t stream_base, void* d_proofs, void* d_commitments, void* d_status) {
+    CtxLock lock_(c);
+    return prove_seeded_device_impl(c, label, label_len, n, d_x, d_s, seed, stream_base, d_proofs, d_commitments, d_status);
+}
+int bppp_u64_prove_batch_seeded(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint64_t* x, const uint8_t* s,
+                                const uint8_t seed[32], uint64_t stream_base, uint8_t* proofs, uint8_t* commitments, int32_t* status) {
+    CtxLock lock_(c);
+    if (!c || !label_ok(label, label_len) || !x || !s || !proofs || !commitments || !draw_args_ok(seed, stream_base, n, 52))
+        return BPPP_ERR_INVALID_ARG;
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // only x and s go up
+    const size_t o_x = 0, o_s = o_x + n * 8, o_p = o_s + n * 32, o_c = o_p + n * (size_t)BPPP_U64_PROOF_BYTES, o_st = o_c + n * 64,
+                 total = o_st + n * sizeof(int32_t);
+    int rc = ensure_io(c, total);
+    if (rc != BPPP_OK) return rc;
+    uint8_t* d = c->d_io;
+    hipError_t e = hipMemcpyAsync(d + o_x, x, n * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_s, s, n * 32, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        rc = prove_seeded_device_impl(c, label, label_len, n, d + o_x, d + o_s, seed, stream_base, d + o_p, d + o_c, d + o_st);
+        if (rc == BPPP_OK) {
+            e = hipMemcpyAsync(proofs, d + o_p, n * (size_t)BPPP_U64_PROOF_BYTES, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(commitments, d + o_c, n * 64, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && status) e = hipMemcpyAsync(status, d + o_st, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        }
+    }
+    if (e != hipSuccess || rc != BPPP_OK) quiesce(c);
+    if (e != hipSuccess) { g_last_error = std::string("prove_batch_seeded: ") + hipGetErrorString(e); return BPPP_ERR_HIP; }
+    return rc;
+}
+
 }  // extern "C"

@@ -138,6 +138,9 @@ struct bppp_ctx {
     // prover's compressed output
     uint8_t* d_wire = nullptr;
     size_t wire_bytes = 0;
+    // the seeded u64 prover's draws (n x 52 x 32, include/bppp.h: "Seeded provers"), zero between calls
+    uint8_t* d_draw = nullptr;
+    size_t draw_bytes = 0;
     int* d_flags = nullptr;
     int n_simds = 1024;            // CUs x 4 (device property), decides between the small-batch and the 2-waves/SIMD lane kernels
     bool borrows_tables = false;   // d_gens / d_table belong to another context (bppp_ctx_create_shared)
@@ -203,6 +206,38 @@ static inline int ensure_buffer(bppp_ctx* c, uint8_t*& d, size_t& have, size_t b
 // stream before it returns, so one buffer serves them all -- no allocator round trip and no implicit device sync per call)
 static inline int ensure_io(bppp_ctx* c, size_t bytes) { return ensure_buffer(c, c->d_io, c->io_bytes, bytes); }
 static inline int ensure_blob(bppp_ctx* c, size_t bytes) { return ensure_buffer(c, c->d_blob, c->blob_bytes, bytes); }
+
+// ---- the seeded provers' draws (draw_core.h, k_draw.hip)
+// a NULL seed, a stream range stream_base .. stream_base + n - 1 that overflows u64, or an output size that overflows size_t
+static inline bool draw_args_ok(const uint8_t* seed, uint64_t stream_base, size_t n, size_t k) {
+    if (!seed) return false;
+    if (n && stream_base > UINT64_MAX - (uint64_t)(n - 1)) return false;
+    return !(k && n > SIZE_MAX / 32 / k);
+}
+// k_draw_scalars over n x k draws into d_out (16-byte aligned), queued on s
+static inline int draw_enqueue(hipStream_t s, const uint8_t* seed, uint64_t stream_base, size_t n, size_t k, uint8_t* d_out) {
+    if (n == 0 || k == 0) return BPPP_OK;
+    const u64 total = (u64)n * k, blocks = (total + 255) / 256;
+    if (blocks > 0xFFFFFFFFu) return BPPP_ERR_INVALID_ARG;
+    DrawKey key;
+    chacha_key(key.w, seed);
+    k_draw_scalars<<<(unsigned)blocks, 256, 0, s>>>(key, stream_base, (u64)k, total, d_out);
+    HIP_TRY(hipGetLastError());
+    return BPPP_OK;
+}
+// draws in a context buffer do not outlive the call: cleared on the call's stream behind the last kernel that reads them (now(), on
+// the success path, so that an error is reported), or on whatever other way the call leaves
+struct DrawWipe {
+    uint8_t* d;
+    size_t bytes;
+    hipStream_t s;
+    hipError_t now() {
+        const hipError_t e = d ? hipMemsetAsync(d, 0, bytes, s) : hipSuccess;
+        d = nullptr;
+        return e;
+    }
+    ~DrawWipe() { if (d) (void)hipMemsetAsync(d, 0, bytes, s); }
+};
 
 // after a failed call: nothing of it may still be running when the entry point returns (the staging is reused by the next call, and
 // copies from / to the caller's memory may be queued) -- what the implicit synchronisation of a per-call hipFree used to provide
@@ -500,6 +535,10 @@ int verify_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
 // bppp_u64.hip: the u64 prover over device buffers, asynchronous on c->stream (the caller holds the context's lock)
 int prove_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_x, const void* d_s, const void* d_rnd,
                       void* d_proofs, void* d_commitments, void* d_status, const VerifyTranscripts* tx);
+// bppp_u64.hip: the same with the 52 draws per proof made on the device from (seed, stream_base) into c->d_draw, which is cleared
+// behind the prover's last kernel
+int prove_seeded_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_x, const void* d_s,
+                             const uint8_t* seed, uint64_t stream_base, void* d_proofs, void* d_commitments, void* d_status);
 // bppp_generic.hip: the reciprocal verifier over device buffers (exact, or RLC when rlc_seed is given); d_reject_count (device
 // int32, optional) receives the number of rejected instances
 int recip_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,

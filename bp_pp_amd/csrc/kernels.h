@@ -13,6 +13,7 @@
 #include "wnla_rlc_core.h"
 #include "wnla_prove_core.h"
 #include "wire_core.h"
+#include "draw_core.h"
 
 #define BPPP_BLOCK 64
 // One-lane-per-proof kernels of the u64 verifier: minimum waves per SIMD the register allocator must leave room for
@@ -138,6 +139,8 @@ __global__ __launch_bounds__(256) void k_sec1_compress(uint8_t* commitments33, u
 // the generic proofs' wire form (k_wire.hip): expand / compress over a layout descriptor
 __global__ __launch_bounds__(256) void k_wire_expand(bppp::WireMap m);
 __global__ __launch_bounds__(256) void k_wire_compress(bppp::WireMap m);
+// the seeded provers' draws (k_draw.hip): n x k scalars in the `rnd` layout, one lane per draw
+__global__ __launch_bounds__(256) void k_draw_scalars(bppp::DrawKey key, bppp::u64 stream_base, bppp::u64 k, bppp::u64 total, uint8_t* out);
 // the u64 prover's stages that touch the transcript run once per distinct sponge position in the wavefront (for_each_position_group
 // above; one trip unless the caller passed per-proof pre-loaded transcripts of different lengths) -- shared by k_prove.hip and k_prove_w2.hip
 #if defined(__HIPCC__)

@@ -17,3 +17,4 @@
 #include "../k_generic.hip"
 #include "../k_gprove.hip"
 #include "../k_wire.hip"
+#include "../k_draw.hip"

@@ -195,6 +195,21 @@ class U64RangeProofGroup(_Group):
                                                                        status.ctypes.data))
         return proofs, commitments, status
 
+    def prove_batch_seeded(self, x, s, seed: bytes, stream_base: int, label: bytes):
+        """prove_batch with the draws made on each device from ChaCha20 (seed, stream_base + i) (include/bppp.h: "Seeded provers"):
+        rank r starts at its shard's first index, so the result is byte-identical to U64RangeProofProtocol.prove_batch_seeded."""
+        import numpy as np
+        from .range_proof import _seed_args
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)
+        n = x.shape[0]
+        s = np.ascontiguousarray(s, dtype=np.uint8).reshape(n, 32)
+        seed, stream_base = _seed_args(seed, stream_base, n)
+        proofs, commitments, status = np.zeros((n, 928), np.uint8), np.zeros((n, 64), np.uint8), np.zeros(n, np.int32)
+        self._capi.check(self._capi.lib().bppp_u64_prove_batch_seeded_sharded(self._grp, label, len(label), n, x.ctypes.data, s.ctypes.data,
+                                                                              seed, stream_base, proofs.ctypes.data,
+                                                                              commitments.ctypes.data, status.ctypes.data))
+        return proofs, commitments, status
+
     def prove_batch_device(self, label: bytes, n: int, d_x, d_s, d_rnd, d_proofs, d_commitments, d_status=None) -> None:
         """Per-device lists of raw device addresses of each rank's shard; blocks until every device is done."""
         mk = self._ptrs

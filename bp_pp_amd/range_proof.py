@@ -27,6 +27,30 @@ def _as_u8(a, shape) -> np.ndarray:
     return arr.reshape(shape)
 
 
+def _seed_args(seed, stream_base: int, n: int) -> Tuple[bytes, int]:
+    """(seed, stream_base) of the seeded provers checked as include/bppp.h states them: 32 seed bytes, and the streams
+    stream_base .. stream_base + n - 1 inside u64."""
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("seed must be exactly 32 bytes")
+    stream_base = int(stream_base)
+    if stream_base < 0 or stream_base + max(int(n), 1) - 1 >= 1 << 64:
+        raise ValueError("stream_base .. stream_base + n - 1 must lie in [0, 2^64)")
+    return seed, stream_base
+
+
+def draw_scalars(seed: bytes, stream_base: int, n: int, k: int) -> np.ndarray:
+    """The seeded provers' draws on the host (bppp_draw_scalars): instance i's k scalars from ChaCha20 stream stream_base + i,
+    block j -> draw j, mod n.  Returns uint8 [n, k, 32], the layout of the provers' `rnd`."""
+    n, k = int(n), int(k)
+    if n < 0 or k < 0:
+        raise ValueError("n and k must be non-negative")
+    seed, stream_base = _seed_args(seed, stream_base, n)
+    out = np.zeros((n, k, 32), dtype=np.uint8)
+    _capi.check(_capi.lib().bppp_draw_scalars(seed, stream_base, n, k, out.ctypes.data))
+    return out
+
+
 def derive_generators(seed: bytes, n: int = 49, first_index: int = 0) -> bytes:
     """n x 64 bytes of nothing-up-my-sleeve generators (include/bppp.h: bppp_derive_generators; host code, no GPU needed):
     g, g_vec[16], h_vec[32] for the u64 protocol when n = 49."""
@@ -311,6 +335,34 @@ class U64RangeProofProtocol:
                            d_status: int = 0) -> None:
         _capi.check(_capi.lib().bppp_u64_prove_batch_device(self._ctx, label, len(label), n, d_x, d_s, d_rnd, d_proofs,
                                                             d_commitments, d_status or None))
+
+    # ---- seeded provers (include/bppp.h: "Seeded provers"): (seed, stream_base) in place of rnd, the draws made on the device
+    def prove_batch_seeded(self, x: np.ndarray, s, seed: bytes, stream_base: int, label: bytes):
+        """prove_batch with proof i's 52 draws taken from ChaCha20 stream stream_base + i of `seed` (draw_scalars); only x and s
+        are uploaded.  Never reuse a (seed, stream) pair for another witness.  Returns (proofs[n,928], commitments[n,64], status[n])."""
+        x = np.ascontiguousarray(x, dtype=np.uint64)
+        n = x.shape[0]
+        s = _as_u8(s, (n, 32))
+        seed, stream_base = _seed_args(seed, stream_base, n)
+        proofs = np.zeros((n, U64_PROOF_BYTES), dtype=np.uint8)
+        com = np.zeros((n, 64), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        _capi.check(_capi.lib().bppp_u64_prove_batch_seeded(self._ctx, label, len(label), n, x.ctypes.data, s.ctypes.data, seed,
+                                                            stream_base, proofs.ctypes.data, com.ctypes.data, status.ctypes.data))
+        return proofs, com, status
+
+    def prove_batch_seeded_device(self, label: bytes, n: int, d_x: int, d_s: int, seed: bytes, stream_base: int, d_proofs: int,
+                                  d_commitments: int, d_status: int = 0) -> None:
+        """prove_batch_device with the draws made on the device (asynchronous on the context's stream)."""
+        seed, stream_base = _seed_args(seed, stream_base, n)
+        _capi.check(_capi.lib().bppp_u64_prove_batch_seeded_device(self._ctx, label, len(label), n, d_x, d_s, seed, stream_base, d_proofs,
+                                                                   d_commitments, d_status or None))
+
+    def draw_scalars_device(self, seed: bytes, stream_base: int, n: int, k: int, d_out: int) -> None:
+        """draw_scalars into device memory d_out (n x k x 32 bytes, 16-byte aligned), asynchronous on the context's stream: the
+        d_rnd of any *_device prover."""
+        seed, stream_base = _seed_args(seed, stream_base, n)
+        _capi.check(_capi.lib().bppp_draw_scalars_device(self._ctx, seed, stream_base, int(n), int(k), d_out))
 
     # ---- plumbing
     def set_stream(self, hip_stream: Optional[int]) -> None:

@@ -246,6 +246,25 @@ class ReciprocalRangeProofProtocol:
                                                             m.ctypes.data, rnd.ctypes.data, proofs.ctypes.data, st.ctypes.data))
         return proofs, st, (rounds.value, nl.value, nn.value)
 
+    def prove_batch_seeded(self, label: bytes, commitments, x, s, digits, m, seed: bytes, stream_base: int):
+        """prove_batch with instance i's 20 + 2 dim_nd draws taken from ChaCha20 stream stream_base + i of `seed` on the device
+        (include/bppp.h: "Seeded provers") -> (proofs, status, (rounds, nl, nn))."""
+        import ctypes as C
+        from .range_proof import _seed_args
+        commitments = _u8(commitments, (-1, 64))
+        B = commitments.shape[0]
+        x, s = _u8(x, (B, 32)), _u8(s, (B, 32))
+        digits, m = _u8(digits, (B, self.dim_nd, 32)), _u8(m, (B, self.dim_np, 32))
+        seed, stream_base = _seed_args(seed, stream_base, B)
+        rounds, nl, nn = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _capi.lib().bppp_wnla_proof_shape(self._w.nh, self._w.ng, C.byref(rounds), C.byref(nl), C.byref(nn))
+        proofs = np.zeros((B, 64 * (5 + 2 * rounds.value) + 32 * (nl.value + nn.value)), np.uint8)
+        st = np.zeros(B, np.int32)
+        _capi.check(_capi.lib().bppp_reciprocal_prove_batch_seeded(self._w._ctx, label, len(label), B, self.dim_nd, self.dim_np,
+                                                                   commitments.ctypes.data, x.ctypes.data, s.ctypes.data, digits.ctypes.data,
+                                                                   m.ctypes.data, seed, stream_base, proofs.ctypes.data, st.ctypes.data))
+        return proofs, st, (rounds.value, nl.value, nn.value)
+
     def commit_value_batch(self, x, s):
         """reciprocal.rs:88-90 for a batch: x [B, 32], s [B, 32] (big-endian scalars) -> (points, status)."""
         x, s = _u8(x, (-1, 32)), _u8(s, (-1, 32))
@@ -448,6 +467,26 @@ class ArithmeticCircuit:
         _capi.check(_capi.lib().bppp_circuit_prove_batch(self._w._ctx, self._circuit, label, len(label), B, v_commitments.ctypes.data,
                                                          v.ctypes.data, s_v.ctypes.data, w_l.ctypes.data, w_r.ctypes.data, w_o.ctypes.data,
                                                          rnd.ctypes.data, proofs.ctypes.data, st.ctypes.data))
+        return proofs, st, (rounds.value, nl.value, nn.value)
+
+    def prove_batch_seeded(self, label: bytes, v_commitments, v, s_v, w_l, w_r, w_o, seed: bytes, stream_base: int):
+        """prove_batch with instance i's 18 + dim_nv + dim_nm draws taken from ChaCha20 stream stream_base + i of `seed` on the
+        device (include/bppp.h: "Seeded provers") -> (proofs, status, (rounds, nl, nn))."""
+        import ctypes as C
+        from .range_proof import _seed_args
+        v_commitments = _u8(v_commitments, (-1, self.k, 64))
+        B = v_commitments.shape[0]
+        v, s_v = _u8(v, (B, self.k, self.dim_nv, 32)), _u8(s_v, (B, self.k, 32))
+        w_l, w_r = _u8(w_l, (B, self.dim_nm, 32)), _u8(w_r, (B, self.dim_nm, 32))
+        w_o = _u8(w_o, (B, self.dim_no, 32))
+        seed, stream_base = _seed_args(seed, stream_base, B)
+        rounds, nl, nn = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _capi.lib().bppp_wnla_proof_shape(self._w.nh, self._w.ng, C.byref(rounds), C.byref(nl), C.byref(nn))
+        proofs = np.zeros((B, 64 * (4 + 2 * rounds.value) + 32 * (nl.value + nn.value)), np.uint8)
+        st = np.zeros(B, np.int32)
+        _capi.check(_capi.lib().bppp_circuit_prove_batch_seeded(self._w._ctx, self._circuit, label, len(label), B, v_commitments.ctypes.data,
+                                                                v.ctypes.data, s_v.ctypes.data, w_l.ctypes.data, w_r.ctypes.data,
+                                                                w_o.ctypes.data, seed, stream_base, proofs.ctypes.data, st.ctypes.data))
         return proofs, st, (rounds.value, nl.value, nn.value)
 
     def commit_batch(self, v, s):

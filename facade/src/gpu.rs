@@ -196,6 +196,27 @@ impl U64RangeProofProtocolGpu {
         Ok((proofs.chunks(928).map(|b| get_u64_proof(b).expect("library emitted an invalid proof")).collect(),
             coms.chunks(64).map(|b| get_point(b).expect("library emitted a point off the curve")).collect()))
     }
+
+    /// n x `prove(x, s, &mut Transcript::new(label), rng)` with the 52 draws per proof made ON THE DEVICE
+    /// (bppp_u64_prove_batch_seeded): proof i draws from ChaCha20 stream `stream_base + i` of `seed`, block j -> draw j, so it equals
+    /// `let mut r = ChaCha20Rng::from_seed(seed); r.set_stream(stream_base + i as u64);` followed by `prove(.., &mut r)` -- the
+    /// design contract of include/bppp.h, not yet pinned against rand_chacha.  The secrets never pass through host memory; only x and
+    /// s are uploaded.  Never reuse a (seed, stream) pair for a different witness: that reveals the witness.
+    pub fn prove_batch_seeded(&self, xs: &[u64], ss: &[Scalar], label: &'static [u8], seed: [u8; 32], stream_base: u64) -> Result<(Vec<Proof>, Vec<ProjectivePoint>), GpuError> {
+        assert_eq!(xs.len(), ss.len());
+        let n = xs.len();
+        let mut sb = Vec::with_capacity(n * 32);
+        ss.iter().for_each(|s| put_scalar(&mut sb, s));
+        let (mut proofs, mut coms, mut st) = (vec![0u8; 928 * n], vec![0u8; 64 * n], vec![0i32; n]);
+        check(unsafe {
+            bppp_u64_prove_batch_seeded(self.ctx, label.as_ptr(), label.len(), n, xs.as_ptr(), sb.as_ptr(), seed.as_ptr(), stream_base, proofs.as_mut_ptr(), coms.as_mut_ptr(), st.as_mut_ptr())
+        })?;
+        if let Some(i) = st.iter().position(|s| *s != 0) {
+            return Err(GpuError::ReferenceWouldPanic { index: i });
+        }
+        Ok((proofs.chunks(928).map(|b| get_u64_proof(b).expect("library emitted an invalid proof")).collect(),
+            coms.chunks(64).map(|b| get_point(b).expect("library emitted a point off the curve")).collect()))
+    }
 }
 
 impl Drop for U64RangeProofProtocolGpu {

@@ -635,6 +635,54 @@ BPPP_API int bppp_reciprocal_verify_batch_rlc_device(bppp_ctx* ctx, const uint8_
                                                      size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
                                                      size_t nn, void* d_accept, void* d_status, const uint8_t seed[32]);
 
+/* ---- Seeded provers: the prover's random scalars drawn on the device from a ChaCha20 seed ----
+ * The `rnd` forms above take the prover's random scalars from the caller (52 per u64 proof, 20 + 2 dim_nd per reciprocal instance,
+ * 18 + dim_nv + dim_nm per circuit instance: the Scalar::generate_biased(rng) draws of reciprocal.rs:121, circuit.rs:264-298 and
+ * :371-372, in that order).  The seeded forms take a 32-byte seed and a 64-bit stream base instead and make the draws themselves:
+ * instance i of a call (0-based, in batch order) uses ChaCha20 stream stream_base + i, and its draws j = 0 .. k-1 are
+ *     block  = the ChaCha20 block function, 20 rounds (RFC 8439 2.1-2.3), state words 0-3 the constants, 4-11 the key = seed
+ *              (little-endian words), 12-13 the 64-bit block counter j (low, high), 14-15 the 64-bit stream stream_base + i (low, high)
+ *     draw_j = the block's 64 output bytes read as a big-endian integer, mod n  (k256 Scalar::generate_biased)
+ * laid out exactly as `rnd` (n x k x 32 big-endian bytes).  For counters below 2^32 a block equals OpenSSL's "chacha20" keystream with
+ * the 16-byte IV le32(j) || 00000000 || le64(stream).
+ * Design contract, NOT verified against rand_chacha here (no Rust toolchain): this is what `let mut r = ChaCha20Rng::from_seed(seed);
+ * r.set_stream(stream_base + i);` followed by k calls of `Scalar::generate_biased(&mut r)` gives -- every 64-byte request takes exactly
+ * one block, so draw j is block j -- and then a seeded proof is byte-identical to the crate's CPU proof for the same seed and stream.
+ * BPPP_ERR_INVALID_ARG for a NULL seed or output, or when stream_base + n - 1 overflows u64.
+ * WARNING: reusing a (seed, stream) pair for two different witnesses reveals the witness, exactly as nonce reuse does.  Give every
+ * proof its own stream (or every call its own seed).  The same inputs with the same (seed, stream) give the same proof.
+ * The seed travels as a kernel argument; the draws live in a context buffer (or the call's staging) that is cleared with
+ * hipMemsetAsync behind the prover's last kernel, so they do not outlive the call in device memory. */
+/* The draws themselves, on the host (no GPU): out = n x k x 32 bytes. */
+BPPP_API int bppp_draw_scalars(const uint8_t seed[32], uint64_t stream_base, size_t n, size_t k, uint8_t* out /* n x k x 32 */);
+/* ... on the device, asynchronous on the context's stream: d_out (16-byte aligned) can feed the d_rnd of any *_device prover
+ * (bppp_u64_prove_batch_device, ..._transcript_device, ..._sec1_device, ..._sharded_device). */
+BPPP_API int bppp_draw_scalars_device(bppp_ctx* ctx, const uint8_t seed[32], uint64_t stream_base, size_t n, size_t k,
+                                      void* d_out /* n x k x 32 */);
+/* bppp_u64_prove_batch[_device] with k = 52 draws per proof made on the device into a context-owned buffer; the host form uploads
+ * only x and s. */
+BPPP_API int bppp_u64_prove_batch_seeded(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, const uint64_t* x,
+                                         const uint8_t* s /* n x 32 */, const uint8_t seed[32], uint64_t stream_base,
+                                         uint8_t* proofs /* n x 928 */, uint8_t* commitments /* n x 64 */, int32_t* status /* n or NULL */);
+BPPP_API int bppp_u64_prove_batch_seeded_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, const void* d_x,
+                                                const void* d_s, const uint8_t seed[32], uint64_t stream_base, void* d_proofs,
+                                                void* d_commitments, void* d_status);
+/* bppp_u64_prove_batch_sharded with the draws made on each device: rank r draws with stream_base + lo_r (bppp_shard_range), so
+ * the bytes equal those of one single-context call. */
+BPPP_API int bppp_u64_prove_batch_seeded_sharded(bppp_group* grp, const uint8_t* label, size_t label_len, size_t n, const uint64_t* x,
+                                                 const uint8_t* s /* n x 32 */, const uint8_t seed[32], uint64_t stream_base,
+                                                 uint8_t* proofs /* n x 928 */, uint8_t* commitments /* n x 64 */,
+                                                 int32_t* status /* n or NULL */);
+/* bppp_reciprocal_prove_batch / bppp_circuit_prove_batch with k = 20 + 2 dim_nd / 18 + dim_nv + dim_nm draws per instance. */
+BPPP_API int bppp_reciprocal_prove_batch_seeded(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
+                                                size_t dim_np, const uint8_t* commitments, const uint8_t* x, const uint8_t* s,
+                                                const uint8_t* digits, const uint8_t* m, const uint8_t seed[32], uint64_t stream_base,
+                                                uint8_t* proofs, int32_t* status /* n or NULL */);
+BPPP_API int bppp_circuit_prove_batch_seeded(bppp_ctx* ctx, const bppp_circuit* circuit, const uint8_t* label, size_t label_len, size_t n,
+                                             const uint8_t* v_commitments, const uint8_t* v, const uint8_t* s_v, const uint8_t* w_l,
+                                             const uint8_t* w_r, const uint8_t* w_o, const uint8_t seed[32], uint64_t stream_base,
+                                             uint8_t* proofs, int32_t* status /* n or NULL */);
+
 /* Profiling aid for bench.py: when enabled, every kernel launch of the verify pipeline is bracketed by HIP events on
  * the context's stream; bppp_ctx_get_timings returns accumulated milliseconds and launch counts per kernel since the
  * last reset.  names[i] points to a static string. */
