@@ -1,0 +1,93 @@
+"""Builds the TEST-ONLY primitive libraries of tests/test_prims.py from one dispatcher (prims_core.h):
+
+  libbppp_prims_gcc.so    g++ host build (prims_host.cpp): the code path of the tests/emul emulation
+  libbppp_prims_clang.so  ROCm's clang++ host build (prims_host.cpp): field.h's __builtin_addc / __builtin_subc carry chains
+  libbppp_prims_hip.so    hipcc gfx950 build (prims_device.hip) with the product's BASE_FLAGS: the code the GPU runs
+
+A library is rebuilt when it is missing or older than any bp_pp_amd/csrc/*.h or tests/prims/* source."""
+import ctypes as C
+import glob
+import os
+import shutil
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+BACKENDS = ("gcc", "clang", "gfx950")
+SO = {
+    "gcc": os.path.join(HERE, "libbppp_prims_gcc.so"),
+    "clang": os.path.join(HERE, "libbppp_prims_clang.so"),
+    "gfx950": os.path.join(HERE, "libbppp_prims_hip.so"),
+}
+HOST_FLAGS = ["-O2", "-shared", "-fPIC", "-std=c++17"]
+
+
+def _hipcc():
+    return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+def clangxx():
+    """ROCm's LLVM clang++, found next to hipcc; None if it is not there."""
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(_hipcc())))
+    for cand in (os.path.join(rocm, "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++"):
+        if os.path.exists(cand):
+            return cand
+    return None
+
+
+def _stale(so):
+    deps = glob.glob(os.path.join(ROOT, "bp_pp_amd", "csrc", "*.h")) + [
+        p for p in glob.glob(os.path.join(HERE, "*")) if os.path.isfile(p) and not p.endswith(".so") and "__pycache__" not in p]
+    return not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps)
+
+
+def unavailable(backend):
+    """Why `backend` cannot be built here, or None."""
+    if backend == "clang" and clangxx() is None:
+        return "ROCm's clang++ (llvm/bin/clang++ beside hipcc) is not installed"
+    if backend == "gfx950" and not os.path.exists(_hipcc()):
+        return "hipcc is not installed"
+    return None
+
+
+def build(backend, force=False):
+    so = SO[backend]
+    if not force and not _stale(so):
+        return so
+    why = unavailable(backend)
+    if why:
+        raise RuntimeError(why)
+    if backend == "gfx950":
+        from bp_pp_amd._build import BASE_FLAGS
+        cmd = [_hipcc(), *BASE_FLAGS, "-shared", "-Wl,-rpath,/opt/rocm/lib", "-o", so + ".tmp", os.path.join(HERE, "prims_device.hip")]
+    else:
+        cxx = "g++" if backend == "gcc" else clangxx()
+        cmd = [cxx, *HOST_FLAGS, "-o", so + ".tmp", os.path.join(HERE, "prims_host.cpp")]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"building {os.path.basename(so)} failed:\n{r.stderr[-6000:]}")
+    os.replace(so + ".tmp", so)
+    return so
+
+
+def build_all():
+    """What __graft_entry__.build() calls: every backend that can be built here (the gfx950 one cross-compiles without a GPU)."""
+    return [build(b) for b in BACKENDS if unavailable(b) is None]
+
+
+def load(backend):
+    L = C.CDLL(build(backend))
+    vp, sz = C.c_void_p, C.c_size_t
+    L.prims_record_words.argtypes = [C.c_int]
+    L.prims_record_words.restype = C.c_int
+    run = L.prims_run_device if backend == "gfx950" else L.prims_run_host
+    run.argtypes = [vp, vp, sz, vp, sz]
+    run.restype = C.c_int
+    L.run = run
+    if backend != "gfx950":
+        L.prims_is_clang.restype = C.c_int
+    return L
