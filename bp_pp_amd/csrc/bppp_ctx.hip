@@ -435,7 +435,7 @@ int bppp_ctx_set_option(bppp_ctx* c, const char* name, long value) {
     return BPPP_ERR_INVALID_ARG;
 }
 // read back a tunable, or one of the read-only facts "fb_window_bits" (the window width in use -- the library's choice when the
-// context was created with 0), "device", "n_generators", "last_verify_plan", "last_prove_plan"
+// context was created with 0), "device", "n_generators", "n_simds", "last_verify_plan", "last_prove_plan", "last_generic_form"
 long bppp_ctx_get_option(bppp_ctx* c, const char* name) {
     CtxLock lock_(c);
     if (!c || !name) return BPPP_ERR_INVALID_ARG;
@@ -476,6 +476,9 @@ long bppp_ctx_get_option(bppp_ctx* c, const char* name) {
     // the kernels the last u64 verify / prove call on this context ran (plan_core.h; text form: bppp_plan_describe)
     if (std::strcmp(name, "last_verify_plan") == 0) return (long)c->last_verify_plan;
     if (std::strcmp(name, "last_prove_plan") == 0) return (long)c->last_prove_plan;
+    // the SIMDs the launch choices go by, and the choices the last generic verify call (WNLA, reciprocal, circuit) made (bppp_generic.hip)
+    if (std::strcmp(name, "n_simds") == 0) return (long)c->n_simds;
+    if (std::strcmp(name, "last_generic_form") == 0) return (long)c->last_generic_form;
     return BPPP_ERR_INVALID_ARG;
 }
 long bppp_u64_plan(int prove, size_t n, int n_simds, int flags) {

@@ -114,13 +114,22 @@ static int wnla_final_scalars_group_lg(const bppp_ctx* c, unsigned rounds, unsig
     while (lg < 3 && ((size_t)blocks << (lg + 1)) <= 4 * (size_t)c->n_simds) lg++;
     return wnla_final_scalars_lg((int)rounds, lg);
 }
-static void launch_wnla_final_scalars(const bppp_ctx* c, const WnlaWs& w, unsigned rounds, size_t n, unsigned blocks, hipStream_t s, unsigned call_blocks = 0) {
-    const int lg = wnla_final_scalars_group_lg(c, rounds, call_blocks ? call_blocks : blocks);
+// (lg: wnla_final_scalars_group_lg by the wavefronts of the whole call -- the caller has recorded it in the call's form)
+static void launch_wnla_final_scalars(const WnlaWs& w, int lg, unsigned blocks, hipStream_t s) {
     if (lg > 0) {
         k_wnla_final_scalars_grp<<<blocks << lg, BPPP_BLOCK, 0, s>>>(w, lg);
         k_wnla_final_scalars_join<<<blocks, BPPP_BLOCK, 0, s>>>(w, lg);
     } else k_wnla_final_scalars<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-    (void)n;
+}
+// "last_generic_form" of bppp_ctx_get_option (include/bppp.h has the bit layout): the launch choices of a generic verify call, each as
+// the value the launch below it is given -- written by the three verify bodies just before their first launch, read by the tests that
+// run every threshold of the predicates above at +- 1 (tests/test_gpu_generic_boundaries.py)
+enum { GENERIC_FORM_WNLA = 1, GENERIC_FORM_RECIPROCAL = 2, GENERIC_FORM_CIRCUIT = 3 };
+enum { GENERIC_FB_LANES8 = 0, GENERIC_FB_WAVEFRONT = 1, GENERIC_FB_ONE_LANE = 2 };
+static uint32_t generic_form_code(int protocol, int tab_parts, int round_group, int final_lg, int fb_form, int p1_group = 0, bool beside = false,
+                                  int parts = 1, bool per_point = false) {
+    return (uint32_t)protocol | (uint32_t)tab_parts << 2 | (uint32_t)round_group << 5 | (uint32_t)final_lg << 10 | (uint32_t)fb_form << 12 |
+           (uint32_t)p1_group << 14 | (uint32_t)(beside ? 1 : 0) << 18 | (uint32_t)parts << 19 | (uint32_t)(per_point ? 1 : 0) << 22;
 }
 // the wire form of the generic proofs (the *_sec1 entry points at the end of this file): conversion launches over a WireMap (wire_core.h)
 static int wire_launch(WireMap m, bool expand, hipStream_t s) {
@@ -227,6 +236,9 @@ static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label
     } else {
         rc = wnla_fast_setup(c, w, n, rounds, 0, nullptr, (size_t)wnla_table_parts(c, n, rounds));
         if (rc != BPPP_OK) return rc;
+        const int grp = wnla_round_group(c, w, blocks), final_lg = wnla_final_scalars_group_lg(c, (unsigned)rounds, blocks);
+        const bool fb_wide = generic_fb_wide(c, n);
+        c->last_generic_form = generic_form_code(GENERIC_FORM_WNLA, w.tab_parts, grp, final_lg, fb_wide ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8);
 #define WLAUNCH(id, ...)                                       \
     do {                                                       \
         rc = timed(c, id, s, [&]() { __VA_ARGS__; });          \
@@ -234,15 +246,12 @@ static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label
     } while (0)
         WLAUNCH(K_WNLA_BEGIN, k_wnla_begin<<<blocks, BPPP_BLOCK, 0, s>>>(w));
         if (w.atab) WLAUNCH(K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, s));
-        {
-            const int grp = wnla_round_group(c, w, blocks);
-            for (int k = 1; k <= (int)rounds; k++) {
-                if (grp > 1) WLAUNCH(K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, k, grp));
-                else WLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, k));
-            }
+        for (int k = 1; k <= (int)rounds; k++) {
+            if (grp > 1) WLAUNCH(K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, k, grp));
+            else WLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, k));
         }
-        WLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(c, w, (unsigned)rounds, n, blocks, s));
-        if (generic_fb_wide(c, n)) WLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
+        WLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, final_lg, blocks, s));
+        if (fb_wide) WLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
         else WLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
         WLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
 #undef WLAUNCH
@@ -310,7 +319,7 @@ int bppp_wnla_verify_batch_transcript(bppp_ctx* c, size_t n, const uint8_t* stat
 // one part of a multi-part call (recip_verify_device_entry): its stream and its shares of the context's buffers
 // (started / stage: an event recorded behind the part's stage-th milestone -- 1 phase 1, 2 the C0 stage, 3 the rounds -- that the NEXT
 // part's chain waits for, so that the chains run out of step: one part's fixed-base sums under another's one-lane kernels)
-struct GenericPart { hipStream_t s; uint8_t* gtab; pt_slot* straus; unsigned call_blocks; hipEvent_t started; int stage; };
+struct GenericPart { hipStream_t s; uint8_t* gtab; pt_slot* straus; unsigned call_blocks; hipEvent_t started; int stage; int n_parts; };
 // workspace bytes (beyond the caller's commitments / proofs / accept / status) of one reciprocal verify call
 static size_t recip_verify_ws_bytes(const bppp_ctx* c, size_t n, size_t dim_nd, size_t dim_np, size_t rounds, bool rlc = false) {
     const size_t NB = (size_t)c->nbases, T = (size_t)1 << rounds, NH = (size_t)c->nh;
@@ -392,6 +401,22 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
     // one, 2^17 154.2 / 153.0, 2^18 314.3 / 301.4: profiles/r06/r06_b1_recip_beside_sizes.txt)
     const bool beside = w.atab && !c->timing && !part && (c->recip_beside >= 0 ? c->recip_beside == 1 : 2 * (size_t)call_blocks <= (size_t)c->n_simds);
     hipStream_t a = beside ? c->aux_stream : s;
+    // lanes per instance for phase 1's two loops over the digits: as many (up to 8) as keep the launch within ONE wavefront per SIMD --
+    // the kernel is an uncapped build (one wavefront per SIMD fits), and a group's lanes each repeat the head (transcript, inversions:
+    // a seventh of the one-lane kernel).  Round 6, configs[4]'s shape, the kernel alone: 2^15 instances 3.48 -> 2.10 ms on 2 lanes
+    // (2.65 on 4, 3.8 on 8: two and four generations of wavefronts); the call 45.71 -> 45.30 ms, because the round-point tables
+    // that ran beside the half-empty one-lane kernel now share its SIMDs (profiles/r06/r06_p2_recip_phase1_groups.txt)
+    int G = 1;
+    if (c->recip_p1_group) G = c->recip_p1_group;
+    else if (!c->no_lane_groups) {
+        if (c->generic_lane_group) G = c->generic_lane_group == 2 ? 2 : 8;      // (tests: the smallest and the largest split at any size)
+        else while (G < 8 && 2 * (size_t)G * call_blocks <= (size_t)c->n_simds) G *= 2;
+    }
+    const bool fb_wide = !fb_one_lane && !part && generic_fb_wide(c, n);
+    const int grp_w = wnla_round_group(c, w, call_blocks), final_lg = wnla_final_scalars_group_lg(c, (unsigned)rounds, call_blocks);
+    c->last_generic_form = generic_form_code(GENERIC_FORM_RECIPROCAL, w.tab_parts, grp_w, final_lg,
+                                             fb_one_lane ? GENERIC_FB_ONE_LANE : fb_wide ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8, G, beside,
+                                             part ? part->n_parts : 1);
 #define GLAUNCH_ON(st, id, ...)                                 \
     do {                                                        \
         rc = timed(c, id, st, [&]() { __VA_ARGS__; });          \
@@ -402,33 +427,19 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
         HIP_TRY(hipStreamWaitEvent(a, c->ev_tab, 0));
         GLAUNCH_ON(a, K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, a));
     }
-    {
-        // lanes per instance for phase 1's two loops over the digits: as many (up to 8) as keep the launch within ONE wavefront per SIMD --
-        // the kernel is an uncapped build (one wavefront per SIMD fits), and a group's lanes each repeat the head (transcript, inversions:
-        // a seventh of the one-lane kernel).  Round 6, configs[4]'s shape, the kernel alone: 2^15 instances 3.48 -> 2.10 ms on 2 lanes
-        // (2.65 on 4, 3.8 on 8: two and four generations of wavefronts); the call 45.71 -> 45.30 ms, because the round-point tables
-        // that ran beside the half-empty one-lane kernel now share its SIMDs (profiles/r06/r06_p2_recip_phase1_groups.txt)
-        int G = 1;
-        if (c->recip_p1_group) G = c->recip_p1_group;
-        else if (!c->no_lane_groups) {
-            if (c->generic_lane_group) G = c->generic_lane_group == 2 ? 2 : 8;      // (tests: the smallest and the largest split at any size)
-            else while (G < 8 && 2 * (size_t)G * call_blocks <= (size_t)c->n_simds) G *= 2;
-        }
-        if (G > 1) GLAUNCH(K_RECIP_PHASE1, k_recip_phase1_grp<<<(unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, G));
-        else GLAUNCH(K_RECIP_PHASE1, k_recip_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    }
+    if (G > 1) GLAUNCH(K_RECIP_PHASE1, k_recip_phase1_grp<<<(unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, G));
+    else GLAUNCH(K_RECIP_PHASE1, k_recip_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
     if (part && part->started && part->stage == 1) HIP_TRY(hipEventRecord(part->started, s));
     if (beside) {
         HIP_TRY(hipEventRecord(c->ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(a, c->ev_fork, 0));
     }
     const unsigned fb1_blocks = (unsigned)((n + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
-    const bool fb_wide = !fb_one_lane && !part && generic_fb_wide(c, n);
     if (fb_one_lane) GLAUNCH(K_RECIP_C0_FIXED, k_recip_c0_fixed_l1<<<fb1_blocks, BPPP_FB_BLOCK, 0, s>>>(r));
     else if (fb_wide) GLAUNCH(K_RECIP_C0_FIXED, k_recip_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
     else GLAUNCH(K_RECIP_C0_FIXED, k_recip_c0_fixed<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(r));
     if (r.atab) {
-        const int grp_r = wnla_round_group(c, w, call_blocks), grp = grp_r > 4 ? 4 : grp_r;      // (C0's sum: lane groups of 2 or 4)
+        const int grp = grp_w > 4 ? 4 : grp_w;      // (C0's sum: lane groups of 2 or 4)
         GLAUNCH_ON(a, K_RECIP_C0_VAR, {
             k_recip_c0_tables<<<blocks, BPPP_BLOCK, 0, a>>>(r);
             if (grp > 1) k_recip_c0_var_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, a>>>(r, grp);
@@ -444,15 +455,12 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
     if (part && part->started && part->stage == 2) HIP_TRY(hipEventRecord(part->started, s));
     GLAUNCH(K_WNLA_BEGIN, k_wnla_begin<<<blocks, BPPP_BLOCK, 0, s>>>(w));
     if (w.atab && !beside) GLAUNCH(K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, s));
-    {
-        const int grp = wnla_round_group(c, w, call_blocks);
-        for (int k = 1; k <= (int)rounds; k++) {
-            if (grp > 1) GLAUNCH(K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, k, grp));
-            else GLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, k));
-        }
+    for (int k = 1; k <= (int)rounds; k++) {
+        if (grp_w > 1) GLAUNCH(K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp_w * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, k, grp_w));
+        else GLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, k));
     }
     if (part && part->started && part->stage == 3) HIP_TRY(hipEventRecord(part->started, s));
-    GLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(c, w, (unsigned)rounds, n, blocks, s, call_blocks));
+    GLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, final_lg, blocks, s));
     if (!rlc_seed) {
         if (fb_one_lane) GLAUNCH(K_WNLA_MSM, k_wnla_msm_l1<<<fb1_blocks, BPPP_FB_BLOCK, 0, s>>>(w));
         else if (fb_wide) GLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
@@ -563,7 +571,7 @@ int recip_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_le
         int rc_parts = BPPP_OK;
         for (int i = 0; i < parts && rc_parts == BPPP_OK; i++) {
             const GenericPart gp = {streams[i], fast ? c->d_gtab + gt_off[i] : nullptr, c->d_straus + lo[i] * 5 * BPPP_STRAUS_ENTRIES, call_blocks,
-                                    stage && i + 1 < parts ? started[i] : nullptr, stage};
+                                    stage && i + 1 < parts ? started[i] : nullptr, stage, parts};
             if (stage && i > 0) HIP_TRY(hipStreamWaitEvent(streams[i], started[i - 1], 0));
             rc_parts = recip_verify_device_impl(c, label, label_len, m[i], dim_nd, dim_np, (const uint8_t*)d_commitments + 64 * lo[i],
                                                 (const uint8_t*)d_proofs + proof_bytes * lo[i], rounds, nl, nn, (uint8_t*)d_accept + lo[i],
@@ -827,36 +835,35 @@ static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const ui
         if (rcf != BPPP_OK) return rcf;
         r.atab = w.atab; r.tscr = w.tscr; r.atab_first = (int)(2 * rounds * 16 * (size_t)w.tab_parts);
     }
+    // C0's variable-base sum: a lane per point (L lanes per instance, tables and sum in one launch) while that stays within two
+    // wavefronts per SIMD, else the one-lane kernels (five points per shared-doubling pass).  Round 6, `mixed_k2` (6 points): one
+    // verify 4.74 -> 2.76 ms (this stage 3.0 -> 0.98), 8,192 instances 1.37 ms where 16,384 on the one-lane kernels take 2.64
+    int L = 8;
+    while (L < 4 + (int)k) L *= 2;
+    const bool per_point = r.atab && !c->no_lane_groups && !c->no_split && L <= 64 && (size_t)L * blocks <= 2 * (size_t)c->n_simds;
+    const bool fb_wide = generic_fb_wide(c, n);
+    const int grp = wnla_round_group(c, w, blocks), final_lg = wnla_final_scalars_group_lg(c, (unsigned)rounds, blocks);
+    c->last_generic_form = generic_form_code(GENERIC_FORM_CIRCUIT, w.tab_parts, grp, final_lg, fb_wide ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8,
+                                             0, false, 1, per_point);
     CLAUNCH(K_CIRCUIT_PHASE1, k_circuit_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    if (generic_fb_wide(c, n)) CLAUNCH(K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    if (fb_wide) CLAUNCH(K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
     else CLAUNCH(K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(r));
-    {
-        // C0's variable-base sum: a lane per point (L lanes per instance, tables and sum in one launch) while that stays within two
-        // wavefronts per SIMD, else the one-lane kernels (five points per shared-doubling pass).  Round 6, `mixed_k2` (6 points): one
-        // verify 4.74 -> 2.76 ms (this stage 3.0 -> 0.98), 8,192 instances 1.37 ms where 16,384 on the one-lane kernels take 2.64
-        int L = 8;
-        while (L < 4 + (int)k) L *= 2;
-        const bool per_point = r.atab && !c->no_lane_groups && !c->no_split && L <= 64 && (size_t)L * blocks <= 2 * (size_t)c->n_simds;
-        CLAUNCH(K_CIRCUIT_C0_VAR, {
-            if (per_point) k_circuit_c0_var_pts<<<(unsigned)(((size_t)L * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, L);
-            else {
-                if (r.atab) k_circuit_c0_tables<<<blocks, BPPP_BLOCK, 0, s>>>(r);
-                k_circuit_c0_var<<<blocks, BPPP_BLOCK, 0, s>>>(r);
-            }
-        });
-    }
+    CLAUNCH(K_CIRCUIT_C0_VAR, {
+        if (per_point) k_circuit_c0_var_pts<<<(unsigned)(((size_t)L * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, L);
+        else {
+            if (r.atab) k_circuit_c0_tables<<<blocks, BPPP_BLOCK, 0, s>>>(r);
+            k_circuit_c0_var<<<blocks, BPPP_BLOCK, 0, s>>>(r);
+        }
+    });
     CLAUNCH(K_CIRCUIT_C0_FINISH, k_circuit_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
     CLAUNCH(K_WNLA_BEGIN, k_wnla_begin<<<blocks, BPPP_BLOCK, 0, s>>>(w));
     if (w.atab) CLAUNCH(K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, s));
-    {
-        const int grp = wnla_round_group(c, w, blocks);
-        for (int kk = 1; kk <= (int)rounds; kk++) {
-            if (grp > 1) CLAUNCH(K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, kk, grp));
-            else CLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, kk));
-        }
+    for (int kk = 1; kk <= (int)rounds; kk++) {
+        if (grp > 1) CLAUNCH(K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, kk, grp));
+        else CLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, kk));
     }
-    CLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(c, w, (unsigned)rounds, n, blocks, s));
-    if (generic_fb_wide(c, n)) CLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
+    CLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, final_lg, blocks, s));
+    if (fb_wide) CLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
     else CLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
     CLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
 #undef CLAUNCH

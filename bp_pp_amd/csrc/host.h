@@ -167,6 +167,7 @@ struct bppp_ctx {
     int fb_one_lane_mode = -1;   // diagnostic BPPP_FB_ONE_LANE: 1 = one lane per proof in the u64 verifier's fixed-base kernels at every size, 0 = never, unset = by size   // diagnostics, read from the environment once at context creation
     // single-proof front end (bppp_coalesce.hip): created at the first *_one call; options "coalesce_max" / "coalesce_us" / "coalesce_lanes"
     uint32_t last_verify_plan = 0, last_prove_plan = 0;      // plan_core.h: the kernels the context's last u64 verify / prove call (or part) ran
+    uint32_t last_generic_form = 0;                          // bppp_generic.hip: generic_form_code of the context's last generic verify call (or part); include/bppp.h has the bits
     struct bppp_fronts* fronts = nullptr;      // lives until the context itself is deleted (closure is sticky: never re-created once closed)
     std::atomic<bool> fronts_closed{false};    // set by bppp_ctx_destroy before it drains: *_one callers return BPPP_ERR_CLOSED instead of retrying
     std::atomic<int> one_callers{0};           // threads inside a *_one entry point (counted before they touch anything else of the context);

@@ -117,6 +117,16 @@ class WeightNormLinearArgument:
     def get_option(self, name: str) -> int:
         return int(_capi.check(_capi.lib().bppp_ctx_get_option(self._ctx, name.encode())))
 
+    def generic_form(self) -> dict:
+        """The launch choices of the context's last generic verify call -- WNLA, reciprocal or circuit: the wrappers of the latter two
+        reach this through their `_w` -- decoded from "last_generic_form" (include/bppp.h has the bits); {} before the first."""
+        v = self.get_option("last_generic_form")
+        if v == 0:
+            return {}
+        return {"protocol": (None, "wnla", "reciprocal", "circuit")[v & 3], "tab_parts": v >> 2 & 7, "round_group": v >> 5 & 31,
+                "final_scalars_lg": v >> 10 & 3, "fixed_base": ("lanes8", "wavefront", "one_lane", None)[v >> 12 & 3],
+                "phase1_group": v >> 14 & 15, "beside": v >> 18 & 1, "parts": v >> 19 & 7, "per_point": v >> 22 & 1}
+
     def enable_timing(self, on: bool = True) -> None:
         _capi.check(_capi.lib().bppp_ctx_enable_timing(self._ctx, 1 if on else 0))
 

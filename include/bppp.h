@@ -137,8 +137,26 @@ BPPP_API int bppp_ctx_set_stream(bppp_ctx* ctx, void* hip_stream);
 BPPP_API int bppp_ctx_set_option(bppp_ctx* ctx, const char* name, long value);
 /* Reads a tunable back, or one of the read-only facts "fb_window_bits" (the width in use: the library's choice when the context was
  * created with 0), "device", "n_generators", "last_verify_plan" / "last_prove_plan" (the plan code -- see bppp_u64_plan -- of the
- * context's last u64 verify / prove call, or of the last part of a call that ran in parts; 0 before the first).  Negative =
- * BPPP_ERR_INVALID_ARG (unknown name). */
+ * context's last u64 verify / prove call, or of the last part of a call that ran in parts; 0 before the first), "n_simds" (CUs x 4 of
+ * the context's device: the number every size threshold of the launch choices is a multiple of), "last_generic_form" (below).  Negative =
+ * BPPP_ERR_INVALID_ARG (unknown name).
+ * "last_generic_form": the launch choices of the context's last GENERIC verify call -- bppp_wnla_verify_batch*, bppp_circuit_verify_batch*,
+ * bppp_reciprocal_verify_batch* (a reciprocal call of the u64 shape runs the u64 kernels, leaves this alone and sets "last_verify_plan")
+ * -- written before the call's first launch, each field the value the launch was given; of a call that ran in parts, the last part's
+ * form.  0 before the first such call.  Bits, from the low end:
+ *    0 ..  1   protocol: 1 = WNLA, 2 = reciprocal, 3 = circuit
+ *    2 ..  4   sets of round-point tables: 4 | 2 (calls of up to n_simds | 4 n_simds instances) | 1
+ *    5 ..  9   lanes per instance in the rounds: 16 | 8 (over 4 | 2 sets of tables) | 4 | 2 (up to 16 | 32 n_simds instances) | 1
+ *   10 .. 11   log2 of the lanes per instance of the final scalars: 3 | 2 | 1 (up to 32 | 64 | 128 n_simds instances) | 0, and at
+ *              most rounds - 1
+ *   12 .. 13   the fixed-base sums: 0 = 8 lanes per instance, 1 = a wavefront per instance (up to 8 n_simds instances), 2 = one lane
+ *              (reciprocal, from 128 n_simds instances)
+ *   14 .. 17   reciprocal: lanes per instance in phase 1: 8 | 4 | 2 (up to 8 | 16 | 32 n_simds instances) | 1; else 0
+ *   18         reciprocal: 1 = the round-point tables and C0's variable-base sum ran on the helper stream (up to 32 n_simds instances,
+ *              one part, kernel timing off)
+ *   19 .. 21   parts the call ran in ("generic_parts"; 1 unless reciprocal)
+ *   22         circuit: 1 = C0's variable-base sum on a lane per point (up to 16 n_simds instances for up to 8 points)
+ * The sizes are those of a default context: the diagnostic environment switches override them, and the field shows what was taken. */
 BPPP_API long bppp_ctx_get_option(bppp_ctx* ctx, const char* name);
 /* Which kernels a u64 verify (prove = 0) or prove (prove = 1) call of n proofs runs on a device of n_simds SIMDs (CUs x 4; MI355X: 1024):
  * the size decides among seven (six) launch sequences, from a wavefront per sum for a handful of proofs to one lane per proof from 2^17

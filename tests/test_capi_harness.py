@@ -62,6 +62,7 @@ def test_c_caller_gets_the_fixture_verdicts(harness, fixture_file, wbits):
     ones, alt = "1" * n, "".join("0" if i % 2 == 0 else "1" for i in range(n))
     assert [int(c["accept"]) for c in gold["cases"]] == [1] * n
     assert out["null_ctx_rc"] == "-2" and out["empty_rc"] == "0"
+    assert out["options"] == "1 0"                             # "n_simds" > 0, "last_generic_form" = 0: read from C
     assert out["verify"] == ones and out["status"].split() == ["0"] * n
     assert out["prove_same_proofs"] == "1" and out["prove_same_commitments"] == "1"
     assert out["sec1_same_x"] == "1" and out["verify_sec1"] == ones

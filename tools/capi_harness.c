@@ -96,6 +96,8 @@ int main(int argc, char** argv) {
 
     /* an empty batch is a no-op */
     printf("empty_rc %d\n", bppp_u64_verify_batch(ctx, label, label_len, 0, V, P, accept, status));
+    /* read-only facts: the SIMD count the launch choices go by, and no generic verify call has run on this context yet */
+    printf("options %d %ld\n", bppp_ctx_get_option(ctx, "n_simds") > 0, bppp_ctx_get_option(ctx, "last_generic_form"));
 
     /* U64RangeProofProtocol::prove + commit_value with the fixture's witnesses and randomness: the same bytes */
     CHECK(bppp_u64_prove_batch(ctx, label, label_len, n, x, s, rnd, P2, V2, status));
