@@ -169,18 +169,95 @@ struct WnlaBlob {
     ~WnlaBlob() { if (c) quiesce(c); }
 };
 
+// ---- the random-linear-combination mode of the final sum (wnla_rlc_core.h), shared by the three generic verifiers: every one of them
+//      ends in the WNLA stage, and this is that stage's last step.
+// Where the RLC buffers sit in a call's workspace: taken behind `off`, the running end of the caller's own layout, whichever it is
+struct WnlaRlcLayout { size_t lhs, sc, flag, list; };
+static WnlaRlcLayout wnla_rlc_take(size_t& off, size_t n, size_t NB) {
+    const size_t nchunks = (n + BPPP_RLC_CHUNK - 1) / BPPP_RLC_CHUNK;
+    auto take = [&](size_t bytes) { size_t o = off; off = align16(off + bytes); return o; };
+    WnlaRlcLayout o;
+    o.lhs = take(30 * n * 4); o.sc = take(NB * 8 * n * 4); o.flag = take(nchunks); o.list = take((nchunks + 4) * 4);
+    return o;
+}
+// RULE for the WNLA and circuit RLC entry points: a call with fewer than one complete chunk (n < 8) runs the exact final sum -- every
+// instance of it would be re-checked by the exact kernels anyway (wnla_rlc_chunk_serial: an incomplete chunk is not usable), so the
+// results are the same by construction and the chunk stage's six launches are saved; such a call reports "last_rlc_superchunk" =
+// "last_rlc_chunk" = 0.  Every other call runs the chunk stage, at any launch form (per-part tables, lane-group rounds and the wide
+// fixed-base sums of the stages before it are untouched; the flagged chunks' exact sums are a wavefront per instance themselves).
+static bool wnla_rlc_applies(size_t n) { return n >= BPPP_RLC_CHUNK; }
+// what such a call allocates besides its workspace, before its first launch: the bucket stage's buffers (launch_bucket_stage asks again)
+static int wnla_rlc_prepare(bppp_ctx* c, size_t n) {
+    return bucket_superchunk_for(c, n) ? ensure_bucket_capacity(c, n, (size_t)c->nbases) : BPPP_OK;
+}
+// The launches behind k_wnla_final_scalars in RLC mode: one MSM per chunk of 8 instances instead of one per instance; what does not
+// pass is re-checked exactly (wnla_rlc_core.h).  d + o.*: the RLC buffers of this call; w.accept is written for every instance.
+static int wnla_rlc_final_sum(bppp_ctx* c, const WnlaWs& w, const uint8_t* rlc_seed, uint8_t* d, const WnlaRlcLayout& o, hipStream_t s) {
+    const size_t n = w.N, nchunks = (n + BPPP_RLC_CHUNK - 1) / BPPP_RLC_CHUNK;
+    const int NB = c->nbases;
+    const unsigned blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
+    const unsigned fb_blocks = (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
+    int rc;
+#define RLAUNCH(id, ...)                                       \
+    do {                                                       \
+        rc = timed(c, id, s, [&]() { __VA_ARGS__; });          \
+        if (rc != BPPP_OK) return rc;                          \
+    } while (0)
+    RlcWs rl;
+    std::memset(&rl, 0, sizeof rl);
+    for (int i = 0; i < 4; i++) {
+        u64 v = 0;
+        for (int k = 0; k < 8; k++) v |= (u64)rlc_seed[8 * i + k] << (8 * k);
+        rl.seed[i] = v;
+    }
+    rl.lhs = (u32*)(d + o.lhs); rl.sc = (u32*)(d + o.sc); rl.flag = d + o.flag;
+    rl.list = (u32*)(d + o.list); rl.count = (int*)(rl.list + nchunks + 1);
+    const unsigned chunk_blocks = (unsigned)((nchunks * BPPP_RLC_CHUNK + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
+    const unsigned check_blocks = (unsigned)(nchunks < 16384 ? nchunks : 16384);
+    HIP_TRY(hipMemsetAsync(w.accept, 0, n, s));
+    HIP_TRY(hipMemsetAsync(rl.count, 0, sizeof(int), s));
+    const unsigned SM = bucket_superchunk_for(c, n);
+    c->last_rlc_super_m = SM; c->last_rlc_chunk = BPPP_RLC_CHUNK;
+    if (SM) {
+        // bucket (Pippenger) stage first, as in the u64 verifier: superchunks of SM instances, the weighted commitments summed by
+        // bucket accumulation and ONE 1 + ng + nh-base MSM per superchunk; the chunk-of-8 kernels only see what failed it
+        BucketWs bw;
+        rc = launch_bucket_stage(c, bw, n, SM, rl.seed, w.status, w.acc, w.msc, NB, w.accept, s,
+                                 [&](int id, auto&& f) { return timed(c, id, s, f); });
+        if (rc != BPPP_OK) return rc;
+        rl.sflag = bw.sflag;
+        rl.super_m = SM;
+    }
+    RLAUNCH(K_WNLA_RLC_LHS, k_wnla_rlc_lhs<<<blocks, BPPP_BLOCK, 0, s>>>(w, rl));
+    RLAUNCH(K_WNLA_RLC_CHUNK, k_wnla_rlc_chunk<<<chunk_blocks, BPPP_FB_BLOCK, 0, s>>>(w, rl));
+    RLAUNCH(K_WNLA_RLC_CHECK, k_wnla_rlc_check<<<check_blocks, 64, 0, s>>>(w, rl));
+    RLAUNCH(K_WNLA_MSM, k_wnla_msm_flagged<<<1024, 64, 0, s>>>(w, rl));
+    RLAUNCH(K_WNLA_MSM, k_wnla_msm_flagged_dense<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, rl));
+    RLAUNCH(K_WNLA_ACCEPT, k_wnla_accept_flagged<<<blocks, BPPP_BLOCK, 0, s>>>(w, rl));
+#undef RLAUNCH
+    return BPPP_OK;
+}
+
 static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments,
                     const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r,
                     const uint8_t* proof_x, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn, uint8_t* out_points,
-                    uint8_t* accept, int32_t* status, const HostTranscripts* tx = nullptr, bool device_io = false) {
+                    uint8_t* accept, int32_t* status, const HostTranscripts* tx = nullptr, bool device_io = false,
+                    const uint8_t* rlc_seed = nullptr) {
     // device_io (bppp_wnla_verify_batch_device): every pointer above is DEVICE memory, read and written in place; the call is asynchronous
     // on the context's stream and only the workspace comes out of the context's buffer
+    // rlc_seed (bppp_wnla_verify_batch_rlc[_device]): the final sum in RLC mode (wnla_rlc_final_sum, and the rule above it)
     HIP_TRY(hipSetDevice(c->device));
     if (rounds > 12 || nl > 4096 || nn > 4096) return BPPP_ERR_INVALID_ARG;
     int rc = check_host_transcripts(tx, n);
     if (rc != BPPP_OK) return rc;
+    const bool rlc = rlc_seed && wnla_rlc_applies(n);
+    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }      // (before the first allocation: a call that fails reports nothing stale)
     rc = ensure_straus_capacity(c, n);
     if (rc != BPPP_OK) return rc;
+    if (rlc) {
+        rc = wnla_rlc_prepare(c, n);
+        if (rc != BPPP_OK) return rc;
+    }
     const size_t NB = (size_t)c->nbases, T = (size_t)1 << rounds;
     // layout of the blob: inputs | outputs | workspace
     size_t off = 0;
@@ -190,6 +267,8 @@ static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label
                  o_out = take(n * 64), o_acc = take(n), o_st = take(n * 4), o_ts = take(52 * n * 4), o_a = take(30 * n * 4),
                  o_pf = take(30 * n * 4), o_ys = take((rounds ? rounds : 1) * 8 * n * 4), o_tab = take(2 * T * 8 * n * 4),
                  o_msc = take(NB * 8 * n * 4), o_ti = take(tx ? tx->n_states * 203 : 0), o_to = take(tx && tx->states_out ? n * 203 : 0);
+    WnlaRlcLayout o_rlc = {0, 0, 0, 0};
+    if (rlc) o_rlc = wnla_rlc_take(off, n, NB);
     WnlaBlob blob;
     if (device_io) { const int rc_b = ensure_blob(c, off + 16); if (rc_b != BPPP_OK) return rc_b; }       // (no sync when the call returns)
     else { const int rc_b = blob.take(c, off + 16); if (rc_b != BPPP_OK) return rc_b; }
@@ -251,9 +330,14 @@ static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label
             else WLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, k));
         }
         WLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, final_lg, blocks, s));
-        if (fb_wide) WLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
-        else WLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
-        WLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
+        if (rlc) {
+            rc = wnla_rlc_final_sum(c, w, rlc_seed, d, o_rlc, s);
+            if (rc != BPPP_OK) return rc;
+        } else {
+            if (fb_wide) WLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
+            else WLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
+            WLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
+        }
 #undef WLAUNCH
         if (w.tio.states_out) k_generic_export_states<<<blocks, BPPP_BLOCK, 0, s>>>(w);
         HIP_TRY(hipGetLastError());
@@ -300,6 +384,33 @@ int bppp_wnla_verify_batch_device(bppp_ctx* c, const uint8_t* label, size_t labe
                     (uint8_t*)d_accept, (int32_t*)d_status, nullptr, true);
 }
 
+// the same two in RLC mode: the exact twins' argument checks, and a seed
+int bppp_wnla_verify_batch_rlc(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments,
+                               const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r,
+                               const uint8_t* proof_x, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
+                               uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!c || !seed || !label_ok(label, label_len) || !commitments || !cvec || !rho || !mu || (rounds && (!proof_r || !proof_x)) ||
+        (!proof_l && nl) || (!proof_n && nn) || !accept)
+        return BPPP_ERR_INVALID_ARG;
+    if (n == 0) return BPPP_OK;
+    return wnla_run(c, false, label, label_len, n, commitments, cvec, rho, mu, rounds, proof_r, proof_x, proof_l, nl, proof_n, nn, nullptr,
+                    accept, status, nullptr, false, seed);
+}
+int bppp_wnla_verify_batch_rlc_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments, const void* d_c,
+                                      const void* d_rho, const void* d_mu, size_t rounds, const void* d_proof_r, const void* d_proof_x,
+                                      const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn, void* d_accept, void* d_status,
+                                      const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!c || !seed || !label_ok(label, label_len) || !d_commitments || !d_c || !d_rho || !d_mu || (rounds && (!d_proof_r || !d_proof_x)) ||
+        (!d_proof_l && nl) || (!d_proof_n && nn) || !d_accept)
+        return BPPP_ERR_INVALID_ARG;
+    if (n == 0) return BPPP_OK;
+    return wnla_run(c, false, label, label_len, n, (const uint8_t*)d_commitments, (const uint8_t*)d_c, (const uint8_t*)d_rho, (const uint8_t*)d_mu, rounds,
+                    (const uint8_t*)d_proof_r, (const uint8_t*)d_proof_x, (const uint8_t*)d_proof_l, nl, (const uint8_t*)d_proof_n, nn, nullptr,
+                    (uint8_t*)d_accept, (int32_t*)d_status, nullptr, true, seed);
+}
+
 int bppp_wnla_verify_batch_transcript(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, const uint8_t* commitments,
                                       const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r,
                                       const uint8_t* proof_x, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
@@ -328,7 +439,7 @@ static size_t recip_verify_ws_bytes(const bppp_ctx* c, size_t n, size_t dim_nd, 
     take(52 * n * 4); take((dim_nd + 6) * 8 * n * 4); take(5 * 16 * n * 4); take(30 * n * 4); take(30 * n * 4); take(dim_np * 8 * n * 4);
     take(n * 64); take(n * NH * 32); take(n * 32); take(n * 32); take((rounds ? rounds : 1) * 8 * n * 4); take(2 * T * 8 * n * 4);
     take(NB * 8 * n * 4);
-    if (rlc) { take(30 * n * 4); take(NB * 8 * n * 4); take((n + BPPP_RLC_CHUNK - 1) / BPPP_RLC_CHUNK); take(((n + BPPP_RLC_CHUNK - 1) / BPPP_RLC_CHUNK + 4) * 4); }
+    if (rlc) (void)wnla_rlc_take(off, n, NB);
     return off;
 }
 // the launch sequence, every buffer in device memory; d_ws holds recip_verify_ws_bytes()
@@ -343,9 +454,8 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
     const size_t o_ts = take(52 * n * 4), o_sc0 = take((dim_nd + 6) * 8 * n * 4), o_pts = take(5 * 16 * n * 4), o_a = take(30 * n * 4),
                  o_pf = take(30 * n * 4), o_inv = take(dim_np * 8 * n * 4), o_wc = take(n * 64), o_wcv = take(n * NH * 32), o_rho = take(n * 32),
                  o_mu = take(n * 32), o_ys = take((rounds ? rounds : 1) * 8 * n * 4), o_tab = take(2 * T * 8 * n * 4), o_msc = take(NB * 8 * n * 4);
-    const size_t nchunks = (n + BPPP_RLC_CHUNK - 1) / BPPP_RLC_CHUNK;
-    const size_t o_rl = rlc_seed ? take(30 * n * 4) : 0, o_rs = rlc_seed ? take(NB * 8 * n * 4) : 0, o_rf = rlc_seed ? take(nchunks) : 0,
-                 o_rli = rlc_seed ? take((nchunks + 4) * 4) : 0;
+    WnlaRlcLayout o_rlc = {0, 0, 0, 0};
+    if (rlc_seed) o_rlc = wnla_rlc_take(off, n, NB);
     uint8_t* d = d_ws;
     hipStream_t s = part ? part->s : c->stream;
     pt_slot* const straus = part ? part->straus : c->d_straus;
@@ -467,36 +577,8 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
         else GLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
         GLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
     } else {
-        // one MSM per chunk of 8 instances instead of one per instance; what does not pass is re-checked exactly (wnla_rlc_core.h)
-        RlcWs rl;
-        std::memset(&rl, 0, sizeof rl);
-        for (int i = 0; i < 4; i++) {
-            u64 v = 0;
-            for (int k = 0; k < 8; k++) v |= (u64)rlc_seed[8 * i + k] << (8 * k);
-            rl.seed[i] = v;
-        }
-        rl.lhs = (u32*)(d + o_rl); rl.sc = (u32*)(d + o_rs); rl.flag = d + o_rf;
-        rl.list = (u32*)(d + o_rli); rl.count = (int*)(rl.list + nchunks + 1);
-        const unsigned chunk_blocks = (unsigned)((nchunks * BPPP_RLC_CHUNK + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
-        const unsigned check_blocks = (unsigned)(nchunks < 16384 ? nchunks : 16384);
-        HIP_TRY(hipMemsetAsync(d_acc, 0, n, s));
-        HIP_TRY(hipMemsetAsync(rl.count, 0, sizeof(int), s));
-        if (const unsigned SM = bucket_superchunk_for(c, n)) {
-            // bucket (Pippenger) stage first, as in the u64 verifier: superchunks of SM instances, the weighted commitments summed by
-            // bucket accumulation and ONE 1 + ng + nh-base MSM per superchunk; the chunk-of-8 kernels only see what failed it
-            BucketWs bw;
-            rc = launch_bucket_stage(c, bw, n, SM, rl.seed, w.status, w.acc, w.msc, (int)NB, d_acc, s,
-                                     [&](int id, auto&& f) { return timed(c, id, s, f); });
-            if (rc != BPPP_OK) return rc;
-            rl.sflag = bw.sflag;
-            rl.super_m = SM;
-        }
-        GLAUNCH(K_WNLA_RLC_LHS, k_wnla_rlc_lhs<<<blocks, BPPP_BLOCK, 0, s>>>(w, rl));
-        GLAUNCH(K_WNLA_RLC_CHUNK, k_wnla_rlc_chunk<<<chunk_blocks, BPPP_FB_BLOCK, 0, s>>>(w, rl));
-        GLAUNCH(K_WNLA_RLC_CHECK, k_wnla_rlc_check<<<check_blocks, 64, 0, s>>>(w, rl));
-        GLAUNCH(K_WNLA_MSM, k_wnla_msm_flagged<<<1024, 64, 0, s>>>(w, rl));
-        GLAUNCH(K_WNLA_MSM, k_wnla_msm_flagged_dense<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, rl));
-        GLAUNCH(K_WNLA_ACCEPT, k_wnla_accept_flagged<<<blocks, BPPP_BLOCK, 0, s>>>(w, rl));
+        rc = wnla_rlc_final_sum(c, w, rlc_seed, d, o_rlc, s);
+        if (rc != BPPP_OK) return rc;
     }
     if (w.tio.states_out) k_generic_export_states<<<blocks, BPPP_BLOCK, 0, s>>>(w);
 #undef GLAUNCH
@@ -744,7 +826,7 @@ void bppp_circuit_destroy(bppp_circuit* q) {
 }
 static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
                                     const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
-                                    int32_t* status, const HostTranscripts* tx, bool device_io = false);
+                                    int32_t* status, const HostTranscripts* tx, bool device_io = false, const uint8_t* rlc_seed = nullptr);
 // ArithmeticCircuit::verify over DEVICE buffers (commitments n x k x 64, proofs, accept n, status n or null), asynchronous on the
 // context's stream: the resident form of bppp_circuit_verify_batch
 int bppp_circuit_verify_batch_device(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments,
@@ -758,6 +840,22 @@ int bppp_circuit_verify_batch(bppp_ctx* c, const bppp_circuit* q, const uint8_t*
     CtxLock lock_(c);
     return circuit_verify_host_impl(c, q, label, label_len, n, commitments, proofs, rounds, nl, nn, accept, status, nullptr);
 }
+// the same two in RLC mode (wnla_rlc_final_sum): the exact twins' argument checks, and a seed
+int bppp_circuit_verify_batch_rlc(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments,
+                                  const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept, int32_t* status,
+                                  const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return circuit_verify_host_impl(c, q, label, label_len, n, commitments, proofs, rounds, nl, nn, accept, status, nullptr, false, seed);
+}
+int bppp_circuit_verify_batch_rlc_device(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                         const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                         void* d_status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return circuit_verify_host_impl(c, q, label, label_len, n, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, rounds, nl, nn,
+                                    (uint8_t*)d_accept, (int32_t*)d_status, nullptr, true, seed);
+}
 int bppp_circuit_verify_batch_transcript(bppp_ctx* c, const bppp_circuit* q, size_t n, const uint8_t* states, size_t n_states,
                                          const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn,
                                          uint8_t* accept, int32_t* status, uint8_t* states_out) {
@@ -768,7 +866,8 @@ int bppp_circuit_verify_batch_transcript(bppp_ctx* c, const bppp_circuit* q, siz
 }
 static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
                                     const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
-                                    int32_t* status, const HostTranscripts* tx, bool device_io) {
+                                    int32_t* status, const HostTranscripts* tx, bool device_io, const uint8_t* rlc_seed) {
+    // rlc_seed (bppp_circuit_verify_batch_rlc[_device]): the final sum in RLC mode (wnla_rlc_final_sum, and the rule above it)
     if (!c || !q || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
     const CircuitDev& cd = q->cd;
     if (cd.nm > c->ng || cd.nv + 9 > c->nh || rounds > 12 || nl > 4096 || nn > 4096) return BPPP_ERR_INVALID_ARG;
@@ -776,8 +875,14 @@ static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const ui
     int rc = check_host_transcripts(tx, n);
     if (rc != BPPP_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
+    const bool rlc = rlc_seed && wnla_rlc_applies(n);
+    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }      // (before the first allocation: a call that fails reports nothing stale)
     rc = ensure_straus_capacity(c, n);
     if (rc != BPPP_OK) return rc;
+    if (rlc) {
+        rc = wnla_rlc_prepare(c, n);
+        if (rc != BPPP_OK) return rc;
+    }
     const size_t NB = (size_t)c->nbases, T = (size_t)1 << rounds, NH = (size_t)c->nh, k = (size_t)cd.k, nm = (size_t)cd.nm, nv = (size_t)cd.nv;
     const size_t proof_bytes = 64 * (4 + 2 * rounds) + 32 * (nl + nn);
     size_t off = 0;
@@ -788,6 +893,8 @@ static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const ui
                  o_wc = take(n * 64), o_wcv = take(n * NH * 32), o_rho = take(n * 32), o_mu = take(n * 32),
                  o_ys = take((rounds ? rounds : 1) * 8 * n * 4), o_tab = take(2 * T * 8 * n * 4), o_msc = take(NB * 8 * n * 4),
                  o_ti = take(tx ? tx->n_states * 203 : 0), o_to = take(tx && tx->states_out ? n * 203 : 0);
+    WnlaRlcLayout o_rlc = {0, 0, 0, 0};
+    if (rlc) o_rlc = wnla_rlc_take(off, n, NB);
     WnlaBlob blob;
     if (device_io) { const int rc_b = ensure_blob(c, off + 16); if (rc_b != BPPP_OK) return rc_b; }       // (no sync when the call returns)
     else { const int rc_b = blob.take(c, off + 16); if (rc_b != BPPP_OK) return rc_b; }
@@ -863,9 +970,14 @@ static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const ui
         else CLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, kk));
     }
     CLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, final_lg, blocks, s));
-    if (fb_wide) CLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
-    else CLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
-    CLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
+    if (rlc) {
+        rc = wnla_rlc_final_sum(c, w, rlc_seed, d, o_rlc, s);
+        if (rc != BPPP_OK) return rc;
+    } else {
+        if (fb_wide) CLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
+        else CLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
+        CLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
+    }
 #undef CLAUNCH
     if (w.tio.states_out) k_generic_export_states<<<blocks, BPPP_BLOCK, 0, s>>>(w);
     HIP_TRY(hipGetLastError());

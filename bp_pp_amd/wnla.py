@@ -26,6 +26,22 @@ def _states(transcripts) -> np.ndarray:
     return _u8(blob, (-1, 203))
 
 
+def _rlc_seed(seed) -> bytes:
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("seed must be 32 bytes")
+    return seed
+
+
+def _rlc_symbol(name: str):
+    """An RLC entry point of the WNLA / circuit verifiers; a library that lacks it (an A/B build of an earlier ABI loaded through
+    BPPP_LIB) is an error, never another path."""
+    fn = getattr(_capi.lib(), name, None)
+    if fn is None:
+        raise NotImplementedError(f"the loaded libbppp_hip.so does not export {name} (built before the generic RLC mode)")
+    return fn
+
+
 class WeightNormLinearArgument:
     def __init__(self, g: bytes, g_vec: Sequence[bytes], h_vec: Sequence[bytes], device: int = 0, fb_window_bits: int = 0,
                  fb_table_budget_bytes: int = 0):
@@ -111,8 +127,44 @@ class WeightNormLinearArgument:
         _capi.check(_capi.lib().bppp_wnla_verify_batch_device(self._ctx, label, len(label), n, d_commitments, d_c, d_rho, d_mu, rounds, d_proof_r,
                                                               d_proof_x, d_proof_l, nl, d_proof_n, nn, d_accept, d_status))
 
+    def verify_batch_rlc(self, label: bytes, commitments, c, rho, mu, proof_r, proof_x, proof_l, proof_n, seed: bytes):
+        """verify_batch in the optional random-linear-combination mode (include/bppp.h: bppp_wnla_verify_batch_rlc): one final MSM per
+        chunk of 8 instances, chunks that do not pass re-checked exactly; accept / status stay per instance.  seed: 32 unpredictable
+        bytes chosen after the proofs are fixed.  -> (accept, status)"""
+        seed = _rlc_seed(seed)
+        fn = _rlc_symbol("bppp_wnla_verify_batch_rlc")
+        commitments = _u8(commitments, (-1, 64))
+        B = commitments.shape[0]
+        c = _u8(c, (B, self.nh, 32))
+        rho, mu = _u8(rho, (B, 32)), _u8(mu, (B, 32))
+        proof_r, proof_x = _u8(proof_r, (B, -1, 64)), _u8(proof_x, (B, -1, 64))
+        if proof_r.shape[1] != proof_x.shape[1]:
+            return np.zeros(B, np.uint8), np.zeros(B, np.int32)          # wnla.rs:76-78
+        proof_l, proof_n = _u8(proof_l, (B, -1, 32)), _u8(proof_n, (B, -1, 32))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(fn(self._ctx, label, len(label), B, commitments.ctypes.data, c.ctypes.data, rho.ctypes.data, mu.ctypes.data,
+                       proof_r.shape[1], proof_r.ctypes.data, proof_x.ctypes.data, proof_l.ctypes.data, proof_l.shape[1],
+                       proof_n.ctypes.data, proof_n.shape[1], acc.ctypes.data, st.ctypes.data, seed))
+        return acc, st
+
+    def verify_batch_rlc_device(self, label: bytes, n: int, d_commitments: int, d_c: int, d_rho: int, d_mu: int, rounds: int, d_proof_r: int,
+                                d_proof_x: int, d_proof_l: int, nl: int, d_proof_n: int, nn: int, d_accept: int, d_status: int,
+                                seed: bytes) -> None:
+        """verify_batch_device in the random-linear-combination mode (raw device pointers; d_status 0 = none), asynchronous on the
+        context's stream."""
+        seed = _rlc_seed(seed)
+        _capi.check(_rlc_symbol("bppp_wnla_verify_batch_rlc_device")(self._ctx, label, len(label), n, d_commitments, d_c, d_rho, d_mu, rounds,
+                                                                     d_proof_r, d_proof_x, d_proof_l, nl, d_proof_n, nn, d_accept,
+                                                                     d_status or None, seed))
+
     def synchronize(self) -> None:
         _capi.check(_capi.lib().bppp_ctx_synchronize(self._ctx))
+
+    def set_option(self, name: str, value: int) -> None:
+        """bppp_ctx_set_option with any option name include/bppp.h lists (an unknown name or value is BPPP_ERR_INVALID_ARG), e.g.
+        "rlc_superchunk": 0 = no bucket stage in front of the RLC mode, else the superchunk size 64..8192; unset = chosen per call from
+        the batch size."""
+        _capi.check(_capi.lib().bppp_ctx_set_option(self._ctx, name.encode(), int(value)))
 
     def get_option(self, name: str) -> int:
         return int(_capi.check(_capi.lib().bppp_ctx_get_option(self._ctx, name.encode())))
@@ -512,8 +564,37 @@ class ArithmeticCircuit:
         _capi.check(_capi.lib().bppp_circuit_verify_batch_device(self._w._ctx, self._circuit, label, len(label), n, d_commitments, d_proofs, rounds,
                                                                  nl, nn, d_accept, d_status))
 
+    def verify_batch_rlc(self, label: bytes, commitments, proofs, rounds: int, nl: int, nn: int, seed: bytes):
+        """verify_batch in the optional random-linear-combination mode (include/bppp.h: bppp_circuit_verify_batch_rlc): one final MSM
+        per chunk of 8 instances, chunks that do not pass re-checked exactly; accept / status stay per instance.  -> (accept, status)"""
+        seed = _rlc_seed(seed)
+        fn = _rlc_symbol("bppp_circuit_verify_batch_rlc")
+        commitments = _u8(commitments, (-1, self.k, 64))
+        B = commitments.shape[0]
+        proofs = _u8(proofs, (B, 64 * (4 + 2 * rounds) + 32 * (nl + nn)))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(fn(self._w._ctx, self._circuit, label, len(label), B, commitments.ctypes.data, proofs.ctypes.data, rounds, nl, nn,
+                       acc.ctypes.data, st.ctypes.data, seed))
+        return acc, st
+
+    def verify_batch_rlc_device(self, label: bytes, n: int, d_commitments: int, d_proofs: int, rounds: int, nl: int, nn: int, d_accept: int,
+                                d_status: int, seed: bytes) -> None:
+        """verify_batch_device in the random-linear-combination mode (raw device pointers; d_status 0 = none), asynchronous on the
+        context's stream."""
+        seed = _rlc_seed(seed)
+        _capi.check(_rlc_symbol("bppp_circuit_verify_batch_rlc_device")(self._w._ctx, self._circuit, label, len(label), n, d_commitments,
+                                                                        d_proofs, rounds, nl, nn, d_accept, d_status or None, seed))
+
     def synchronize(self) -> None:
         self._w.synchronize()
+
+    def set_option(self, name: str, value: int) -> None:
+        """bppp_ctx_set_option on the circuit's context, any option name (WeightNormLinearArgument.set_option)."""
+        self._w.set_option(name, value)
+
+    def get_option(self, name: str) -> int:
+        """bppp_ctx_get_option on the circuit's context, any option name."""
+        return self._w.get_option(name)
 
     def enable_timing(self, on: bool = True) -> None:
         self._w.enable_timing(on)

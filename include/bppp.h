@@ -652,6 +652,32 @@ BPPP_API int bppp_reciprocal_verify_batch_rlc(bppp_ctx* ctx, const uint8_t* labe
 BPPP_API int bppp_reciprocal_verify_batch_rlc_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
                                                      size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
                                                      size_t nn, void* d_accept, void* d_status, const uint8_t seed[32]);
+/* The same mode for WeightNormLinearArgument::verify and ArithmeticCircuit::verify: the arguments, argument checks, layouts and
+ * (device forms) asynchrony of bppp_wnla_verify_batch[_device] / bppp_circuit_verify_batch[_device], and the seed (NULL:
+ * BPPP_ERR_INVALID_ARG).  Everything before the final sum -- phase 1, C0, the rounds, in whichever launch form the call's size gives
+ * ("last_generic_form") -- is the exact pipeline; the final sum over the 1 + |g_vec| + |h_vec| generators is done once per chunk of 8
+ * instances, behind the bucket stage over superchunks where "rlc_superchunk" (or the automatic choice) is not 0; a chunk that is
+ * incomplete, fails or holds a flagged instance (status != 0) is re-checked by the exact kernels, so accept / status equal the exact
+ * entry points' per instance except with probability <= 2^-128 per invalid chunk.
+ * RULE: a call with fewer than one complete chunk (n < 8) runs the exact final sum (every instance would be re-checked exactly anyway;
+ * identical results), and reports "last_rlc_superchunk" = "last_rlc_chunk" = 0; every other call runs the chunk stage and reports the
+ * superchunk it used (0 = no bucket stage) and 8. */
+BPPP_API int bppp_wnla_verify_batch_rlc(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                        const uint8_t* commitments /* n x 64 */, const uint8_t* c /* n x nh x 32 */,
+                                        const uint8_t* rho /* n x 32 */, const uint8_t* mu /* n x 32 */, size_t rounds,
+                                        const uint8_t* proof_r /* n x rounds x 64 */, const uint8_t* proof_x /* n x rounds x 64 */,
+                                        const uint8_t* proof_l /* n x nl x 32 */, size_t nl, const uint8_t* proof_n /* n x nn x 32 */,
+                                        size_t nn, uint8_t* accept /* n */, int32_t* status /* n or NULL */, const uint8_t seed[32]);
+BPPP_API int bppp_wnla_verify_batch_rlc_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments,
+                                               const void* d_c, const void* d_rho, const void* d_mu, size_t rounds, const void* d_proof_r,
+                                               const void* d_proof_x, const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn,
+                                               void* d_accept, void* d_status, const uint8_t seed[32]);
+BPPP_API int bppp_circuit_verify_batch_rlc(bppp_ctx* ctx, const bppp_circuit* circuit, const uint8_t* label, size_t label_len, size_t n,
+                                           const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn,
+                                           uint8_t* accept /* n */, int32_t* status /* n or NULL */, const uint8_t seed[32]);
+BPPP_API int bppp_circuit_verify_batch_rlc_device(bppp_ctx* ctx, const bppp_circuit* circuit, const uint8_t* label, size_t label_len,
+                                                  size_t n, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
+                                                  size_t nn, void* d_accept, void* d_status, const uint8_t seed[32]);
 
 /* ---- Seeded provers: the prover's random scalars drawn on the device from a ChaCha20 seed ----
  * The `rnd` forms above take the prover's random scalars from the caller (52 per u64 proof, 20 + 2 dim_nd per reciprocal instance,
