@@ -2,6 +2,41 @@
 // generic fixed-base linear combination (the crate's commit functions).
 #include "host.h"
 
+// one launch (or a short run of launches) on stream `st`, timed under KernelId `id` when kernel timing is on; a failure leaves the
+// calling function with its code (an `int rc` and the context `c` are in scope wherever this is used)
+#define GLAUNCH(st, id, ...)                                   \
+    do {                                                       \
+        rc = timed(c, id, st, [&]() { __VA_ARGS__; });         \
+        if (rc != BPPP_OK) return rc;                          \
+    } while (0)
+static unsigned blocks_of(size_t n) { return (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK); }
+static unsigned fb_blocks_of(size_t n) { return (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK); }
+static size_t take_bytes(size_t& off, size_t bytes) { const size_t o = off; off = align16(off + bytes); return o; }
+
+// The WnlaWs of a WNLA stage that CONTINUES an outer protocol (r: the reciprocal verifier's RecipWs, 5 points per proof, or the circuit
+// verifier's CircuitWs, 4): every instance's transcript goes on where the outer stage left it in r.tstate, the commitment and c, rho,
+// mu are what the outer stage wrote to r.wn_*, and the proof fields are read in place out of the outer proof blob --
+// 4 points | r | x | the points beyond 4 | l | n.  accept, ys, tab, msc: the stage's own buffers.
+template <typename OuterWs>
+static WnlaWs wnla_ws_continuing(const bppp_ctx* c, const OuterWs& r, size_t points, size_t nl, size_t nn, uint8_t* accept, u32* ys, u32* tab,
+                                 u32* msc) {
+    const size_t rounds = (size_t)r.rounds;
+    WnlaWs w;
+    std::memset(&w, 0, sizeof w);
+    w.N = r.N; w.ng = c->ng; w.nh = c->nh; w.rounds = r.rounds; w.nl = (int)nl; w.nn = (int)nn;
+    w.base = r.base; w.tio = r.tio; w.divergent_positions = r.tio.states && r.tio.n_states != 1;
+    w.commitments = r.wn_commit; w.c = r.wn_c; w.rho = r.wn_rho; w.mu = r.wn_mu;
+    w.proof_r = r.proofs + 256; w.proof_x = r.proofs + 256 + 64 * rounds; w.proof_l = r.proofs + 64 * points + 128 * rounds;
+    w.proof_n = w.proof_l + 32 * nl;
+    w.stride_r = w.stride_x = w.stride_l = w.stride_n = r.proof_bytes;
+    w.transcript_preloaded = 1;
+    w.accept = accept; w.status = r.status; w.tstate = r.tstate; w.acc = r.acc; w.pfix = r.pfix;
+    w.ys = ys; w.tab = tab; w.msc = msc;
+    w.straus = r.straus;
+    w.fb = r.fb;
+    return w;
+}
+
 extern "C" {
 
 // caller transcripts of the generic verifiers (host pointers): n_states x 203 in, n x 203 out (optional)
@@ -96,6 +131,7 @@ static bool generic_fb_wide(const bppp_ctx* c, size_t n) {
     return !c->no_lane_groups && !c->no_split && n <= 8 * (size_t)c->n_simds;
 }
 static unsigned fb64_blocks_of(size_t n) { return (unsigned)((n * 64 + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK); }
+static unsigned fb1_blocks_of(size_t n) { return (unsigned)((n + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK); }
 // the round points' window tables: a lane per instance, or a lane per (point, part) table in a call that leaves the chip empty
 static void launch_wnla_tables(const WnlaWs& w, size_t n, unsigned blocks, hipStream_t s) {
     if (w.tab_parts > 1) {
@@ -126,9 +162,33 @@ static void launch_wnla_final_scalars(const WnlaWs& w, int lg, unsigned blocks, 
 // run every threshold of the predicates above at +- 1 (tests/test_gpu_generic_boundaries.py)
 enum { GENERIC_FORM_WNLA = 1, GENERIC_FORM_RECIPROCAL = 2, GENERIC_FORM_CIRCUIT = 3 };
 enum { GENERIC_FB_LANES8 = 0, GENERIC_FB_WAVEFRONT = 1, GENERIC_FB_ONE_LANE = 2 };
-static uint32_t generic_form_code(int protocol, int tab_parts, int round_group, int final_lg, int fb_form, int p1_group = 0, bool beside = false,
-                                  int parts = 1, bool per_point = false) {
-    return (uint32_t)protocol | (uint32_t)tab_parts << 2 | (uint32_t)round_group << 5 | (uint32_t)final_lg << 10 | (uint32_t)fb_form << 12 |
+// one part of a multi-part call (recip_verify_device_entry): its stream and its shares of the context's buffers
+// (started / stage: an event recorded behind the part's stage-th milestone -- 1 phase 1, 2 the C0 stage, 3 the rounds -- that the NEXT
+// part's chain waits for, so that the chains run out of step: one part's fixed-base sums under another's one-lane kernels)
+struct GenericPart { hipStream_t s; uint8_t* gtab; pt_slot* straus; unsigned call_blocks; hipEvent_t started; int stage; int n_parts; };
+static int part_milestone(const GenericPart* part, int stage, hipStream_t s) {
+    if (part && part->started && part->stage == stage) HIP_TRY(hipEventRecord(part->started, s));
+    return BPPP_OK;
+}
+// The launch choices of a call's WNLA stage (the table parts are in WnlaWs::tab_parts): made once per call by wnla_form_setup, recorded
+// by generic_form_code, carried out by wnla_verify_stage
+struct WnlaForm { int round_group, final_lg, fb; };      // lanes per instance in the rounds | log2 of those in the final scalars | GENERIC_FB_*
+// The stage's table buffer (room for extra_points tables behind the round points': the outer protocol's C0 points) and its form, by the
+// predicates above over the instances of this call (or part) and the wavefronts of the WHOLE call -- the parts of a multi-part call
+// share the chip, and they take neither table parts nor the wavefront sums.  fb_one_lane: the reciprocal verifier's own choice.
+static int wnla_form_setup(bppp_ctx* c, WnlaWs& w, WnlaForm& f, size_t extra_points, const GenericPart* part = nullptr, bool fb_one_lane = false) {
+    const size_t n = w.N, rounds = (size_t)w.rounds;
+    const unsigned call_blocks = part ? part->call_blocks : blocks_of(n);
+    const int rc = wnla_fast_setup(c, w, n, rounds, extra_points, part ? part->gtab : nullptr, part ? 1 : (size_t)wnla_table_parts(c, n, rounds));
+    if (rc != BPPP_OK) return rc;
+    f.round_group = wnla_round_group(c, w, call_blocks);
+    f.final_lg = wnla_final_scalars_group_lg(c, (unsigned)rounds, call_blocks);
+    f.fb = fb_one_lane ? GENERIC_FB_ONE_LANE : (!part && generic_fb_wide(c, n)) ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8;
+    return BPPP_OK;
+}
+static uint32_t generic_form_code(int protocol, const WnlaWs& w, const WnlaForm& f, int p1_group = 0, bool beside = false, int parts = 1,
+                                  bool per_point = false) {
+    return (uint32_t)protocol | (uint32_t)w.tab_parts << 2 | (uint32_t)f.round_group << 5 | (uint32_t)f.final_lg << 10 | (uint32_t)f.fb << 12 |
            (uint32_t)p1_group << 14 | (uint32_t)(beside ? 1 : 0) << 18 | (uint32_t)parts << 19 | (uint32_t)(per_point ? 1 : 0) << 22;
 }
 // the wire form of the generic proofs (the *_sec1 entry points at the end of this file): conversion launches over a WireMap (wire_core.h)
@@ -148,6 +208,18 @@ static void wire_add_proof(WireMap& m, const uint8_t* src33, uint8_t* dst64, siz
     wire_map_add(m, true, src33 + 33 * P, b33, dst64 + 64 * P, b64, S);
 }
 static size_t wire_proof_bytes(size_t P, size_t S) { return 33 * P + 32 * S; }
+// a prover's input points (k per instance) from the caller's host memory to d_dst in the 64-byte form: copied as they are, or (sec1)
+// staged as 33 bytes at the head of the wire buffer, grown to wire_bytes for what the call will put behind them, and expanded on the device
+static int prover_points_in(bppp_ctx* c, bool sec1, const uint8_t* src, uint8_t* d_dst, size_t n, size_t k, size_t wire_bytes, hipStream_t s) {
+    if (!sec1) { HIP_TRY(hipMemcpyAsync(d_dst, src, n * k * 64, hipMemcpyHostToDevice, s)); return BPPP_OK; }
+    const int rc = ensure_buffer(c, c->d_wire, c->wire_bytes, wire_bytes);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_wire, src, n * k * 33, hipMemcpyHostToDevice, s));
+    WireMap wm;
+    wire_map_init(wm, n);
+    wire_map_add(wm, false, c->d_wire, 33 * k, d_dst, 64 * k, k);
+    return wire_launch(wm, true, s);
+}
 // a failed host-buffer call leaves nothing running behind it (the staging is reused by the next call); after the final sync it costs nothing
 struct WireQuiesce {
     bppp_ctx* c = nullptr;
@@ -195,14 +267,8 @@ static int wnla_rlc_prepare(bppp_ctx* c, size_t n) {
 static int wnla_rlc_final_sum(bppp_ctx* c, const WnlaWs& w, const uint8_t* rlc_seed, uint8_t* d, const WnlaRlcLayout& o, hipStream_t s) {
     const size_t n = w.N, nchunks = (n + BPPP_RLC_CHUNK - 1) / BPPP_RLC_CHUNK;
     const int NB = c->nbases;
-    const unsigned blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
-    const unsigned fb_blocks = (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
+    const unsigned blocks = blocks_of(n), fb_blocks = fb_blocks_of(n);
     int rc;
-#define RLAUNCH(id, ...)                                       \
-    do {                                                       \
-        rc = timed(c, id, s, [&]() { __VA_ARGS__; });          \
-        if (rc != BPPP_OK) return rc;                          \
-    } while (0)
     RlcWs rl;
     std::memset(&rl, 0, sizeof rl);
     for (int i = 0; i < 4; i++) {
@@ -228,15 +294,70 @@ static int wnla_rlc_final_sum(bppp_ctx* c, const WnlaWs& w, const uint8_t* rlc_s
         rl.sflag = bw.sflag;
         rl.super_m = SM;
     }
-    RLAUNCH(K_WNLA_RLC_LHS, k_wnla_rlc_lhs<<<blocks, BPPP_BLOCK, 0, s>>>(w, rl));
-    RLAUNCH(K_WNLA_RLC_CHUNK, k_wnla_rlc_chunk<<<chunk_blocks, BPPP_FB_BLOCK, 0, s>>>(w, rl));
-    RLAUNCH(K_WNLA_RLC_CHECK, k_wnla_rlc_check<<<check_blocks, 64, 0, s>>>(w, rl));
-    RLAUNCH(K_WNLA_MSM, k_wnla_msm_flagged<<<1024, 64, 0, s>>>(w, rl));
-    RLAUNCH(K_WNLA_MSM, k_wnla_msm_flagged_dense<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, rl));
-    RLAUNCH(K_WNLA_ACCEPT, k_wnla_accept_flagged<<<blocks, BPPP_BLOCK, 0, s>>>(w, rl));
-#undef RLAUNCH
+    GLAUNCH(s, K_WNLA_RLC_LHS, k_wnla_rlc_lhs<<<blocks, BPPP_BLOCK, 0, s>>>(w, rl));
+    GLAUNCH(s, K_WNLA_RLC_CHUNK, k_wnla_rlc_chunk<<<chunk_blocks, BPPP_FB_BLOCK, 0, s>>>(w, rl));
+    GLAUNCH(s, K_WNLA_RLC_CHECK, k_wnla_rlc_check<<<check_blocks, 64, 0, s>>>(w, rl));
+    GLAUNCH(s, K_WNLA_MSM, k_wnla_msm_flagged<<<1024, 64, 0, s>>>(w, rl));
+    GLAUNCH(s, K_WNLA_MSM, k_wnla_msm_flagged_dense<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, rl));
+    GLAUNCH(s, K_WNLA_ACCEPT, k_wnla_accept_flagged<<<blocks, BPPP_BLOCK, 0, s>>>(w, rl));
     return BPPP_OK;
 }
+// what the WNLA and circuit verifiers do in front of their workspace: whether the call's final sum runs in RLC mode (the rule above),
+// "last_rlc_*" reset before the first allocation (a call that fails reports nothing stale), the projective tables, the bucket stage
+static int wnla_call_prepare(bppp_ctx* c, size_t n, const uint8_t* rlc_seed, bool& rlc) {
+    rlc = rlc_seed && wnla_rlc_applies(n);
+    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
+    const int rc = ensure_straus_capacity(c, n);
+    if (rc != BPPP_OK) return rc;
+    return rlc ? wnla_rlc_prepare(c, n) : BPPP_OK;
+}
+
+// THE WNLA VERIFY STAGE, the tail of all three generic verifiers: on stream s over a prepared WnlaWs, in the form wnla_form_setup chose --
+// the transcript's start, the round points' tables, the rounds, the final scalars, the final sum and the verdicts, the transcripts out.
+// tables_done: the caller has launched the tables already (the reciprocal verifier, on its helper stream beside phase 1)
+// rlc_seed: the final sum in RLC mode over the buffers d + o_rlc (wnla_rlc_final_sum); null = every instance's own sum
+// part: the part of a multi-part call this is (its stage-3 milestone lies behind the rounds); null = the whole call
+static int wnla_verify_stage(bppp_ctx* c, const WnlaWs& w, const WnlaForm& f, hipStream_t s, bool tables_done = false,
+                             const uint8_t* rlc_seed = nullptr, uint8_t* d = nullptr, const WnlaRlcLayout& o_rlc = {0, 0, 0, 0},
+                             const GenericPart* part = nullptr) {
+    const size_t n = w.N;
+    const unsigned blocks = blocks_of(n);
+    const int grp = f.round_group;
+    int rc;
+    GLAUNCH(s, K_WNLA_BEGIN, k_wnla_begin<<<blocks, BPPP_BLOCK, 0, s>>>(w));
+    if (w.atab && !tables_done) GLAUNCH(s, K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, s));
+    for (int k = 1; k <= w.rounds; k++) {
+        if (grp > 1) GLAUNCH(s, K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, k, grp));
+        else GLAUNCH(s, K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, k));
+    }
+    rc = part_milestone(part, 3, s);
+    if (rc != BPPP_OK) return rc;
+    GLAUNCH(s, K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, f.final_lg, blocks, s));
+    if (rlc_seed) {
+        rc = wnla_rlc_final_sum(c, w, rlc_seed, d, o_rlc, s);
+        if (rc != BPPP_OK) return rc;
+    } else {
+        if (f.fb == GENERIC_FB_ONE_LANE) GLAUNCH(s, K_WNLA_MSM, k_wnla_msm_l1<<<fb1_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
+        else if (f.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
+        else GLAUNCH(s, K_WNLA_MSM, k_wnla_msm<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w, 0));
+        GLAUNCH(s, K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
+    }
+    if (w.tio.states_out) k_generic_export_states<<<blocks, BPPP_BLOCK, 0, s>>>(w);
+    HIP_TRY(hipGetLastError());
+    return BPPP_OK;
+}
+
+// what every WNLA verify entry point checks of its pointers (label: null with length 0 in the transcript form), and the sizes wnla_run
+// takes -- checked by wnla_run itself, and by the wire-form entry points before they size their staging by them
+static int wnla_verify_check(const bppp_ctx* c, const uint8_t* label, size_t label_len, const void* commitments, const void* cvec, const void* rho,
+                             const void* mu, size_t rounds, const void* proof_r, const void* proof_x, const void* proof_l, size_t nl,
+                             const void* proof_n, size_t nn, const void* accept) {
+    if (!c || !label_ok(label, label_len) || !commitments || !cvec || !rho || !mu || (rounds && (!proof_r || !proof_x)) || (!proof_l && nl) ||
+        (!proof_n && nn) || !accept)
+        return BPPP_ERR_INVALID_ARG;
+    return BPPP_OK;
+}
+static bool wnla_shape_ok(size_t rounds, size_t nl, size_t nn) { return rounds <= 12 && nl <= 4096 && nn <= 4096; }
 
 static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments,
                     const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r,
@@ -247,21 +368,16 @@ static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label
     // on the context's stream and only the workspace comes out of the context's buffer
     // rlc_seed (bppp_wnla_verify_batch_rlc[_device]): the final sum in RLC mode (wnla_rlc_final_sum, and the rule above it)
     HIP_TRY(hipSetDevice(c->device));
-    if (rounds > 12 || nl > 4096 || nn > 4096) return BPPP_ERR_INVALID_ARG;
+    if (!wnla_shape_ok(rounds, nl, nn)) return BPPP_ERR_INVALID_ARG;
     int rc = check_host_transcripts(tx, n);
     if (rc != BPPP_OK) return rc;
-    const bool rlc = rlc_seed && wnla_rlc_applies(n);
-    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }      // (before the first allocation: a call that fails reports nothing stale)
-    rc = ensure_straus_capacity(c, n);
+    bool rlc;
+    rc = wnla_call_prepare(c, n, rlc_seed, rlc);
     if (rc != BPPP_OK) return rc;
-    if (rlc) {
-        rc = wnla_rlc_prepare(c, n);
-        if (rc != BPPP_OK) return rc;
-    }
     const size_t NB = (size_t)c->nbases, T = (size_t)1 << rounds;
     // layout of the blob: inputs | outputs | workspace
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align16(off + bytes); return o; };
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes); };
     const size_t o_com = take(n * 64), o_c = take(n * (size_t)c->nh * 32), o_rho = take(n * 32), o_mu = take(n * 32),
                  o_r = take(n * rounds * 64), o_x = take(n * rounds * 64), o_l = take(n * nl * 32), o_n = take(n * nn * 32),
                  o_out = take(n * 64), o_acc = take(n), o_st = take(n * 4), o_ts = take(52 * n * 4), o_a = take(30 * n * 4),
@@ -304,43 +420,20 @@ static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label
         w.tio.no_ops = rounds == 0;
         w.divergent_positions = tx->n_states != 1;
     }
-    const unsigned blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
-    const unsigned fb_blocks = (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
+    const unsigned blocks = blocks_of(n);
     if (commit) {
         k_wnla_commit_scalars<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-        k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 1);
+        k_wnla_msm<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w, 1);
         k_wnla_commit_store<<<blocks, BPPP_BLOCK, 0, s>>>(w);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(out_points, d + o_out, n * 64, hipMemcpyDeviceToHost, s));
     } else {
-        rc = wnla_fast_setup(c, w, n, rounds, 0, nullptr, (size_t)wnla_table_parts(c, n, rounds));
+        WnlaForm f;
+        rc = wnla_form_setup(c, w, f, 0);
         if (rc != BPPP_OK) return rc;
-        const int grp = wnla_round_group(c, w, blocks), final_lg = wnla_final_scalars_group_lg(c, (unsigned)rounds, blocks);
-        const bool fb_wide = generic_fb_wide(c, n);
-        c->last_generic_form = generic_form_code(GENERIC_FORM_WNLA, w.tab_parts, grp, final_lg, fb_wide ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8);
-#define WLAUNCH(id, ...)                                       \
-    do {                                                       \
-        rc = timed(c, id, s, [&]() { __VA_ARGS__; });          \
-        if (rc != BPPP_OK) return rc;                          \
-    } while (0)
-        WLAUNCH(K_WNLA_BEGIN, k_wnla_begin<<<blocks, BPPP_BLOCK, 0, s>>>(w));
-        if (w.atab) WLAUNCH(K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, s));
-        for (int k = 1; k <= (int)rounds; k++) {
-            if (grp > 1) WLAUNCH(K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, k, grp));
-            else WLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, k));
-        }
-        WLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, final_lg, blocks, s));
-        if (rlc) {
-            rc = wnla_rlc_final_sum(c, w, rlc_seed, d, o_rlc, s);
-            if (rc != BPPP_OK) return rc;
-        } else {
-            if (fb_wide) WLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
-            else WLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
-            WLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
-        }
-#undef WLAUNCH
-        if (w.tio.states_out) k_generic_export_states<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-        HIP_TRY(hipGetLastError());
+        c->last_generic_form = generic_form_code(GENERIC_FORM_WNLA, w, f);
+        rc = wnla_verify_stage(c, w, f, s, false, rlc ? rlc_seed : nullptr, d, o_rlc);
+        if (rc != BPPP_OK) return rc;
         if (device_io) return BPPP_OK;
         HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
         if (w.tio.states_out) HIP_TRY(hipMemcpyAsync(tx->states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
@@ -363,10 +456,8 @@ int bppp_wnla_verify_batch(bppp_ctx* c, const uint8_t* label, size_t label_len, 
                            const uint8_t* proof_x, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
                            uint8_t* accept, int32_t* status) {
     CtxLock lock_(c);
-    if (!c || !label_ok(label, label_len) || !commitments || !cvec || !rho || !mu || (rounds && (!proof_r || !proof_x)) || (!proof_l && nl) ||
-        (!proof_n && nn) || !accept)
-        return BPPP_ERR_INVALID_ARG;
-    if (n == 0) return BPPP_OK;
+    const int rc = wnla_verify_check(c, label, label_len, commitments, cvec, rho, mu, rounds, proof_r, proof_x, proof_l, nl, proof_n, nn, accept);
+    if (rc != BPPP_OK || n == 0) return rc;
     return wnla_run(c, false, label, label_len, n, commitments, cvec, rho, mu, rounds, proof_r, proof_x, proof_l, nl, proof_n, nn, nullptr,
                     accept, status);
 }
@@ -375,10 +466,9 @@ int bppp_wnla_verify_batch_device(bppp_ctx* c, const uint8_t* label, size_t labe
                                   const void* d_rho, const void* d_mu, size_t rounds, const void* d_proof_r, const void* d_proof_x,
                                   const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn, void* d_accept, void* d_status) {
     CtxLock lock_(c);
-    if (!c || !label_ok(label, label_len) || !d_commitments || !d_c || !d_rho || !d_mu || (rounds && (!d_proof_r || !d_proof_x)) || (!d_proof_l && nl) ||
-        (!d_proof_n && nn) || !d_accept)
-        return BPPP_ERR_INVALID_ARG;
-    if (n == 0) return BPPP_OK;
+    const int rc = wnla_verify_check(c, label, label_len, d_commitments, d_c, d_rho, d_mu, rounds, d_proof_r, d_proof_x, d_proof_l, nl, d_proof_n, nn,
+                                     d_accept);
+    if (rc != BPPP_OK || n == 0) return rc;
     return wnla_run(c, false, label, label_len, n, (const uint8_t*)d_commitments, (const uint8_t*)d_c, (const uint8_t*)d_rho, (const uint8_t*)d_mu, rounds,
                     (const uint8_t*)d_proof_r, (const uint8_t*)d_proof_x, (const uint8_t*)d_proof_l, nl, (const uint8_t*)d_proof_n, nn, nullptr,
                     (uint8_t*)d_accept, (int32_t*)d_status, nullptr, true);
@@ -390,10 +480,9 @@ int bppp_wnla_verify_batch_rlc(bppp_ctx* c, const uint8_t* label, size_t label_l
                                const uint8_t* proof_x, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
                                uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
     CtxLock lock_(c);
-    if (!c || !seed || !label_ok(label, label_len) || !commitments || !cvec || !rho || !mu || (rounds && (!proof_r || !proof_x)) ||
-        (!proof_l && nl) || (!proof_n && nn) || !accept)
-        return BPPP_ERR_INVALID_ARG;
-    if (n == 0) return BPPP_OK;
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    const int rc = wnla_verify_check(c, label, label_len, commitments, cvec, rho, mu, rounds, proof_r, proof_x, proof_l, nl, proof_n, nn, accept);
+    if (rc != BPPP_OK || n == 0) return rc;
     return wnla_run(c, false, label, label_len, n, commitments, cvec, rho, mu, rounds, proof_r, proof_x, proof_l, nl, proof_n, nn, nullptr,
                     accept, status, nullptr, false, seed);
 }
@@ -402,10 +491,10 @@ int bppp_wnla_verify_batch_rlc_device(bppp_ctx* c, const uint8_t* label, size_t 
                                       const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn, void* d_accept, void* d_status,
                                       const uint8_t seed[32]) {
     CtxLock lock_(c);
-    if (!c || !seed || !label_ok(label, label_len) || !d_commitments || !d_c || !d_rho || !d_mu || (rounds && (!d_proof_r || !d_proof_x)) ||
-        (!d_proof_l && nl) || (!d_proof_n && nn) || !d_accept)
-        return BPPP_ERR_INVALID_ARG;
-    if (n == 0) return BPPP_OK;
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    const int rc = wnla_verify_check(c, label, label_len, d_commitments, d_c, d_rho, d_mu, rounds, d_proof_r, d_proof_x, d_proof_l, nl, d_proof_n, nn,
+                                     d_accept);
+    if (rc != BPPP_OK || n == 0) return rc;
     return wnla_run(c, false, label, label_len, n, (const uint8_t*)d_commitments, (const uint8_t*)d_c, (const uint8_t*)d_rho, (const uint8_t*)d_mu, rounds,
                     (const uint8_t*)d_proof_r, (const uint8_t*)d_proof_x, (const uint8_t*)d_proof_l, nl, (const uint8_t*)d_proof_n, nn, nullptr,
                     (uint8_t*)d_accept, (int32_t*)d_status, nullptr, true, seed);
@@ -416,10 +505,9 @@ int bppp_wnla_verify_batch_transcript(bppp_ctx* c, size_t n, const uint8_t* stat
                                       const uint8_t* proof_x, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
                                       uint8_t* accept, int32_t* status, uint8_t* states_out) {
     CtxLock lock_(c);
-    if (!c || !states || !commitments || !cvec || !rho || !mu || (rounds && (!proof_r || !proof_x)) || (!proof_l && nl) || (!proof_n && nn) ||
-        !accept)
-        return BPPP_ERR_INVALID_ARG;
-    if (n == 0) return BPPP_OK;
+    if (!states) return BPPP_ERR_INVALID_ARG;
+    const int rc = wnla_verify_check(c, nullptr, 0, commitments, cvec, rho, mu, rounds, proof_r, proof_x, proof_l, nl, proof_n, nn, accept);
+    if (rc != BPPP_OK || n == 0) return rc;
     HostTranscripts tx = {states, n_states, states_out};
     return wnla_run(c, false, nullptr, 0, n, commitments, cvec, rho, mu, rounds, proof_r, proof_x, proof_l, nl, proof_n, nn, nullptr, accept,
                     status, &tx);
@@ -427,76 +515,54 @@ int bppp_wnla_verify_batch_transcript(bppp_ctx* c, size_t n, const uint8_t* stat
 
 // ---- generic ReciprocalRangeProofProtocol::verify (reciprocal.rs:98-107) on a context built by bppp_wnla_ctx_create over
 //      g, g_vec || g_vec_, h_vec || h_vec_
-// one part of a multi-part call (recip_verify_device_entry): its stream and its shares of the context's buffers
-// (started / stage: an event recorded behind the part's stage-th milestone -- 1 phase 1, 2 the C0 stage, 3 the rounds -- that the NEXT
-// part's chain waits for, so that the chains run out of step: one part's fixed-base sums under another's one-lane kernels)
-struct GenericPart { hipStream_t s; uint8_t* gtab; pt_slot* straus; unsigned call_blocks; hipEvent_t started; int stage; int n_parts; };
-// workspace bytes (beyond the caller's commitments / proofs / accept / status) of one reciprocal verify call
-static size_t recip_verify_ws_bytes(const bppp_ctx* c, size_t n, size_t dim_nd, size_t dim_np, size_t rounds, bool rlc = false) {
+// workspace (beyond the caller's commitments / proofs / accept / status) of one reciprocal verify call: where each buffer sits, and the total
+struct RecipVerifyLayout { size_t ts, sc0, pts, a, pf, inv, wc, wcv, rho, mu, ys, tab, msc; WnlaRlcLayout rlc; size_t total; };
+static RecipVerifyLayout recip_verify_layout(const bppp_ctx* c, size_t n, size_t dim_nd, size_t dim_np, size_t rounds, bool rlc) {
     const size_t NB = (size_t)c->nbases, T = (size_t)1 << rounds, NH = (size_t)c->nh;
     size_t off = 0;
-    auto take = [&](size_t bytes) { off = align16(off + bytes); };
-    take(52 * n * 4); take((dim_nd + 6) * 8 * n * 4); take(5 * 16 * n * 4); take(30 * n * 4); take(30 * n * 4); take(dim_np * 8 * n * 4);
-    take(n * 64); take(n * NH * 32); take(n * 32); take(n * 32); take((rounds ? rounds : 1) * 8 * n * 4); take(2 * T * 8 * n * 4);
-    take(NB * 8 * n * 4);
-    if (rlc) (void)wnla_rlc_take(off, n, NB);
-    return off;
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes); };
+    RecipVerifyLayout o;
+    o.ts = take(52 * n * 4); o.sc0 = take((dim_nd + 6) * 8 * n * 4); o.pts = take(5 * 16 * n * 4); o.a = take(30 * n * 4);
+    o.pf = take(30 * n * 4); o.inv = take(dim_np * 8 * n * 4); o.wc = take(n * 64); o.wcv = take(n * NH * 32); o.rho = take(n * 32);
+    o.mu = take(n * 32); o.ys = take((rounds ? rounds : 1) * 8 * n * 4); o.tab = take(2 * T * 8 * n * 4); o.msc = take(NB * 8 * n * 4);
+    o.rlc = {0, 0, 0, 0};
+    if (rlc) o.rlc = wnla_rlc_take(off, n, NB);
+    o.total = off;
+    return o;
+}
+static size_t recip_verify_ws_bytes(const bppp_ctx* c, size_t n, size_t dim_nd, size_t dim_np, size_t rounds, bool rlc = false) {
+    return recip_verify_layout(c, n, dim_nd, dim_np, rounds, rlc).total;
 }
 // the launch sequence, every buffer in device memory; d_ws holds recip_verify_ws_bytes()
 static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
                                     const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
                                     int32_t* d_st, uint8_t* d_ws, const TranscriptIo* dtio = nullptr, const uint8_t* rlc_seed = nullptr,
                                     const GenericPart* part = nullptr) {
-    const size_t NB = (size_t)c->nbases, T = (size_t)1 << rounds, NH = (size_t)c->nh;
-    const size_t proof_bytes = 64 * (5 + 2 * rounds) + 32 * (nl + nn);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align16(off + bytes); return o; };
-    const size_t o_ts = take(52 * n * 4), o_sc0 = take((dim_nd + 6) * 8 * n * 4), o_pts = take(5 * 16 * n * 4), o_a = take(30 * n * 4),
-                 o_pf = take(30 * n * 4), o_inv = take(dim_np * 8 * n * 4), o_wc = take(n * 64), o_wcv = take(n * NH * 32), o_rho = take(n * 32),
-                 o_mu = take(n * 32), o_ys = take((rounds ? rounds : 1) * 8 * n * 4), o_tab = take(2 * T * 8 * n * 4), o_msc = take(NB * 8 * n * 4);
-    WnlaRlcLayout o_rlc = {0, 0, 0, 0};
-    if (rlc_seed) o_rlc = wnla_rlc_take(off, n, NB);
+    const RecipVerifyLayout o = recip_verify_layout(c, n, dim_nd, dim_np, rounds, rlc_seed != nullptr);
     uint8_t* d = d_ws;
     hipStream_t s = part ? part->s : c->stream;
-    pt_slot* const straus = part ? part->straus : c->d_straus;
     RecipWs r;
     std::memset(&r, 0, sizeof r);
     r.N = n; r.nd = (int)dim_nd; r.np = (int)dim_np; r.rounds = (int)rounds; r.nl = (int)nl; r.nn = (int)nn;
-    r.NG = c->ng; r.NH = c->nh; r.proof_bytes = proof_bytes;
-    r.commitments = d_com; r.proofs = d_proofs; r.status = d_st; r.tstate = (u32*)(d + o_ts);
-    r.sc0 = (u32*)(d + o_sc0); r.pts = (u32*)(d + o_pts); r.acc = (u32*)(d + o_a); r.pfix = (u32*)(d + o_pf); r.inv = (u32*)(d + o_inv);
-    r.straus = straus;
-    r.wn_commit = d + o_wc; r.wn_c = d + o_wcv; r.wn_rho = d + o_rho; r.wn_mu = d + o_mu;
+    r.NG = c->ng; r.NH = c->nh; r.proof_bytes = 64 * (5 + 2 * rounds) + 32 * (nl + nn);
+    r.commitments = d_com; r.proofs = d_proofs; r.status = d_st; r.tstate = (u32*)(d + o.ts);
+    r.sc0 = (u32*)(d + o.sc0); r.pts = (u32*)(d + o.pts); r.acc = (u32*)(d + o.a); r.pfix = (u32*)(d + o.pf); r.inv = (u32*)(d + o.inv);
+    r.straus = part ? part->straus : c->d_straus;
+    r.wn_commit = d + o.wc; r.wn_c = d + o.wcv; r.wn_rho = d + o.rho; r.wn_mu = d + o.mu;
     r.fb = fb_table_of(c, n);
     t_new(r.base, label, (u32)label_len);
     if (dtio) r.tio = *dtio;
-    WnlaWs w;
-    std::memset(&w, 0, sizeof w);
-    w.N = n; w.ng = c->ng; w.nh = c->nh; w.rounds = (int)rounds; w.nl = (int)nl; w.nn = (int)nn;
-    w.base = r.base;
-    if (dtio) { w.tio = *dtio; w.divergent_positions = dtio->n_states != 1; }
-    w.commitments = r.wn_commit; w.c = r.wn_c; w.rho = r.wn_rho; w.mu = r.wn_mu;
-    w.proof_r = r.proofs + 256; w.proof_x = r.proofs + 256 + 64 * rounds; w.proof_l = r.proofs + 320 + 128 * rounds;
-    w.proof_n = w.proof_l + 32 * nl;
-    w.stride_r = w.stride_x = w.stride_l = w.stride_n = proof_bytes;
-    w.transcript_preloaded = 1;
-    w.accept = d_acc; w.status = r.status; w.tstate = r.tstate; w.acc = r.acc; w.pfix = r.pfix;
-    w.ys = (u32*)(d + o_ys); w.tab = (u32*)(d + o_tab); w.msc = (u32*)(d + o_msc);
-    w.straus = straus;
-    w.fb = r.fb;
-    const unsigned blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
-    const unsigned fb_blocks = (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
+    WnlaWs w = wnla_ws_continuing(c, r, 5, nl, nn, d_acc, (u32*)(d + o.ys), (u32*)(d + o.tab), (u32*)(d + o.msc));
+    const unsigned blocks = blocks_of(n);
     // (the lane-group choices below go by the wavefronts of the WHOLE call: the parts of a multi-part call share the chip)
     const unsigned call_blocks = part ? part->call_blocks : blocks;
     int rc;
-#define GLAUNCH(id, ...)                                       \
-    do {                                                       \
-        rc = timed(c, id, s, [&]() { __VA_ARGS__; });          \
-        if (rc != BPPP_OK) return rc;                          \
-    } while (0)
+    // the two fixed-base sums: 8 lanes per instance, or one from the size at which one lane per instance fills the SIMDs twice over
+    const bool fb_one_lane = c->fb_one_lane_mode >= 0 ? c->fb_one_lane_mode == 1 : n >= (size_t)128 * (size_t)c->n_simds;
     // the WNLA stage's table buffer with room for the five C0 points' tables behind the round points': the variable-base part of C0 on
     // affine window tables too (and on lane groups while one lane per instance leaves wavefront slots free)
-    rc = wnla_fast_setup(c, w, n, rounds, 5, part ? part->gtab : nullptr, part ? 1 : (size_t)wnla_table_parts(c, n, rounds));
+    WnlaForm f;
+    rc = wnla_form_setup(c, w, f, 5, part, fb_one_lane);
     if (rc != BPPP_OK) return rc;
     r.atab = w.atab; r.tscr = w.tscr; r.atab_first = (int)(2 * rounds * 16 * (size_t)w.tab_parts);
     // What needs nothing but the proof bytes -- the round points' window tables -- and what needs only phase 1 -- the C0 points' tables
@@ -504,8 +570,6 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
     // half of C0 (8 lanes per instance: the kernel that fills the chip); round 6: 2^15 instances of configs[4]'s shape, where the
     // one-lane kernels are half a wavefront per SIMD, 46.6 -> 45.0 ms per batch.  With kernel timing on everything stays on one stream so
     // that the per-kernel times add up; the parts of a multi-part call are chains of their own.
-    // the two fixed-base sums: 8 lanes per instance, or one from the size at which one lane per instance fills the SIMDs twice over
-    const bool fb_one_lane = c->fb_one_lane_mode >= 0 ? c->fb_one_lane_mode == 1 : n >= (size_t)128 * (size_t)c->n_simds;
     // (only while the one-lane kernels are at most half a wavefront per SIMD: beyond that the kernels fill the chip by themselves and side
     // by side they take LONGER than one after the other, as in the u64 verifier -- 2^16 instances 79.6 ms on two streams against 79.2 on
     // one, 2^17 154.2 / 153.0, 2^18 314.3 / 301.4: profiles/r06/r06_b1_recip_beside_sizes.txt)
@@ -522,68 +586,39 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
         if (c->generic_lane_group) G = c->generic_lane_group == 2 ? 2 : 8;      // (tests: the smallest and the largest split at any size)
         else while (G < 8 && 2 * (size_t)G * call_blocks <= (size_t)c->n_simds) G *= 2;
     }
-    const bool fb_wide = !fb_one_lane && !part && generic_fb_wide(c, n);
-    const int grp_w = wnla_round_group(c, w, call_blocks), final_lg = wnla_final_scalars_group_lg(c, (unsigned)rounds, call_blocks);
-    c->last_generic_form = generic_form_code(GENERIC_FORM_RECIPROCAL, w.tab_parts, grp_w, final_lg,
-                                             fb_one_lane ? GENERIC_FB_ONE_LANE : fb_wide ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8, G, beside,
-                                             part ? part->n_parts : 1);
-#define GLAUNCH_ON(st, id, ...)                                 \
-    do {                                                        \
-        rc = timed(c, id, st, [&]() { __VA_ARGS__; });          \
-        if (rc != BPPP_OK) return rc;                           \
-    } while (0)
+    c->last_generic_form = generic_form_code(GENERIC_FORM_RECIPROCAL, w, f, G, beside, part ? part->n_parts : 1);
     if (beside) {
         HIP_TRY(hipEventRecord(c->ev_tab, s));               // (the call's inputs are ready on s)
         HIP_TRY(hipStreamWaitEvent(a, c->ev_tab, 0));
-        GLAUNCH_ON(a, K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, a));
+        GLAUNCH(a, K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, a));
     }
-    if (G > 1) GLAUNCH(K_RECIP_PHASE1, k_recip_phase1_grp<<<(unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, G));
-    else GLAUNCH(K_RECIP_PHASE1, k_recip_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    if (part && part->started && part->stage == 1) HIP_TRY(hipEventRecord(part->started, s));
+    if (G > 1) GLAUNCH(s, K_RECIP_PHASE1, k_recip_phase1_grp<<<(unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, G));
+    else GLAUNCH(s, K_RECIP_PHASE1, k_recip_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
+    rc = part_milestone(part, 1, s);
+    if (rc != BPPP_OK) return rc;
     if (beside) {
         HIP_TRY(hipEventRecord(c->ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(a, c->ev_fork, 0));
     }
-    const unsigned fb1_blocks = (unsigned)((n + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
-    if (fb_one_lane) GLAUNCH(K_RECIP_C0_FIXED, k_recip_c0_fixed_l1<<<fb1_blocks, BPPP_FB_BLOCK, 0, s>>>(r));
-    else if (fb_wide) GLAUNCH(K_RECIP_C0_FIXED, k_recip_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
-    else GLAUNCH(K_RECIP_C0_FIXED, k_recip_c0_fixed<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(r));
+    if (f.fb == GENERIC_FB_ONE_LANE) GLAUNCH(s, K_RECIP_C0_FIXED, k_recip_c0_fixed_l1<<<fb1_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    else if (f.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_RECIP_C0_FIXED, k_recip_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    else GLAUNCH(s, K_RECIP_C0_FIXED, k_recip_c0_fixed<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
     if (r.atab) {
-        const int grp = grp_w > 4 ? 4 : grp_w;      // (C0's sum: lane groups of 2 or 4)
-        GLAUNCH_ON(a, K_RECIP_C0_VAR, {
+        const int grp = f.round_group > 4 ? 4 : f.round_group;      // (C0's sum: lane groups of 2 or 4)
+        GLAUNCH(a, K_RECIP_C0_VAR, {
             k_recip_c0_tables<<<blocks, BPPP_BLOCK, 0, a>>>(r);
             if (grp > 1) k_recip_c0_var_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, a>>>(r, grp);
             else k_recip_c0_var<<<blocks, BPPP_BLOCK, 0, a>>>(r);
         });
-    } else GLAUNCH(K_RECIP_C0_VAR, k_recip_c0_var<<<blocks, BPPP_BLOCK, 0, s>>>(r));
+    } else GLAUNCH(s, K_RECIP_C0_VAR, k_recip_c0_var<<<blocks, BPPP_BLOCK, 0, s>>>(r));
     if (beside) {
         HIP_TRY(hipEventRecord(c->ev_join, a));
         HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
     }
-#undef GLAUNCH_ON
-    GLAUNCH(K_RECIP_C0_FINISH, k_recip_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    if (part && part->started && part->stage == 2) HIP_TRY(hipEventRecord(part->started, s));
-    GLAUNCH(K_WNLA_BEGIN, k_wnla_begin<<<blocks, BPPP_BLOCK, 0, s>>>(w));
-    if (w.atab && !beside) GLAUNCH(K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, s));
-    for (int k = 1; k <= (int)rounds; k++) {
-        if (grp_w > 1) GLAUNCH(K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp_w * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, k, grp_w));
-        else GLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, k));
-    }
-    if (part && part->started && part->stage == 3) HIP_TRY(hipEventRecord(part->started, s));
-    GLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, final_lg, blocks, s));
-    if (!rlc_seed) {
-        if (fb_one_lane) GLAUNCH(K_WNLA_MSM, k_wnla_msm_l1<<<fb1_blocks, BPPP_FB_BLOCK, 0, s>>>(w));
-        else if (fb_wide) GLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
-        else GLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
-        GLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
-    } else {
-        rc = wnla_rlc_final_sum(c, w, rlc_seed, d, o_rlc, s);
-        if (rc != BPPP_OK) return rc;
-    }
-    if (w.tio.states_out) k_generic_export_states<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-#undef GLAUNCH
-    HIP_TRY(hipGetLastError());
-    return BPPP_OK;
+    GLAUNCH(s, K_RECIP_C0_FINISH, k_recip_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
+    rc = part_milestone(part, 2, s);
+    if (rc != BPPP_OK) return rc;
+    return wnla_verify_stage(c, w, f, s, beside, rlc_seed, d, o.rlc, part);      // (the final sum in RLC mode whenever a seed is given, at any n)
 }
 // parts of a reciprocal verify call (see recip_verify_device_entry): by how far one lane per instance under-fills the chip; one part
 // with kernel timing on (the per-kernel times must add up), in RLC mode (its stages work on the whole batch) and for small calls
@@ -824,6 +859,14 @@ void bppp_circuit_destroy(bppp_circuit* q) {
     if (q->d_blob) (void)hipFree(q->d_blob);
     delete q;
 }
+// what every circuit verify entry point checks of its arguments (label: null with length 0 in the transcript form)
+static int circuit_verify_check(const bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, const void* commitments,
+                              const void* proofs, const void* accept, size_t rounds, size_t nl, size_t nn) {
+    if (!c || !q || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
+    const CircuitDev& cd = q->cd;
+    if (cd.nm > c->ng || cd.nv + 9 > c->nh || rounds > 12 || nl > 4096 || nn > 4096) return BPPP_ERR_INVALID_ARG;
+    return BPPP_OK;
+}
 static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
                                     const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
                                     int32_t* status, const HostTranscripts* tx, bool device_io = false, const uint8_t* rlc_seed = nullptr);
@@ -868,25 +911,19 @@ static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const ui
                                     const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
                                     int32_t* status, const HostTranscripts* tx, bool device_io, const uint8_t* rlc_seed) {
     // rlc_seed (bppp_circuit_verify_batch_rlc[_device]): the final sum in RLC mode (wnla_rlc_final_sum, and the rule above it)
-    if (!c || !q || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
+    int rc = circuit_verify_check(c, q, label, label_len, commitments, proofs, accept, rounds, nl, nn);
+    if (rc != BPPP_OK || n == 0) return rc;
     const CircuitDev& cd = q->cd;
-    if (cd.nm > c->ng || cd.nv + 9 > c->nh || rounds > 12 || nl > 4096 || nn > 4096) return BPPP_ERR_INVALID_ARG;
-    if (n == 0) return BPPP_OK;
-    int rc = check_host_transcripts(tx, n);
+    rc = check_host_transcripts(tx, n);
     if (rc != BPPP_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const bool rlc = rlc_seed && wnla_rlc_applies(n);
-    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }      // (before the first allocation: a call that fails reports nothing stale)
-    rc = ensure_straus_capacity(c, n);
+    bool rlc;
+    rc = wnla_call_prepare(c, n, rlc_seed, rlc);
     if (rc != BPPP_OK) return rc;
-    if (rlc) {
-        rc = wnla_rlc_prepare(c, n);
-        if (rc != BPPP_OK) return rc;
-    }
     const size_t NB = (size_t)c->nbases, T = (size_t)1 << rounds, NH = (size_t)c->nh, k = (size_t)cd.k, nm = (size_t)cd.nm, nv = (size_t)cd.nv;
     const size_t proof_bytes = 64 * (4 + 2 * rounds) + 32 * (nl + nn);
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align16(off + bytes); return o; };
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes); };
     const size_t o_com = take(n * k * 64), o_pr = take(n * proof_bytes), o_acc = take(n), o_st = take(n * 4), o_ts = take(52 * n * 4),
                  o_lam = take((size_t)cd.nl * 8 * n * 4), o_muv = take(nm * 8 * n * 4), o_coef = take((3 * nm + 3 * nv) * 8 * n * 4),
                  o_sc0 = take((nm + 5 + k) * 8 * n * 4), o_pts = take((4 + k) * 16 * n * 4), o_a = take(30 * n * 4), o_pf = take(30 * n * 4),
@@ -917,70 +954,33 @@ static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const ui
     r.fb = fb_table_of(c, n);
     t_new(r.base, label, (u32)label_len);
     if (tx) { r.tio.states = d + o_ti; r.tio.n_states = tx->n_states; r.tio.states_out = tx->states_out ? d + o_to : nullptr; }
-    WnlaWs w;
-    std::memset(&w, 0, sizeof w);
-    w.N = n; w.ng = c->ng; w.nh = c->nh; w.rounds = (int)rounds; w.nl = (int)nl; w.nn = (int)nn;
-    w.base = r.base; w.tio = r.tio; w.divergent_positions = tx && tx->n_states != 1;
-    w.commitments = r.wn_commit; w.c = r.wn_c; w.rho = r.wn_rho; w.mu = r.wn_mu;
-    w.proof_r = r.proofs + 256; w.proof_x = r.proofs + 256 + 64 * rounds; w.proof_l = r.proofs + 256 + 128 * rounds;
-    w.proof_n = w.proof_l + 32 * nl;
-    w.stride_r = w.stride_x = w.stride_l = w.stride_n = proof_bytes;
-    w.transcript_preloaded = 1;
-    w.accept = device_io ? accept : d + o_acc; w.status = r.status; w.tstate = r.tstate; w.acc = r.acc; w.pfix = r.pfix;
-    w.ys = (u32*)(d + o_ys); w.tab = (u32*)(d + o_tab); w.msc = (u32*)(d + o_msc);
-    w.straus = c->d_straus;
-    w.fb = r.fb;
-    const unsigned blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
-    const unsigned fb_blocks = (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
-#define CLAUNCH(id, ...)                                       \
-    do {                                                       \
-        rc = timed(c, id, s, [&]() { __VA_ARGS__; });          \
-        if (rc != BPPP_OK) return rc;                          \
-    } while (0)
-    {   // the WNLA stage's table buffer with room for the 4 + k points of C0's variable-base part behind the round points' tables
-        int rcf = wnla_fast_setup(c, w, n, rounds, 4 + k, nullptr, (size_t)wnla_table_parts(c, n, rounds));
-        if (rcf != BPPP_OK) return rcf;
-        r.atab = w.atab; r.tscr = w.tscr; r.atab_first = (int)(2 * rounds * 16 * (size_t)w.tab_parts);
-    }
+    WnlaWs w = wnla_ws_continuing(c, r, 4, nl, nn, device_io ? accept : d + o_acc, (u32*)(d + o_ys), (u32*)(d + o_tab), (u32*)(d + o_msc));
+    const unsigned blocks = blocks_of(n);
+    // the WNLA stage's table buffer with room for the 4 + k points of C0's variable-base part behind the round points' tables
+    WnlaForm f;
+    rc = wnla_form_setup(c, w, f, 4 + k);
+    if (rc != BPPP_OK) return rc;
+    r.atab = w.atab; r.tscr = w.tscr; r.atab_first = (int)(2 * rounds * 16 * (size_t)w.tab_parts);
     // C0's variable-base sum: a lane per point (L lanes per instance, tables and sum in one launch) while that stays within two
     // wavefronts per SIMD, else the one-lane kernels (five points per shared-doubling pass).  Round 6, `mixed_k2` (6 points): one
     // verify 4.74 -> 2.76 ms (this stage 3.0 -> 0.98), 8,192 instances 1.37 ms where 16,384 on the one-lane kernels take 2.64
     int L = 8;
     while (L < 4 + (int)k) L *= 2;
     const bool per_point = r.atab && !c->no_lane_groups && !c->no_split && L <= 64 && (size_t)L * blocks <= 2 * (size_t)c->n_simds;
-    const bool fb_wide = generic_fb_wide(c, n);
-    const int grp = wnla_round_group(c, w, blocks), final_lg = wnla_final_scalars_group_lg(c, (unsigned)rounds, blocks);
-    c->last_generic_form = generic_form_code(GENERIC_FORM_CIRCUIT, w.tab_parts, grp, final_lg, fb_wide ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8,
-                                             0, false, 1, per_point);
-    CLAUNCH(K_CIRCUIT_PHASE1, k_circuit_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    if (fb_wide) CLAUNCH(K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
-    else CLAUNCH(K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(r));
-    CLAUNCH(K_CIRCUIT_C0_VAR, {
+    c->last_generic_form = generic_form_code(GENERIC_FORM_CIRCUIT, w, f, 0, false, 1, per_point);
+    GLAUNCH(s, K_CIRCUIT_PHASE1, k_circuit_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
+    if (f.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    else GLAUNCH(s, K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    GLAUNCH(s, K_CIRCUIT_C0_VAR, {
         if (per_point) k_circuit_c0_var_pts<<<(unsigned)(((size_t)L * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, L);
         else {
             if (r.atab) k_circuit_c0_tables<<<blocks, BPPP_BLOCK, 0, s>>>(r);
             k_circuit_c0_var<<<blocks, BPPP_BLOCK, 0, s>>>(r);
         }
     });
-    CLAUNCH(K_CIRCUIT_C0_FINISH, k_circuit_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    CLAUNCH(K_WNLA_BEGIN, k_wnla_begin<<<blocks, BPPP_BLOCK, 0, s>>>(w));
-    if (w.atab) CLAUNCH(K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, s));
-    for (int kk = 1; kk <= (int)rounds; kk++) {
-        if (grp > 1) CLAUNCH(K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, kk, grp));
-        else CLAUNCH(K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, kk));
-    }
-    CLAUNCH(K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, final_lg, blocks, s));
-    if (rlc) {
-        rc = wnla_rlc_final_sum(c, w, rlc_seed, d, o_rlc, s);
-        if (rc != BPPP_OK) return rc;
-    } else {
-        if (fb_wide) CLAUNCH(K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
-        else CLAUNCH(K_WNLA_MSM, k_wnla_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0));
-        CLAUNCH(K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
-    }
-#undef CLAUNCH
-    if (w.tio.states_out) k_generic_export_states<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-    HIP_TRY(hipGetLastError());
+    GLAUNCH(s, K_CIRCUIT_C0_FINISH, k_circuit_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
+    rc = wnla_verify_stage(c, w, f, s, false, rlc ? rlc_seed : nullptr, d, o_rlc);
+    if (rc != BPPP_OK) return rc;
     if (device_io) return BPPP_OK;
     HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
     if (w.tio.states_out) HIP_TRY(hipMemcpyAsync(tx->states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
@@ -1054,6 +1054,153 @@ static int ct_setup(bppp_ctx* c, FbTable& fb_ct, int& ct, size_t n) {
     ct = 1;
     return BPPP_OK;
 }
+// ---- the WNLA prove stage, the tail of all three generic provers
+struct WnlaProveShape { size_t n, nl, nn, rounds, nl_f, nn_f; };      // instances | lengths of l and n | wnla_proof_shape of the two
+struct WnlaProveBufs { size_t pr, px, pl, pn, vl, vn, vc, ch, cg, prm, cm; };
+// The stage's buffers out of a caller's running layout, in two runs -- the proof fields it writes, then its state (the WNLA prover has
+// its status and transcripts between the two).  pad: bytes of slack behind each buffer, as the caller's layout has always had them.
+static void wnla_prove_take_proof(WnlaProveBufs& o, size_t& off, const WnlaProveShape& sh, size_t pad) {
+    o.pr = take_bytes(off, sh.n * sh.rounds * 64 + pad); o.px = take_bytes(off, sh.n * sh.rounds * 64 + pad);
+    o.pl = take_bytes(off, sh.n * sh.nl_f * 32 + pad); o.pn = take_bytes(off, sh.n * sh.nn_f * 32 + pad);
+}
+static void wnla_prove_take_state(WnlaProveBufs& o, size_t& off, const bppp_ctx* c, const WnlaProveShape& sh, size_t pad) {
+    const size_t n = sh.n, ng = (size_t)c->ng, nh = (size_t)c->nh;
+    o.vl = take_bytes(off, (sh.nl + 1) * 8 * n * 4 + pad); o.vn = take_bytes(off, (sh.nn + 1) * 8 * n * 4 + pad);
+    o.vc = take_bytes(off, nh * 8 * n * 4 + pad); o.ch = take_bytes(off, nh * 8 * n * 4 + pad); o.cg = take_bytes(off, (ng + 1) * 8 * n * 4 + pad);
+    o.prm = take_bytes(off, 3 * 8 * n * 4 + pad); o.cm = take_bytes(off, 16 * n * 4 + pad);
+}
+// The stage's WnlaProveWs over those buffers at d and the caller's inputs (device memory); grows the projective tables of X, R (the next
+// commitment by the relation).  Left to the caller: the transcript (base, tio, or transcript_preloaded) and the "ct_prover" table.
+static int wnla_prove_fill(bppp_ctx* c, WnlaProveWs& w, const WnlaProveShape& sh, uint8_t* d, const WnlaProveBufs& o, const uint8_t* commitments,
+                           const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, const uint8_t* l_in, const uint8_t* n_in, int32_t* status,
+                           u32* tstate, u32* msc, u32* pbuf) {
+    std::memset(&w, 0, sizeof w);
+    const int rc = ensure_straus_capacity(c, sh.n);
+    if (rc != BPPP_OK) return rc;
+    w.straus = c->d_straus;
+    w.N = sh.n; w.ng = c->ng; w.nh = c->nh; w.nl = (int)sh.nl; w.nn = (int)sh.nn; w.rounds = (int)sh.rounds; w.nl_f = (int)sh.nl_f; w.nn_f = (int)sh.nn_f;
+    w.commitments = commitments; w.c = cvec; w.rho = rho; w.mu = mu; w.l_in = l_in; w.n_in = n_in;
+    w.proof_r = d + o.pr; w.proof_x = d + o.px; w.proof_l = d + o.pl; w.proof_n = d + o.pn;
+    w.status = status; w.tstate = tstate; w.vl = (u32*)(d + o.vl); w.vn = (u32*)(d + o.vn); w.vc = (u32*)(d + o.vc);
+    w.ch = (u32*)(d + o.ch); w.cg = (u32*)(d + o.cg); w.prm = (u32*)(d + o.prm); w.com = (u32*)(d + o.cm); w.msc = msc; w.pbuf = pbuf;
+    w.fb = fb_table_of(c, sh.n);
+    return BPPP_OK;
+}
+static void wnla_prove_launch(const WnlaProveWs& w, hipStream_t s) {
+    const unsigned blocks = blocks_of(w.N), fb_blocks = fb_blocks_of(w.N);
+    k_wprove_init<<<blocks, BPPP_BLOCK, 0, s>>>(w);
+    for (int k = 0; k < w.rounds; k++) {
+        k_wprove_round_scalars<<<blocks, BPPP_BLOCK, 0, s>>>(w, k);
+        k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0, -1);
+        k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 1, k);
+        k_wprove_round_fold<<<blocks, BPPP_BLOCK, 0, s>>>(w, k);
+        if (k == 0 && w.rounds > 1) k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 2, -1);   // level 1's commitment; later levels by the relation
+    }
+    k_wprove_finish<<<blocks, BPPP_BLOCK, 0, s>>>(w);
+}
+
+// ---- the circuit prove stage, shared by the circuit prover and the reciprocal prover (whose circuit is built per call)
+struct CircuitProveBufs { size_t r9, lv, nv, lam, muv, coef, misc, msc, pb, wc, wcv, rho, mu, wlv, wnv; };
+// the stage's scalar vectors, scalar sets and what it hands to the WNLA stage, out of a caller's running layout (16 bytes of slack each)
+static CircuitProveBufs circuit_prove_take(size_t& off, const bppp_ctx* c, size_t n, size_t nm, size_t nv, size_t nl) {
+    const size_t NB = (size_t)c->nbases, NG = (size_t)c->ng, NH = (size_t)c->nh;
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes + 16); };
+    CircuitProveBufs o;
+    o.r9 = take(4 * 9 * 8 * n * 4); o.lv = take(6 * nv * 8 * n * 4); o.nv = take(4 * nm * 8 * n * 4); o.lam = take(nl * 8 * n * 4);
+    o.muv = take(nm * 8 * n * 4); o.coef = take((3 * nm + 3 * nv) * 8 * n * 4); o.misc = take(8 * 8 * n * 4); o.msc = take(3 * NB * 8 * n * 4);
+    o.pb = take(3 * 30 * n * 4); o.wc = take(n * 64); o.wcv = take(n * NH * 32); o.rho = take(n * 32); o.mu = take(n * 32);
+    o.wlv = take(n * NH * 32); o.wnv = take(n * NG * 32);
+    return o;
+}
+// those buffers into a CircuitProveWs whose N and cd are set
+static void circuit_prove_carve(CircuitProveWs& p, uint8_t* d, const CircuitProveBufs& o) {
+    const size_t n = p.N, nm = (size_t)p.cd.nm, nv = (size_t)p.cd.nv;
+    u32* r9 = (u32*)(d + o.r9);
+    p.ro = r9; p.rl = r9 + 72 * n; p.rr = r9 + 144 * n; p.rs = r9 + 216 * n;
+    u32* lv = (u32*)(d + o.lv);
+    p.lo = lv; p.ll = lv + nv * 8 * n; p.lr = lv + 2 * nv * 8 * n; p.ls = lv + 3 * nv * 8 * n; p.v1 = lv + 4 * nv * 8 * n; p.cl0 = lv + 5 * nv * 8 * n;
+    u32* nvv = (u32*)(d + o.nv);
+    p.no = nvv; p.nl = nvv + nm * 8 * n; p.nr = nvv + 2 * nm * 8 * n; p.ns = nvv + 3 * nm * 8 * n;
+    p.lamv = (u32*)(d + o.lam); p.muv = (u32*)(d + o.muv); p.coef = (u32*)(d + o.coef); p.misc = (u32*)(d + o.misc);
+    p.msc = (u32*)(d + o.msc); p.pbuf = (u32*)(d + o.pb);
+    p.wn_commit = d + o.wc; p.wn_c = d + o.wcv; p.wn_rho = d + o.rho; p.wn_mu = d + o.mu; p.wn_l = d + o.wlv; p.wn_n = d + o.wnv;
+}
+static int circuit_prove_launch(const bppp_ctx* c, const CircuitProveWs& p, hipStream_t s) {
+    const unsigned blocks = blocks_of(p.N), fb_blocks = fb_blocks_of(p.N);
+    HIP_TRY(hipMemsetAsync(p.msc, 0, 3 * (size_t)c->nbases * 8 * p.N * 4, s));     // the sets are written sparsely (slot = base index)
+    k_cprove_stage_a<<<blocks, BPPP_BLOCK, 0, s>>>(p);
+    for (int set = 0; set < 3; set++) k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, set, 0);
+    k_cprove_stage_b<<<blocks, BPPP_BLOCK, 0, s>>>(p);
+    k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 0);
+    k_cprove_stage_c<<<blocks, BPPP_BLOCK, 0, s>>>(p);
+    k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 1);
+    k_cprove_stage_d<<<blocks, BPPP_BLOCK, 0, s>>>(p);
+    return BPPP_OK;
+}
+// the WNLA stage behind it: the circuit stage's outputs in, its transcript continued
+static int wnla_prove_fill_behind(bppp_ctx* c, WnlaProveWs& w, const WnlaProveShape& sh, uint8_t* d, const WnlaProveBufs& o, const CircuitProveWs& p) {
+    const int rc = wnla_prove_fill(c, w, sh, d, o, p.wn_commit, p.wn_c, p.wn_rho, p.wn_mu, p.wn_l, p.wn_n, p.status, p.tstate, p.msc, p.pbuf);
+    w.transcript_preloaded = 1;
+    w.base = p.base; w.tio = p.tio; w.divergent_positions = p.divergent_positions;
+    return rc;
+}
+
+// ---- the proofs of the circuit and reciprocal provers back to the caller: head (4 points) | r | x | [extra: one more point] | l | n per
+//      instance out of the two stages' buffers, a flagged instance as zero bytes; then the transcripts, the draws wiped, the stream waited for
+struct ProveReturn { uint8_t* proofs; int32_t* status; const HostTranscripts* tx; TxDev* txd; DrawWipe* wipe; };
+static int prove_return_tail(const CircuitProveWs& p, const ProveReturn& r, hipStream_t s) {
+    const int rc = r.txd->finish(r.tx, p.tio, p.base, p.tstate, p.N, p.status, s);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(r.wipe->now());      // the draws cleared behind the last kernel that reads them
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPPP_OK;
+}
+// the 33-byte form: assembled and compressed on the device into d_out (the wire buffer), one copy back
+static int prove_return_sec1(const CircuitProveWs& p, const WnlaProveWs& w, const uint8_t* d_extra, uint8_t* d_out, const ProveReturn& r, hipStream_t s) {
+    const size_t n = p.N, rounds = (size_t)w.rounds, nl_f = (size_t)w.nl_f, nn_f = (size_t)w.nn_f, wP = 4 + 2 * rounds + (d_extra ? 1 : 0);
+    const size_t pb = wire_proof_bytes(wP, nl_f + nn_f);
+    WireMap wm;
+    wire_map_init(wm, n);
+    wm.zero_if = p.status;
+    wire_map_add(wm, false, p.proof_head, 256, d_out, pb, 4);
+    wire_map_add(wm, false, w.proof_r, rounds * 64, d_out + 33 * 4, pb, rounds);
+    wire_map_add(wm, false, w.proof_x, rounds * 64, d_out + 33 * (4 + rounds), pb, rounds);
+    if (d_extra) wire_map_add(wm, false, d_extra, 64, d_out + 33 * (4 + 2 * rounds), pb, 1);
+    wire_map_add(wm, true, w.proof_l, nl_f * 32, d_out + 33 * wP, pb, nl_f);
+    wire_map_add(wm, true, w.proof_n, nn_f * 32, d_out + 33 * wP + 32 * nl_f, pb, nn_f);
+    const int rc = wire_launch(wm, false, s);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(r.proofs, d_out, n * pb, hipMemcpyDeviceToHost, s));
+    if (r.status) HIP_TRY(hipMemcpyAsync(r.status, p.status, n * 4, hipMemcpyDeviceToHost, s));
+    return prove_return_tail(p, r, s);
+}
+// the 64-byte form: assembled on the host side of the copy
+static int prove_return_64(const CircuitProveWs& p, const WnlaProveWs& w, const uint8_t* d_extra, const ProveReturn& r, hipStream_t s) {
+    const size_t n = p.N, b_rx = (size_t)w.rounds * 64, b_e = d_extra ? 64 : 0, b_l = (size_t)w.nl_f * 32, b_n = (size_t)w.nn_f * 32;
+    const size_t proof_bytes = 256 + 2 * b_rx + b_e + b_l + b_n;
+    std::vector<uint8_t> head(n * 256), pe(n * b_e), pr(n * b_rx), px(n * b_rx), pl(n * b_l), pn(n * b_n);
+    std::vector<int32_t> st(n);
+    HIP_TRY(hipMemcpyAsync(head.data(), p.proof_head, n * 256, hipMemcpyDeviceToHost, s));
+    if (b_e) HIP_TRY(hipMemcpyAsync(pe.data(), d_extra, n * b_e, hipMemcpyDeviceToHost, s));
+    if (b_rx) {
+        HIP_TRY(hipMemcpyAsync(pr.data(), w.proof_r, n * b_rx, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(px.data(), w.proof_x, n * b_rx, hipMemcpyDeviceToHost, s));
+    }
+    if (b_l) HIP_TRY(hipMemcpyAsync(pl.data(), w.proof_l, n * b_l, hipMemcpyDeviceToHost, s));
+    if (b_n) HIP_TRY(hipMemcpyAsync(pn.data(), w.proof_n, n * b_n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(st.data(), p.status, n * 4, hipMemcpyDeviceToHost, s));
+    const int rc = prove_return_tail(p, r, s);
+    if (rc != BPPP_OK) return rc;
+    for (size_t i = 0; i < n; i++) {
+        uint8_t* o = r.proofs + i * proof_bytes;
+        if (st[i] != 0) { std::memset(o, 0, proof_bytes); continue; }
+        auto put = [&](const std::vector<uint8_t>& v, size_t bytes) { if (bytes) std::memcpy(o, v.data() + i * bytes, bytes); o += bytes; };
+        put(head, 256); put(pr, b_rx); put(px, b_rx); put(pe, b_e); put(pl, b_l); put(pn, b_n);
+    }
+    if (r.status) std::memcpy(r.status, st.data(), n * 4);
+    return BPPP_OK;
+}
+
 static int wnla_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, const HostTranscripts* tx, size_t n, const uint8_t* commitments,
                            const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, const uint8_t* l, size_t nl, const uint8_t* nvec, size_t nn,
                            uint8_t* proof_r, uint8_t* proof_x, uint8_t* proof_l, uint8_t* proof_n, int32_t* status, bool sec1 = false) {
@@ -1065,78 +1212,55 @@ static int wnla_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, 
     if ((rounds && (!proof_r || !proof_x)) || (nl_f && !proof_l) || (nn_f && !proof_n)) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t NB = (size_t)c->nbases, ng = (size_t)c->ng, nh = (size_t)c->nh;
+    const size_t NB = (size_t)c->nbases, nh = (size_t)c->nh;
+    const WnlaProveShape sh = {n, nl, nn, rounds, nl_f, nn_f};
+    WnlaProveBufs o;
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align16(off + bytes); return o; };
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes); };
     const size_t o_com = take(n * 64), o_c = take(n * nh * 32), o_rho = take(n * 32), o_mu = take(n * 32), o_l = take(n * nl * 32 + 16),
-                 o_n = take(n * nn * 32 + 16), o_pr = take(n * rounds * 64 + 16), o_px = take(n * rounds * 64 + 16),
-                 o_pl = take(n * nl_f * 32 + 16), o_pn = take(n * nn_f * 32 + 16), o_st = take(n * 4), o_ts = take(52 * n * 4),
-                 o_vl = take((nl + 1) * 8 * n * 4), o_vn = take((nn + 1) * 8 * n * 4), o_vc = take(nh * 8 * n * 4), o_ch = take(nh * 8 * n * 4),
-                 o_cg = take((ng + 1) * 8 * n * 4), o_prm = take(3 * 8 * n * 4), o_cm = take(16 * n * 4), o_msc = take(3 * NB * 8 * n * 4),
-                 o_pb = take(3 * 30 * n * 4);
+                 o_n = take(n * nn * 32 + 16);
+    wnla_prove_take_proof(o, off, sh, 16);
+    const size_t o_st = take(n * 4), o_ts = take(52 * n * 4);
+    wnla_prove_take_state(o, off, c, sh, 0);
+    const size_t o_msc = take(3 * NB * 8 * n * 4), o_pb = take(3 * 30 * n * 4);
     WnlaBlob blob;
     { const int rc_b = blob.take(c, off); if (rc_b != BPPP_OK) return rc_b; }
     uint8_t* d = blob.d;
     hipStream_t s = c->stream;
     const size_t o_wout = align16(n * 33), o_wout_x = o_wout + align16(n * rounds * 33);
-    if (sec1) {
-        { const int rc_w = ensure_buffer(c, c->d_wire, c->wire_bytes, o_wout_x + n * rounds * 33 + 16); if (rc_w != BPPP_OK) return rc_w; }
-        HIP_TRY(hipMemcpyAsync(c->d_wire, commitments, n * 33, hipMemcpyHostToDevice, s));
-        WireMap wm;
-        wire_map_init(wm, n);
-        wire_map_add(wm, false, c->d_wire, 33, d + o_com, 64, 1);
-        const int rc_e = wire_launch(wm, true, s);
-        if (rc_e != BPPP_OK) return rc_e;
-    } else HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * 64, hipMemcpyHostToDevice, s));
+    { const int rc_i = prover_points_in(c, sec1, commitments, d + o_com, n, 1, o_wout_x + n * rounds * 33 + 16, s); if (rc_i != BPPP_OK) return rc_i; }
     HIP_TRY(hipMemcpyAsync(d + o_c, cvec, n * nh * 32, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_rho, rho, n * 32, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_mu, mu, n * 32, hipMemcpyHostToDevice, s));
     if (nl) HIP_TRY(hipMemcpyAsync(d + o_l, l, n * nl * 32, hipMemcpyHostToDevice, s));
     if (nn) HIP_TRY(hipMemcpyAsync(d + o_n, nvec, n * nn * 32, hipMemcpyHostToDevice, s));
     WnlaProveWs w;
-    std::memset(&w, 0, sizeof w);
-    { const int rc_s = ensure_straus_capacity(c, n); if (rc_s != BPPP_OK) return rc_s; }   // window tables of X, R (next commitment by the relation)
-    w.straus = c->d_straus;
-    w.N = n; w.ng = c->ng; w.nh = c->nh; w.nl = (int)nl; w.nn = (int)nn; w.rounds = (int)rounds; w.nl_f = (int)nl_f; w.nn_f = (int)nn_f;
-    w.commitments = d + o_com; w.c = d + o_c; w.rho = d + o_rho; w.mu = d + o_mu; w.l_in = d + o_l; w.n_in = d + o_n;
-    w.proof_r = d + o_pr; w.proof_x = d + o_px; w.proof_l = d + o_pl; w.proof_n = d + o_pn;
-    w.status = (int32_t*)(d + o_st); w.tstate = (u32*)(d + o_ts); w.vl = (u32*)(d + o_vl); w.vn = (u32*)(d + o_vn); w.vc = (u32*)(d + o_vc);
-    w.ch = (u32*)(d + o_ch); w.cg = (u32*)(d + o_cg); w.prm = (u32*)(d + o_prm); w.com = (u32*)(d + o_cm); w.msc = (u32*)(d + o_msc);
-    w.pbuf = (u32*)(d + o_pb);
-    w.fb = fb_table_of(c, n);
+    int rc = wnla_prove_fill(c, w, sh, d, o, d + o_com, d + o_c, d + o_rho, d + o_mu, d + o_l, d + o_n, (int32_t*)(d + o_st), (u32*)(d + o_ts),
+                             (u32*)(d + o_msc), (u32*)(d + o_pb));
+    if (rc != BPPP_OK) return rc;
     { const int rc_ct = ct_setup(c, w.fb_ct, w.ct, n); if (rc_ct != BPPP_OK) return rc_ct; }      // l, n are the caller's secrets here (wnla.rs:152-160)
     t_new(w.base, label, (u32)label_len);
     TxDev txd;
-    int rc = txd.begin(c, tx, n, s, w.tio, w.divergent_positions);
+    rc = txd.begin(c, tx, n, s, w.tio, w.divergent_positions);
     if (rc != BPPP_OK) return rc;
     w.tio.no_ops = rounds == 0;
-    const unsigned blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
-    const unsigned fb_blocks = (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
-    k_wprove_init<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-    for (int k = 0; k < (int)rounds; k++) {
-        k_wprove_round_scalars<<<blocks, BPPP_BLOCK, 0, s>>>(w, k);
-        k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0, -1);
-        k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 1, k);
-        k_wprove_round_fold<<<blocks, BPPP_BLOCK, 0, s>>>(w, k);
-        if (k == 0 && rounds > 1) k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 2, -1);   // level 1's commitment; later levels by the relation
-    }
-    k_wprove_finish<<<blocks, BPPP_BLOCK, 0, s>>>(w);
+    wnla_prove_launch(w, s);
     HIP_TRY(hipGetLastError());
     if (rounds && sec1) {
         WireMap wm;
         wire_map_init(wm, n);
-        wire_map_add(wm, false, d + o_pr, rounds * 64, c->d_wire + o_wout, rounds * 33, rounds);
-        wire_map_add(wm, false, d + o_px, rounds * 64, c->d_wire + o_wout_x, rounds * 33, rounds);
+        wire_map_add(wm, false, d + o.pr, rounds * 64, c->d_wire + o_wout, rounds * 33, rounds);
+        wire_map_add(wm, false, d + o.px, rounds * 64, c->d_wire + o_wout_x, rounds * 33, rounds);
         rc = wire_launch(wm, false, s);
         if (rc != BPPP_OK) return rc;
         HIP_TRY(hipMemcpyAsync(proof_r, c->d_wire + o_wout, n * rounds * 33, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(proof_x, c->d_wire + o_wout_x, n * rounds * 33, hipMemcpyDeviceToHost, s));
     } else if (rounds) {
-        HIP_TRY(hipMemcpyAsync(proof_r, d + o_pr, n * rounds * 64, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(proof_x, d + o_px, n * rounds * 64, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(proof_r, d + o.pr, n * rounds * 64, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(proof_x, d + o.px, n * rounds * 64, hipMemcpyDeviceToHost, s));
     }
-    if (nl_f) HIP_TRY(hipMemcpyAsync(proof_l, d + o_pl, n * nl_f * 32, hipMemcpyDeviceToHost, s));
-    if (nn_f) HIP_TRY(hipMemcpyAsync(proof_n, d + o_pn, n * nn_f * 32, hipMemcpyDeviceToHost, s));
+    if (nl_f) HIP_TRY(hipMemcpyAsync(proof_l, d + o.pl, n * nl_f * 32, hipMemcpyDeviceToHost, s));
+    if (nn_f) HIP_TRY(hipMemcpyAsync(proof_n, d + o.pn, n * nn_f * 32, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
     rc = txd.finish(tx, w.tio, w.base, w.tstate, n, w.status, s);
     if (rc != BPPP_OK) return rc;
@@ -1170,39 +1294,29 @@ static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t*
     if ((cd.no && !w_o) || cd.nm > c->ng || cd.nv + 9 > c->nh) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t NB = (size_t)c->nbases, NG = (size_t)c->ng, NH = (size_t)c->nh, k = (size_t)cd.k, nm = (size_t)cd.nm, nv = (size_t)cd.nv,
-                 no = (size_t)cd.no, nl = (size_t)cd.nl, n_rnd = 18 + nv + nm;
+    const size_t NG = (size_t)c->ng, NH = (size_t)c->nh, k = (size_t)cd.k, nm = (size_t)cd.nm, nv = (size_t)cd.nv, no = (size_t)cd.no,
+                 n_rnd = 18 + nv + nm;
     // seeded (bppp_*_prove_batch_seeded): the draws are made on the device below instead of uploaded
     if (seed && !draw_args_ok(seed, stream_base, n, n_rnd)) return BPPP_ERR_INVALID_ARG;
-    size_t rounds, nl_f, nn_f;
-    wnla_proof_shape(NH, NG, rounds, nl_f, nn_f);
-    const size_t proof_bytes = 64 * (4 + 2 * rounds) + 32 * (nl_f + nn_f);
+    WnlaProveShape sh = {n, NH, NG, 0, 0, 0};
+    wnla_proof_shape(NH, NG, sh.rounds, sh.nl_f, sh.nn_f);
+    const size_t proof_bytes = 64 * (4 + 2 * sh.rounds) + 32 * (sh.nl_f + sh.nn_f);
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align16(off + bytes + 16); return o; };
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes + 16); };
     const size_t o_vp = take(n * k * 64), o_v = take(n * k * nv * 32), o_sv = take(n * k * 32), o_wl = take(n * nm * 32), o_wr = take(n * nm * 32),
-                 o_wo = take(n * no * 32), o_rnd = take(n * n_rnd * 32), o_head = take(n * 256), o_st = take(n * 4), o_ts = take(52 * n * 4),
-                 o_r9 = take(4 * 9 * 8 * n * 4), o_lv = take(6 * nv * 8 * n * 4), o_nv = take(4 * nm * 8 * n * 4), o_lam = take(nl * 8 * n * 4),
-                 o_muv = take(nm * 8 * n * 4), o_coef = take((3 * nm + 3 * nv) * 8 * n * 4), o_misc = take(8 * 8 * n * 4),
-                 o_msc = take(3 * NB * 8 * n * 4), o_pb = take(3 * 30 * n * 4), o_wc = take(n * 64), o_wcv = take(n * NH * 32),
-                 o_rho = take(n * 32), o_mu = take(n * 32), o_wlv = take(n * NH * 32), o_wnv = take(n * NG * 32),
-                 // WNLA prover state
-                 o_pr = take(n * rounds * 64), o_px = take(n * rounds * 64), o_pl = take(n * nl_f * 32), o_pn = take(n * nn_f * 32),
-                 o_vl = take((NH + 1) * 8 * n * 4), o_vn = take((NG + 1) * 8 * n * 4), o_vc = take(NH * 8 * n * 4), o_ch = take(NH * 8 * n * 4),
-                 o_cg = take((NG + 1) * 8 * n * 4), o_prm = take(3 * 8 * n * 4), o_cm = take(16 * n * 4), o_proofs = take(n * proof_bytes);
+                 o_wo = take(n * no * 32), o_rnd = take(n * n_rnd * 32), o_head = take(n * 256), o_st = take(n * 4), o_ts = take(52 * n * 4);
+    const CircuitProveBufs o_c = circuit_prove_take(off, c, n, nm, nv, (size_t)cd.nl);
+    WnlaProveBufs o_w;
+    wnla_prove_take_proof(o_w, off, sh, 16);
+    wnla_prove_take_state(o_w, off, c, sh, 16);
+    (void)take(n * proof_bytes);      // (unused room at the blob's end, kept: the blob's size decides which later call on the context reallocates)
     WnlaBlob blob;
     { const int rc_b = blob.take(c, off); if (rc_b != BPPP_OK) return rc_b; }
     uint8_t* d = blob.d;
     hipStream_t s = c->stream;
-    const size_t wP = 4 + 2 * rounds, wS = nl_f + nn_f, o_wout = align16(n * k * 33);
-    if (sec1) {
-        { const int rc_w = ensure_buffer(c, c->d_wire, c->wire_bytes, o_wout + n * wire_proof_bytes(wP, wS) + 16); if (rc_w != BPPP_OK) return rc_w; }
-        HIP_TRY(hipMemcpyAsync(c->d_wire, v_commitments, n * k * 33, hipMemcpyHostToDevice, s));
-        WireMap wm;
-        wire_map_init(wm, n);
-        wire_map_add(wm, false, c->d_wire, 33 * k, d + o_vp, 64 * k, k);
-        const int rc_e = wire_launch(wm, true, s);
-        if (rc_e != BPPP_OK) return rc_e;
-    } else HIP_TRY(hipMemcpyAsync(d + o_vp, v_commitments, n * k * 64, hipMemcpyHostToDevice, s));
+    const size_t o_wout = align16(n * k * 33);
+    const size_t wire_bytes = o_wout + n * wire_proof_bytes(4 + 2 * sh.rounds, sh.nl_f + sh.nn_f) + 16;
+    { const int rc_i = prover_points_in(c, sec1, v_commitments, d + o_vp, n, k, wire_bytes, s); if (rc_i != BPPP_OK) return rc_i; }
     HIP_TRY(hipMemcpyAsync(d + o_v, v, n * k * nv * 32, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_sv, s_v, n * k * 32, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_wl, w_l, n * nm * 32, hipMemcpyHostToDevice, s));
@@ -1216,15 +1330,7 @@ static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t*
     p.N = n; p.cd = cd; p.NG = c->ng; p.NH = c->nh; p.n_rnd = (int)n_rnd; p.rnd_stride = n_rnd * 32; p.part = q->d_part;
     p.v_pts = d + o_vp; p.v = d + o_v; p.s_v = d + o_sv; p.w_l = d + o_wl; p.w_r = d + o_wr; p.w_o = d + o_wo; p.rnd = d + o_rnd;
     p.proof_head = d + o_head; p.status = (int32_t*)(d + o_st); p.tstate = (u32*)(d + o_ts);
-    u32* r9 = (u32*)(d + o_r9);
-    p.ro = r9; p.rl = r9 + 72 * n; p.rr = r9 + 144 * n; p.rs = r9 + 216 * n;
-    u32* lv = (u32*)(d + o_lv);
-    p.lo = lv; p.ll = lv + nv * 8 * n; p.lr = lv + 2 * nv * 8 * n; p.ls = lv + 3 * nv * 8 * n; p.v1 = lv + 4 * nv * 8 * n; p.cl0 = lv + 5 * nv * 8 * n;
-    u32* nvv = (u32*)(d + o_nv);
-    p.no = nvv; p.nl = nvv + nm * 8 * n; p.nr = nvv + 2 * nm * 8 * n; p.ns = nvv + 3 * nm * 8 * n;
-    p.lamv = (u32*)(d + o_lam); p.muv = (u32*)(d + o_muv); p.coef = (u32*)(d + o_coef); p.misc = (u32*)(d + o_misc);
-    p.msc = (u32*)(d + o_msc); p.pbuf = (u32*)(d + o_pb);
-    p.wn_commit = d + o_wc; p.wn_c = d + o_wcv; p.wn_rho = d + o_rho; p.wn_mu = d + o_mu; p.wn_l = d + o_wlv; p.wn_n = d + o_wnv;
+    circuit_prove_carve(p, d, o_c);
     p.fb = fb_table_of(c, n);
     { const int rc_ct = ct_setup(c, p.fb_ct, p.ct, n); if (rc_ct != BPPP_OK) return rc_ct; }      // c_l, c_r, c_o, c_s: witness and blindings (circuit.rs:336-345, 469-470)
     t_new(p.base, label, (u32)label_len);
@@ -1232,87 +1338,14 @@ static int circuit_prove_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t*
     int rc = txd.begin(c, tx, n, s, p.tio, p.divergent_positions);
     if (rc != BPPP_OK) return rc;
     WnlaProveWs w;
-    std::memset(&w, 0, sizeof w);
-    { const int rc_s = ensure_straus_capacity(c, n); if (rc_s != BPPP_OK) return rc_s; }   // window tables of X, R (next commitment by the relation)
-    w.straus = c->d_straus;
-    w.N = n; w.ng = c->ng; w.nh = c->nh; w.nl = (int)NH; w.nn = (int)NG; w.rounds = (int)rounds; w.nl_f = (int)nl_f; w.nn_f = (int)nn_f;
-    w.transcript_preloaded = 1;
-    w.base = p.base; w.tio = p.tio; w.divergent_positions = p.divergent_positions;
-    w.commitments = p.wn_commit; w.c = p.wn_c; w.rho = p.wn_rho; w.mu = p.wn_mu; w.l_in = p.wn_l; w.n_in = p.wn_n;
-    w.proof_r = d + o_pr; w.proof_x = d + o_px; w.proof_l = d + o_pl; w.proof_n = d + o_pn;
-    w.status = p.status; w.tstate = p.tstate; w.vl = (u32*)(d + o_vl); w.vn = (u32*)(d + o_vn); w.vc = (u32*)(d + o_vc);
-    w.ch = (u32*)(d + o_ch); w.cg = (u32*)(d + o_cg); w.prm = (u32*)(d + o_prm); w.com = (u32*)(d + o_cm); w.msc = p.msc; w.pbuf = p.pbuf;
-    w.fb = p.fb;
-    const unsigned blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
-    const unsigned fb_blocks = (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
-    HIP_TRY(hipMemsetAsync(p.msc, 0, 3 * NB * 8 * n * 4, s));     // the sets are written sparsely (slot = base index)
-    k_cprove_stage_a<<<blocks, BPPP_BLOCK, 0, s>>>(p);
-    for (int set = 0; set < 3; set++) k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, set, 0);
-    k_cprove_stage_b<<<blocks, BPPP_BLOCK, 0, s>>>(p);
-    k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 0);
-    k_cprove_stage_c<<<blocks, BPPP_BLOCK, 0, s>>>(p);
-    k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 1);
-    k_cprove_stage_d<<<blocks, BPPP_BLOCK, 0, s>>>(p);
-    k_wprove_init<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-    for (int kk = 0; kk < (int)rounds; kk++) {
-        k_wprove_round_scalars<<<blocks, BPPP_BLOCK, 0, s>>>(w, kk);
-        k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0, -1);
-        k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 1, kk);
-        k_wprove_round_fold<<<blocks, BPPP_BLOCK, 0, s>>>(w, kk);
-        if (kk == 0 && rounds > 1) k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 2, -1);   // level 1's commitment; later levels by the relation
-    }
-    k_wprove_finish<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-    HIP_TRY(hipGetLastError());
-    if (sec1) {
-        // the proofs assembled and compressed on the device, head | r | x | l | n; a flagged instance comes out as zero bytes
-        const size_t pb = wire_proof_bytes(wP, wS);
-        uint8_t* out = c->d_wire + o_wout;
-        WireMap wm;
-        wire_map_init(wm, n);
-        wm.zero_if = p.status;
-        wire_map_add(wm, false, d + o_head, 256, out, pb, 4);
-        wire_map_add(wm, false, d + o_pr, rounds * 64, out + 33 * 4, pb, rounds);
-        wire_map_add(wm, false, d + o_px, rounds * 64, out + 33 * (4 + rounds), pb, rounds);
-        wire_map_add(wm, true, d + o_pl, nl_f * 32, out + 33 * wP, pb, nl_f);
-        wire_map_add(wm, true, d + o_pn, nn_f * 32, out + 33 * wP + 32 * nl_f, pb, nn_f);
-        rc = wire_launch(wm, false, s);
-        if (rc != BPPP_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(proofs, out, n * pb, hipMemcpyDeviceToHost, s));
-        if (status) HIP_TRY(hipMemcpyAsync(status, p.status, n * 4, hipMemcpyDeviceToHost, s));
-        rc = txd.finish(tx, p.tio, p.base, p.tstate, n, p.status, s);
-        if (rc != BPPP_OK) return rc;
-        HIP_TRY(wipe.now());
-        HIP_TRY(hipStreamSynchronize(s));
-        return BPPP_OK;
-    }
-    // assemble the proofs on the host side of the copy: head | r | x | l | n per instance
-    std::vector<uint8_t> head(n * 256), pr(n * rounds * 64), px(n * rounds * 64), pl(n * nl_f * 32), pn(n * nn_f * 32);
-    std::vector<int32_t> st(n);
-    HIP_TRY(hipMemcpyAsync(head.data(), d + o_head, head.size(), hipMemcpyDeviceToHost, s));
-    if (rounds) {
-        HIP_TRY(hipMemcpyAsync(pr.data(), d + o_pr, pr.size(), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(px.data(), d + o_px, px.size(), hipMemcpyDeviceToHost, s));
-    }
-    if (nl_f) HIP_TRY(hipMemcpyAsync(pl.data(), d + o_pl, pl.size(), hipMemcpyDeviceToHost, s));
-    if (nn_f) HIP_TRY(hipMemcpyAsync(pn.data(), d + o_pn, pn.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(st.data(), d + o_st, n * 4, hipMemcpyDeviceToHost, s));
-    rc = txd.finish(tx, p.tio, p.base, p.tstate, n, p.status, s);
+    rc = wnla_prove_fill_behind(c, w, sh, d, o_w, p);
     if (rc != BPPP_OK) return rc;
-    HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < n; i++) {
-        uint8_t* o = proofs + i * proof_bytes;
-        if (st[i] != 0) { std::memset(o, 0, proof_bytes); continue; }
-        std::memcpy(o, &head[i * 256], 256);
-        o += 256;
-        std::memcpy(o, &pr[i * rounds * 64], rounds * 64); o += rounds * 64;
-        std::memcpy(o, &px[i * rounds * 64], rounds * 64); o += rounds * 64;
-        std::memcpy(o, &pl[i * nl_f * 32], nl_f * 32); o += nl_f * 32;
-        std::memcpy(o, &pn[i * nn_f * 32], nn_f * 32);
-    }
-    if (status) std::memcpy(status, st.data(), n * 4);
-    (void)o_proofs;
-    return BPPP_OK;
+    rc = circuit_prove_launch(c, p, s);
+    if (rc != BPPP_OK) return rc;
+    wnla_prove_launch(w, s);
+    HIP_TRY(hipGetLastError());
+    const ProveReturn ret = {proofs, status, tx, &txd, &wipe};
+    return sec1 ? prove_return_sec1(p, w, nullptr, c->d_wire + o_wout, ret, s) : prove_return_64(p, w, nullptr, ret, s);
 }
 int bppp_circuit_prove_batch(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n, const uint8_t* v_commitments,
                              const uint8_t* v, const uint8_t* s_v, const uint8_t* w_l, const uint8_t* w_r, const uint8_t* w_o,
@@ -1342,15 +1375,13 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     HIP_TRY(hipSetDevice(c->device));
     RecipPattern P;
     recip_pattern_build(P, dim_nd, dim_np);
-    const size_t NB = (size_t)c->nbases, NG = (size_t)c->ng, NH = (size_t)c->nh, nd = dim_nd, np = dim_np, nm = nd, nv = nd + 1, nl = nv,
-                 n_rnd = 20 + 2 * nd;
+    const size_t NG = (size_t)c->ng, NH = (size_t)c->nh, nd = dim_nd, np = dim_np, nm = nd, nv = nd + 1, nl = nv, n_rnd = 20 + 2 * nd;
     // seeded (bppp_*_prove_batch_seeded): the draws are made on the device below instead of uploaded
     if (seed && !draw_args_ok(seed, stream_base, n, n_rnd)) return BPPP_ERR_INVALID_ARG;
-    size_t rounds, nl_f, nn_f;
-    wnla_proof_shape(NH, NG, rounds, nl_f, nn_f);
-    const size_t proof_bytes = 64 * (5 + 2 * rounds) + 32 * (nl_f + nn_f);
+    WnlaProveShape sh = {n, NH, NG, 0, 0, 0};
+    wnla_proof_shape(NH, NG, sh.rounds, sh.nl_f, sh.nn_f);
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align16(off + bytes + 16); return o; };
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes + 16); };
     const CircuitHostData& hd = P.hd;
     // circuit pattern
     const size_t o_cpl = take(hd.cpl.size() * 4), o_rl = take(hd.rl.size() * 4), o_vl = take(hd.vl.size() * 4), o_cpm = take(hd.cpm.size() * 4),
@@ -1362,15 +1393,12 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     // reciprocal stage
     const size_t o_st = take(n * 4), o_ts = take(52 * n * 4), o_inst = take((1 + np) * 8 * n * 4), o_scr = take((nd + np) * 8 * n * 4),
                  o_cpv = take(n * nv * 32), o_cpsv = take(n * 32), o_cpwr = take(n * nm * 32), o_cpvp = take(n * 64), o_prr = take(n * 64);
-    // circuit prover
-    const size_t o_head = take(n * 256), o_r9 = take(4 * 9 * 8 * n * 4), o_lv = take(6 * nv * 8 * n * 4), o_nv = take(4 * nm * 8 * n * 4),
-                 o_lam = take(nl * 8 * n * 4), o_muv = take(nm * 8 * n * 4), o_coef = take((3 * nm + 3 * nv) * 8 * n * 4), o_misc = take(8 * 8 * n * 4),
-                 o_msc = take(3 * NB * 8 * n * 4), o_pb = take(3 * 30 * n * 4), o_wc = take(n * 64), o_wcv = take(n * NH * 32),
-                 o_rho = take(n * 32), o_mu = take(n * 32), o_wlv = take(n * NH * 32), o_wnv = take(n * NG * 32);
-    // WNLA prover
-    const size_t o_pr = take(n * rounds * 64), o_px = take(n * rounds * 64), o_pl = take(n * nl_f * 32), o_pn = take(n * nn_f * 32),
-                 o_vl2 = take((NH + 1) * 8 * n * 4), o_vn2 = take((NG + 1) * 8 * n * 4), o_vc = take(NH * 8 * n * 4), o_ch = take(NH * 8 * n * 4),
-                 o_cg = take((NG + 1) * 8 * n * 4), o_prm = take(3 * 8 * n * 4), o_cm = take(16 * n * 4);
+    // circuit prover, WNLA prover
+    const size_t o_head = take(n * 256);
+    const CircuitProveBufs o_c = circuit_prove_take(off, c, n, nm, nv, nl);
+    WnlaProveBufs o_w;
+    wnla_prove_take_proof(o_w, off, sh, 16);
+    wnla_prove_take_state(o_w, off, c, sh, 16);
     WnlaBlob blob;
     { const int rc_b = blob.take(c, off); if (rc_b != BPPP_OK) return rc_b; }
     uint8_t* d = blob.d;
@@ -1381,16 +1409,9 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     HIP_TRY(up(o_cmp, hd.colmap.data(), hd.colmap.size() * 4)); HIP_TRY(up(o_al, hd.al.data(), hd.al.size() * 4)); HIP_TRY(up(o_am, hd.am.data(), hd.am.size() * 4));
     HIP_TRY(up(o_il, P.inst_l.data(), P.inst_l.size() * 4)); HIP_TRY(up(o_im, P.inst_m.data(), P.inst_m.size() * 4));
     HIP_TRY(up(o_part, P.parts.data(), P.parts.size() * 4));
-    const size_t wP = 5 + 2 * rounds, wS = nl_f + nn_f, o_wout = align16(n * 33);
-    if (sec1) {
-        { const int rc_w = ensure_buffer(c, c->d_wire, c->wire_bytes, o_wout + n * wire_proof_bytes(wP, wS) + 16); if (rc_w != BPPP_OK) return rc_w; }
-        HIP_TRY(hipMemcpyAsync(c->d_wire, commitments, n * 33, hipMemcpyHostToDevice, s));
-        WireMap wm;
-        wire_map_init(wm, n);
-        wire_map_add(wm, false, c->d_wire, 33, d + o_com, 64, 1);
-        const int rc_e = wire_launch(wm, true, s);
-        if (rc_e != BPPP_OK) return rc_e;
-    } else HIP_TRY(up(o_com, commitments, n * 64));
+    const size_t o_wout = align16(n * 33);
+    const size_t wire_bytes = o_wout + n * wire_proof_bytes(5 + 2 * sh.rounds, sh.nl_f + sh.nn_f) + 16;
+    { const int rc_i = prover_points_in(c, sec1, commitments, d + o_com, n, 1, wire_bytes, s); if (rc_i != BPPP_OK) return rc_i; }
     HIP_TRY(up(o_x, x, n * 32)); HIP_TRY(up(o_s, sblind, n * 32));
     HIP_TRY(up(o_dig, digits, n * nd * 32)); HIP_TRY(up(o_m, m, n * np * 32));
     DrawWipe wipe = {seed ? d + o_rnd : nullptr, n * n_rnd * 32, s};
@@ -1402,7 +1423,7 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     r.N = n; r.nd = (int)nd; r.np = (int)np; r.NG = c->ng; r.NH = c->nh; r.n_rnd = (int)n_rnd;
     r.commitments = d + o_com; r.x = d + o_x; r.s = d + o_s; r.digits = d + o_dig; r.m = d + o_m; r.rnd = d + o_rnd;
     r.status = (int32_t*)(d + o_st); r.tstate = (u32*)(d + o_ts); r.inst_vals = (u32*)(d + o_inst); r.scr = (u32*)(d + o_scr);
-    r.msc = (u32*)(d + o_msc); r.pbuf = (u32*)(d + o_pb);
+    r.msc = (u32*)(d + o_c.msc); r.pbuf = (u32*)(d + o_c.pb);      // (the circuit stage's: the two stages run one after the other)
     r.cp_v = d + o_cpv; r.cp_sv = d + o_cpsv; r.cp_wr = d + o_cpwr; r.cp_vpts = d + o_cpvp; r.proof_r = d + o_prr;
     r.fb = fb_table_of(c, n);
     { const int rc_ct = ct_setup(c, r.fb_ct, r.ct, n); if (rc_ct != BPPP_OK) return rc_ct; }      // the reciprocals 1 / (e + d_i) (reciprocal.rs:118)
@@ -1423,102 +1444,22 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     p.transcript_preloaded = 1;
     p.v_pts = r.cp_vpts; p.v = r.cp_v; p.s_v = r.cp_sv; p.w_l = r.digits; p.w_r = r.cp_wr; p.w_o = r.m; p.rnd = r.rnd + 32;
     p.proof_head = d + o_head; p.status = r.status; p.tstate = r.tstate;
-    u32* r9 = (u32*)(d + o_r9);
-    p.ro = r9; p.rl = r9 + 72 * n; p.rr = r9 + 144 * n; p.rs = r9 + 216 * n;
-    u32* lv = (u32*)(d + o_lv);
-    p.lo = lv; p.ll = lv + nv * 8 * n; p.lr = lv + 2 * nv * 8 * n; p.ls = lv + 3 * nv * 8 * n; p.v1 = lv + 4 * nv * 8 * n; p.cl0 = lv + 5 * nv * 8 * n;
-    u32* nvv = (u32*)(d + o_nv);
-    p.no = nvv; p.nl = nvv + nm * 8 * n; p.nr = nvv + 2 * nm * 8 * n; p.ns = nvv + 3 * nm * 8 * n;
-    p.lamv = (u32*)(d + o_lam); p.muv = (u32*)(d + o_muv); p.coef = (u32*)(d + o_coef); p.misc = (u32*)(d + o_misc);
-    p.msc = r.msc; p.pbuf = r.pbuf;
-    p.wn_commit = d + o_wc; p.wn_c = d + o_wcv; p.wn_rho = d + o_rho; p.wn_mu = d + o_mu; p.wn_l = d + o_wlv; p.wn_n = d + o_wnv;
+    circuit_prove_carve(p, d, o_c);
     p.fb = r.fb; p.fb_ct = r.fb_ct; p.ct = r.ct;
     WnlaProveWs w;
-    std::memset(&w, 0, sizeof w);
-    { const int rc_s = ensure_straus_capacity(c, n); if (rc_s != BPPP_OK) return rc_s; }   // window tables of X, R (next commitment by the relation)
-    w.straus = c->d_straus;
-    w.N = n; w.ng = c->ng; w.nh = c->nh; w.nl = (int)NH; w.nn = (int)NG; w.rounds = (int)rounds; w.nl_f = (int)nl_f; w.nn_f = (int)nn_f;
-    w.transcript_preloaded = 1;
-    w.base = r.base; w.tio = r.tio; w.divergent_positions = r.divergent_positions;
-    w.commitments = p.wn_commit; w.c = p.wn_c; w.rho = p.wn_rho; w.mu = p.wn_mu; w.l_in = p.wn_l; w.n_in = p.wn_n;
-    w.proof_r = d + o_pr; w.proof_x = d + o_px; w.proof_l = d + o_pl; w.proof_n = d + o_pn;
-    w.status = r.status; w.tstate = r.tstate; w.vl = (u32*)(d + o_vl2); w.vn = (u32*)(d + o_vn2); w.vc = (u32*)(d + o_vc);
-    w.ch = (u32*)(d + o_ch); w.cg = (u32*)(d + o_cg); w.prm = (u32*)(d + o_prm); w.com = (u32*)(d + o_cm); w.msc = p.msc; w.pbuf = p.pbuf;
-    w.fb = p.fb;
-    const unsigned blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
-    const unsigned fb_blocks = (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK);
-    HIP_TRY(hipMemsetAsync(p.msc, 0, 3 * NB * 8 * n * 4, s));
-    k_rprove_stage_r1<<<blocks, BPPP_BLOCK, 0, s>>>(r);
-    k_rprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(r);
-    k_rprove_stage_r2<<<blocks, BPPP_BLOCK, 0, s>>>(r);
-    HIP_TRY(hipMemsetAsync(p.msc, 0, 3 * NB * 8 * n * 4, s));
-    k_cprove_stage_a<<<blocks, BPPP_BLOCK, 0, s>>>(p);
-    for (int set = 0; set < 3; set++) k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, set, 0);
-    k_cprove_stage_b<<<blocks, BPPP_BLOCK, 0, s>>>(p);
-    k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 0);
-    k_cprove_stage_c<<<blocks, BPPP_BLOCK, 0, s>>>(p);
-    k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 1);
-    k_cprove_stage_d<<<blocks, BPPP_BLOCK, 0, s>>>(p);
-    k_wprove_init<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-    for (int kk = 0; kk < (int)rounds; kk++) {
-        k_wprove_round_scalars<<<blocks, BPPP_BLOCK, 0, s>>>(w, kk);
-        k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 0, -1);
-        k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 1, kk);
-        k_wprove_round_fold<<<blocks, BPPP_BLOCK, 0, s>>>(w, kk);
-        if (kk == 0 && rounds > 1) k_wprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(w, 2, -1);   // level 1's commitment; later levels by the relation
-    }
-    k_wprove_finish<<<blocks, BPPP_BLOCK, 0, s>>>(w);
-    HIP_TRY(hipGetLastError());
-    if (sec1) {
-        // the proofs assembled and compressed on the device, head | r | x | reciprocal r | l | n; a flagged instance comes out as zero bytes
-        const size_t pb = wire_proof_bytes(wP, wS);
-        uint8_t* out = c->d_wire + o_wout;
-        WireMap wm;
-        wire_map_init(wm, n);
-        wm.zero_if = r.status;
-        wire_map_add(wm, false, d + o_head, 256, out, pb, 4);
-        wire_map_add(wm, false, d + o_pr, rounds * 64, out + 33 * 4, pb, rounds);
-        wire_map_add(wm, false, d + o_px, rounds * 64, out + 33 * (4 + rounds), pb, rounds);
-        wire_map_add(wm, false, d + o_prr, 64, out + 33 * (4 + 2 * rounds), pb, 1);
-        wire_map_add(wm, true, d + o_pl, nl_f * 32, out + 33 * wP, pb, nl_f);
-        wire_map_add(wm, true, d + o_pn, nn_f * 32, out + 33 * wP + 32 * nl_f, pb, nn_f);
-        rc = wire_launch(wm, false, s);
-        if (rc != BPPP_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(proofs, out, n * pb, hipMemcpyDeviceToHost, s));
-        if (status) HIP_TRY(hipMemcpyAsync(status, r.status, n * 4, hipMemcpyDeviceToHost, s));
-        rc = txd.finish(tx, r.tio, r.base, r.tstate, n, r.status, s);
-        if (rc != BPPP_OK) return rc;
-        HIP_TRY(wipe.now());
-        HIP_TRY(hipStreamSynchronize(s));
-        return BPPP_OK;
-    }
-    std::vector<uint8_t> head(n * 256), prr(n * 64), pr(n * rounds * 64 + 1), px(n * rounds * 64 + 1), pl(n * nl_f * 32 + 1), pn(n * nn_f * 32 + 1);
-    std::vector<int32_t> st(n);
-    HIP_TRY(hipMemcpyAsync(head.data(), d + o_head, n * 256, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(prr.data(), d + o_prr, n * 64, hipMemcpyDeviceToHost, s));
-    if (rounds) {
-        HIP_TRY(hipMemcpyAsync(pr.data(), d + o_pr, n * rounds * 64, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(px.data(), d + o_px, n * rounds * 64, hipMemcpyDeviceToHost, s));
-    }
-    if (nl_f) HIP_TRY(hipMemcpyAsync(pl.data(), d + o_pl, n * nl_f * 32, hipMemcpyDeviceToHost, s));
-    if (nn_f) HIP_TRY(hipMemcpyAsync(pn.data(), d + o_pn, n * nn_f * 32, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(st.data(), d + o_st, n * 4, hipMemcpyDeviceToHost, s));
-    rc = txd.finish(tx, r.tio, r.base, r.tstate, n, r.status, s);
+    rc = wnla_prove_fill_behind(c, w, sh, d, o_w, p);
     if (rc != BPPP_OK) return rc;
-    HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < n; i++) {
-        uint8_t* o = proofs + i * proof_bytes;
-        if (st[i] != 0) { std::memset(o, 0, proof_bytes); continue; }
-        std::memcpy(o, &head[i * 256], 256); o += 256;
-        std::memcpy(o, &pr[i * rounds * 64], rounds * 64); o += rounds * 64;
-        std::memcpy(o, &px[i * rounds * 64], rounds * 64); o += rounds * 64;
-        std::memcpy(o, &prr[i * 64], 64); o += 64;
-        std::memcpy(o, &pl[i * nl_f * 32], nl_f * 32); o += nl_f * 32;
-        std::memcpy(o, &pn[i * nn_f * 32], nn_f * 32);
-    }
-    if (status) std::memcpy(status, st.data(), n * 4);
-    return BPPP_OK;
+    const unsigned blocks = blocks_of(n);
+    HIP_TRY(hipMemsetAsync(r.msc, 0, 3 * (size_t)c->nbases * 8 * n * 4, s));
+    k_rprove_stage_r1<<<blocks, BPPP_BLOCK, 0, s>>>(r);
+    k_rprove_msm<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r);
+    k_rprove_stage_r2<<<blocks, BPPP_BLOCK, 0, s>>>(r);
+    rc = circuit_prove_launch(c, p, s);
+    if (rc != BPPP_OK) return rc;
+    wnla_prove_launch(w, s);
+    HIP_TRY(hipGetLastError());
+    const ProveReturn ret = {proofs, status, tx, &txd, &wipe};
+    return sec1 ? prove_return_sec1(p, w, r.proof_r, c->d_wire + o_wout, ret, s) : prove_return_64(p, w, r.proof_r, ret, s);
 }
 int bppp_reciprocal_prove_batch(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
                                 const uint8_t* commitments, const uint8_t* x, const uint8_t* sblind, const uint8_t* digits, const uint8_t* m,
@@ -1606,13 +1547,6 @@ int bppp_reciprocal_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t 
 }
 
 // ---- circuit
-static int circuit_sec1_check(const bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, const void* commitments,
-                              const void* proofs, const void* accept, size_t rounds, size_t nl, size_t nn) {
-    if (!c || !q || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
-    const CircuitDev& cd = q->cd;
-    if (cd.nm > c->ng || cd.nv + 9 > c->nh || rounds > 12 || nl > 4096 || nn > 4096) return BPPP_ERR_INVALID_ARG;
-    return BPPP_OK;
-}
 static size_t circuit_sec1_exp_bytes(size_t n, size_t k, size_t rounds, size_t nl, size_t nn) {
     return align16(n * k * 64) + n * (64 * (4 + 2 * rounds) + 32 * (nl + nn));
 }
@@ -1631,7 +1565,7 @@ int bppp_circuit_verify_batch_sec1_device(bppp_ctx* c, const bppp_circuit* q, co
                                           const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
                                           void* d_accept, void* d_status) {
     CtxLock lock_(c);
-    int rc = circuit_sec1_check(c, q, label, label_len, d_commitments33, d_proofs33, d_accept, rounds, nl, nn);
+    int rc = circuit_verify_check(c, q, label, label_len, d_commitments33, d_proofs33, d_accept, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -1644,7 +1578,7 @@ int bppp_circuit_verify_batch_sec1(bppp_ctx* c, const bppp_circuit* q, const uin
                                    const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
                                    int32_t* status) {
     CtxLock lock_(c);
-    int rc = circuit_sec1_check(c, q, label, label_len, commitments33, proofs33, accept, rounds, nl, nn);
+    int rc = circuit_verify_check(c, q, label, label_len, commitments33, proofs33, accept, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -1667,15 +1601,6 @@ int bppp_circuit_verify_batch_sec1(bppp_ctx* c, const bppp_circuit* q, const uin
 }
 
 // ---- WeightNormLinearArgument (the commitment and proof.r / proof.x are points; proof.l / proof.n scalars, taken as they are)
-static int wnla_sec1_check(const bppp_ctx* c, const uint8_t* label, size_t label_len, const void* commitments, const void* cvec, const void* rho,
-                           const void* mu, size_t rounds, const void* proof_r, const void* proof_x, const void* proof_l, size_t nl,
-                           const void* proof_n, size_t nn, const void* accept) {
-    if (!c || !label_ok(label, label_len) || !commitments || !cvec || !rho || !mu || (rounds && (!proof_r || !proof_x)) || (!proof_l && nl) ||
-        (!proof_n && nn) || !accept)
-        return BPPP_ERR_INVALID_ARG;
-    if (rounds > 12 || nl > 4096 || nn > 4096) return BPPP_ERR_INVALID_ARG;      // (wnla_run's own check, before anything is sized by them)
-    return BPPP_OK;
-}
 static size_t wnla_sec1_exp_bytes(size_t n, size_t rounds) { return align16(n * 64) + 2 * align16(n * rounds * 64); }
 static int wnla_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* d_com33, const uint8_t* d_c,
                          const uint8_t* d_rho, const uint8_t* d_mu, size_t rounds, const uint8_t* d_r33, const uint8_t* d_x33, const uint8_t* d_l,
@@ -1698,9 +1623,10 @@ int bppp_wnla_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t
                                        const void* d_proof_x33, const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn,
                                        void* d_accept, void* d_status) {
     CtxLock lock_(c);
-    int rc = wnla_sec1_check(c, label, label_len, d_commitments33, d_c, d_rho, d_mu, rounds, d_proof_r33, d_proof_x33, d_proof_l, nl, d_proof_n,
-                             nn, d_accept);
+    int rc = wnla_verify_check(c, label, label_len, d_commitments33, d_c, d_rho, d_mu, rounds, d_proof_r33, d_proof_x33, d_proof_l, nl, d_proof_n,
+                               nn, d_accept);
     if (rc != BPPP_OK) return rc;
+    if (!wnla_shape_ok(rounds, nl, nn)) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
     rc = ensure_buffer(c, c->d_wire, c->wire_bytes, wnla_sec1_exp_bytes(n, rounds));
@@ -1714,8 +1640,9 @@ int bppp_wnla_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_
                                 const uint8_t* proof_x33, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
                                 uint8_t* accept, int32_t* status) {
     CtxLock lock_(c);
-    int rc = wnla_sec1_check(c, label, label_len, commitments33, cvec, rho, mu, rounds, proof_r33, proof_x33, proof_l, nl, proof_n, nn, accept);
+    int rc = wnla_verify_check(c, label, label_len, commitments33, cvec, rho, mu, rounds, proof_r33, proof_x33, proof_l, nl, proof_n, nn, accept);
     if (rc != BPPP_OK) return rc;
+    if (!wnla_shape_ok(rounds, nl, nn)) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t NH = (size_t)c->nh;
@@ -1791,3 +1718,4 @@ int bppp_circuit_prove_batch_seeded(bppp_ctx* c, const bppp_circuit* q, const ui
 }
 
 }  // extern "C"
+#undef GLAUNCH
