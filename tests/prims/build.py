@@ -4,7 +4,8 @@
   libbppp_prims_clang.so  ROCm's clang++ host build (prims_host.cpp): field.h's __builtin_addc / __builtin_subc carry chains
   libbppp_prims_hip.so    hipcc gfx950 build (prims_device.hip) with the product's BASE_FLAGS: the code the GPU runs
 
-A library is rebuilt when it is missing or older than any bp_pp_amd/csrc/*.h or tests/prims/* source."""
+Each library exports the dispatcher (prims_run_host / prims_run_device) and the variable-base sums (prims_run_sums_host: the one-lane
+forms; prims_run_sums_device: those and the lane-group forms).  A library is rebuilt when it is missing or older than any bp_pp_amd/csrc/*.h or tests/prims/* source."""
 import ctypes as C
 import glob
 import os
@@ -88,6 +89,12 @@ def load(backend):
     run.argtypes = [vp, vp, sz, vp, sz]
     run.restype = C.c_int
     L.run = run
+    L.prims_sum_words.argtypes = [C.c_int]
+    L.prims_sum_words.restype = C.c_int
+    run_sums = L.prims_run_sums_device if backend == "gfx950" else L.prims_run_sums_host
+    run_sums.argtypes = [C.c_uint32, vp, vp, sz]
+    run_sums.restype = C.c_int
+    L.run_sums = run_sums
     if backend != "gfx950":
         L.prims_is_clang.restype = C.c_int
     return L

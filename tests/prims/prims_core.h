@@ -8,6 +8,8 @@
 //
 // Field elements are loaded and stored limb by limb (never by struct copy); the host build sets each operand's declared magnitude,
 // so the FE_CHECK asserts of field.h guard the contract of every call.  The device build carries no magnitude.
+//
+// The variable-base sums (straus_core.h) have a second record format and entry points of their own, further down: SumForm.
 #pragma once
 #include "../../bp_pp_amd/csrc/field.h"
 #include "../../bp_pp_amd/csrc/modinv.h"
@@ -17,8 +19,10 @@
 #include "../../bp_pp_amd/csrc/verify_core.h"
 
 #define PRIM_IN_WORDS 176
-#define PRIM_OUT_WORDS 168
+#define PRIM_OUT_WORDS 200
 #define PRIM_BATCH_NMAX 48    // fe_batch_inv_lane: largest batch a record may describe
+#define PRIM_ACC_STEPS 12     // accumulator programs: most steps a record may hold
+#define PRIM_ACC_NOPROBE 0xFFu
 
 namespace prims {
 using namespace bppp;
@@ -30,7 +34,9 @@ enum Op : u32 {
     OP_BE32_TO_LIMBS = 48, OP_FE_FROM_BE, OP_SC_FROM_BE, OP_SEC1_DECOMPRESS, OP_LIMBS_TO_BE32,
     OP_PT_ADD = 64, OP_PT_DBL, OP_PT_MADD_NONID, OP_PT_MADD,
     OP_GLV = 80, OP_DRAW_SCALAR,
+    OP_ACCUM = 96, OP_RECODE, OP_TABLE,
 };
+enum AccStep : u32 { ACC_DBL = 0, ACC_MADD = 1 };
 enum Status : u32 { ST_OK = 0, ST_BAD_OP = 1, ST_BAD_PARAM = 2, ST_BAD_OFFSET = 3 };
 
 HD int mag_of(const u32* in, int k) { return (int)((in[1] >> (8 * k)) & 0xFFu); }
@@ -113,6 +119,218 @@ HD void batch_inv_case(const u32* in, u32* out, u32 n, u32 i, bool in_place) {
         }
     }
     out[160] = foreign;
+}
+
+// ---- accumulator programs (OP_ACCUM): at most PRIM_ACC_STEPS steps over the incomplete Jacobian (kind 0: ptj_dbl, ptj_madd) or XYZZ
+// (kind 1: ptz_madd) accumulator, then ptj_to_pt / ptz_to_pt.
+//   in[1]       declared magnitudes of the raw start state's coordinates (X, Y, Z | X, Y, ZZ, ZZZ), one byte each
+//   in[2]       kind | steps << 8 | raw start << 16 | probe step << 24 (PRIM_ACC_NOPROBE: none)
+//   in[4 .. 7)  one byte per step: operand index (bits 0-1) | skip << 2 | (ACC_DBL or ACC_MADD) << 4
+//   in[8 .. 88) four affine operands, x then y as 10 raw limbs each (declared magnitudes 1 and 2: a table entry whose y may be negated)
+//   in[88 ..)   the raw start state (30 or 40 limbs); without it the program starts from the empty accumulator
+// Out: the converted point out[0 .. 30), `empty` out[30], the raw Z (ZZ) after step s at out[31 + 10 s ..), and the whole raw accumulator
+// after the probe step at out[151 ..).
+HD u32 acc_step(const u32* in, u32 s) { return (in[4 + (s >> 2)] >> (8 * (s & 3))) & 0xFFu; }
+HD void acc_operand(apt& q, const u32* in, u32 step) {
+    const u32* w = in + 8 + 20 * (step & 3u);
+    ld_fe(q.x, w, 1);
+    ld_fe(q.y, w + 10, 2);
+}
+HD void accum_jacobian(const u32* in, u32* out, u32 ns, bool raw, u32 probe) {
+    ptj a;
+    bool empty = true;
+    ptj_init(a);
+    if (raw) {
+        ld_fe(a.X, in + 88, mag_of(in, 0)); ld_fe(a.Y, in + 98, mag_of(in, 1)); ld_fe(a.Z, in + 108, mag_of(in, 2));
+        empty = false;
+    }
+#pragma nounroll
+    for (u32 s = 0; s < ns; s++) {
+        const u32 b = acc_step(in, s);
+        if ((b >> 4) == ACC_DBL) {
+            ptj_dbl(a);
+        } else {
+            apt q;
+            acc_operand(q, in, b);
+            ptj_madd(a, empty, q, ((b >> 2) & 1u) != 0);
+        }
+        st_fe(out + 31 + 10 * s, a.Z);
+        if (s == probe) { st_fe(out + 151, a.X); st_fe(out + 161, a.Y); st_fe(out + 171, a.Z); }
+    }
+    pt r;
+    ptj_to_pt(r, a, empty);
+    st_pt(out, r);
+    out[30] = empty ? 1u : 0u;
+}
+HD void accum_xyzz(const u32* in, u32* out, u32 ns, bool raw, u32 probe) {
+    ptz a;
+    bool empty = true;
+    ptz_init(a);
+    if (raw) {
+        ld_fe(a.X, in + 88, mag_of(in, 0)); ld_fe(a.Y, in + 98, mag_of(in, 1));
+        ld_fe(a.ZZ, in + 108, mag_of(in, 2)); ld_fe(a.ZZZ, in + 118, mag_of(in, 3));
+        empty = false;
+    }
+#pragma nounroll
+    for (u32 s = 0; s < ns; s++) {
+        const u32 b = acc_step(in, s);
+        apt q;
+        acc_operand(q, in, b);
+        ptz_madd(a, empty, q, ((b >> 2) & 1u) != 0);
+        st_fe(out + 31 + 10 * s, a.ZZ);
+        if (s == probe) { st_fe(out + 151, a.X); st_fe(out + 161, a.Y); st_fe(out + 171, a.ZZ); st_fe(out + 181, a.ZZZ); }
+    }
+    pt r;
+    ptz_to_pt(r, a, empty);
+    st_pt(out, r);
+    out[30] = empty ? 1u : 0u;
+}
+// ---- signed 5-bit recoding (OP_RECODE) of the 2M GLV half-scalars of an M-point sum.  in[2] = M, in[3] = 1: the M scalars at in[4 + 8 j ..)
+// go through glv_decompose; in[3] = 0: glv_split contents as they stand, 12 words per point (k1[5], k2[5], neg1, neg2) at in[4 + 12 j ..).
+// Out: glv_recode5's words of stream st at out[5 st ..), its 26 window digits (glv_window_digits + glv_digit_of) one byte each
+// (magnitude | negative << 7) at out[50 + 7 st ..), its sign flag at out[120 + st].
+template <int M>
+HD void recode_case(const u32* in, u32* out, bool from_scalars) {
+    glv_words<M> g;
+#pragma nounroll
+    for (int j = 0; j < M; j++) {
+        glv_split sp;
+        if (from_scalars) {
+            sc k;
+            ld_sc(k, in + 4 + 8 * j);
+            glv_decompose(sp, k);
+        } else {
+            const u32* w = in + 4 + 12 * j;
+#pragma unroll
+            for (int i = 0; i < 5; i++) { sp.k1[i] = w[i]; sp.k2[i] = w[5 + i]; }
+            sp.neg1 = (w[10] & 1u) != 0;
+            sp.neg2 = (w[11] & 1u) != 0;
+        }
+        glv_words_set<M>(g, j, sp);
+    }
+#pragma nounroll
+    for (int st = 0; st < 2 * M; st++) {
+#pragma unroll
+        for (int i = 0; i < 5; i++) out[5 * st + i] = g.w[st][i];
+        out[120 + st] = g.neg[st] ? 1u : 0u;
+#pragma unroll
+        for (int i = 0; i < 7; i++) out[50 + 7 * st + i] = 0;
+    }
+#pragma nounroll
+    for (int i = 0; i < BPPP_STRAUS_WINDOWS; i++) {
+        const u64 pk = glv_window_digits<M>(g, i);
+#pragma nounroll
+        for (int st = 0; st < 2 * M; st++) {
+            int mag;
+            bool neg;
+            glv_digit_of<M>(g, pk, st, mag, neg);
+            out[50 + 7 * st + (i >> 2)] |= ((u32)mag | (neg ? 0x80u : 0u)) << (8 * (i & 3));
+        }
+    }
+}
+
+// ================================================================ the variable-base SUMS on tables built by the production builders
+// A second record format (SUM_IN_WORDS in, SUM_OUT_WORDS out), one record per SUM of M points: the launch's configuration word
+// (form | M << 8 | G << 16 | parts << 24) at in[0], point j as packed canonical words (x[8], y[8]; all zero = the identity sentinel) at
+// in[4 + 16 j ..), scalar j at in[84 + 8 j ..).  Out: the sum's raw coordinates out[0 .. 30), pt_to_affine of it out[30 .. 50), out[50] =
+// what the fast form returned (2: the form returns no flag), out[72] = lanes of the group whose total differs from lane 0's, out[73] = 1 when
+// a lane of the group met an exceptional addition, recomputed beside the function under test (group forms).
+#define SUM_IN_WORDS 128
+#define SUM_OUT_WORDS 80
+enum SumForm : u32 {
+    SUM_AFFINE = 0,        // straus_affine<M>
+    SUM_FAST_COMPLETE,     // straus_affine_fast<M>, then straus_affine_complete<M> if it returned false
+    SUM_SPLIT_LANES,       // straus_split_lane<M> for the 2 M parts lanes one after the other, complete additions, fallback as straus_affine_split
+    SUM_COMPLETE,          // straus_affine_complete<M> alone
+    SUM_GROUP,             // straus_affine_g4<M, G> on G lanes (device only)
+    SUM_SPLIT_GROUP,       // straus_affine_split<M, G, parts> on G lanes (device only)
+};
+HD u32 sum_cfg(u32 form, u32 m, u32 g, u32 parts) { return form | (m << 8) | (g << 16) | (parts << 24); }
+// workspace of one launch of N sums, laid out as the verifiers' (limb-major / entry-major over the instances)
+struct SumWs {
+    size_t N;
+    u32* pts;            // [16 M][N]
+    u32* tscr;           // [BPPP_TSCR_PER_POINT M 10][N]
+    apt_packed* atab;    // [max(parts, 1) M 16][N]
+};
+// tables 1P .. 16P of the record's M points by the four-inversion builder (the one-lane and lane-group sums' tables)
+template <int M>
+HD void sum_tables_build(const SumWs& w, size_t t, const u32* rec) {
+#pragma nounroll
+    for (int p = 0; p < M; p++) {
+        ws_st8(w.pts, w.N, t, 2 * p, rec + 4 + 16 * p);
+        ws_st8(w.pts, w.N, t, 2 * p + 1, rec + 4 + 16 * p + 8);
+    }
+    affine_tables_build(atab_of(w.atab, w.N, t), w.tscr, w.pts, w.N, t, M);
+}
+// table slot h M + p (part h of point p) by the one-lane builder (the split sums' tables, stride M between parts)
+template <int M>
+HD void sum_table_one(const SumWs& w, size_t t, const u32* rec, int slot, int parts) {
+    const int h = slot / M, p = slot - h * M;
+    apt P;
+    fe_from_w8(P.x, rec + 4 + 16 * p);
+    fe_from_w8(P.y, rec + 4 + 16 * p + 8);
+    affine_table_one(atab_of(w.atab, w.N, t) + slot * 16, P, 5 * split_begin(parts, h));
+}
+template <int M>
+HD void sum_scalars(glv_words<M>& g, int* pidx, const u32* rec) {
+#pragma unroll
+    for (int j = 0; j < M; j++) {
+        sc k;
+        glv_split sp;
+        ld_sc(k, rec + 84 + 8 * j);
+        glv_decompose(sp, k);
+        glv_words_set<M>(g, j, sp);
+        pidx[j] = j;
+    }
+}
+HD void sum_outputs(u32* out, const pt& r, u32 flag) {
+    st_pt(out, r);
+    apt a;
+    pt_to_affine(a, r);
+    st_fe(out + 30, a.x);
+    st_fe(out + 40, a.y);
+    out[50] = flag;
+}
+// the forms that run on one lane
+template <int M>
+HD void sum_one_lane(u32 form, int parts, const SumWs& w, size_t t, const u32* rec, u32* out) {
+    int pidx[M];
+    glv_words<M> g;
+    sum_scalars<M>(g, pidx, rec);
+    const atab_ref tab = atab_of(w.atab, w.N, t);
+    pt r;
+    u32 flag = 2;
+    if (form == SUM_AFFINE) {
+        straus_affine<M>(r, tab, pidx, g);
+    } else if (form == SUM_FAST_COMPLETE) {
+        const bool ok = straus_affine_fast<M>(r, tab, pidx, g);
+        if (!ok) straus_affine_complete<M>(r, tab, pidx, g);
+        flag = ok ? 1u : 0u;
+    } else if (form == SUM_COMPLETE) {
+        straus_affine_complete<M>(r, tab, pidx, g);
+    } else {
+        bool ok = true;
+        pt_set_identity(r);
+#pragma nounroll
+        for (int q = 0; q < 2 * M * parts; q++) {
+            pt part;
+            ok &= straus_split_lane<M>(part, tab, pidx, g, q, parts, M);
+            pt_add(r, r, part);
+        }
+        if (!ok) straus_affine_complete<M>(r, tab, pidx, g);
+        flag = ok ? 1u : 0u;
+    }
+    sum_outputs(out, r, flag);
+}
+HD bool sum_cfg_ok(u32 cfg) {
+    const u32 form = cfg & 0xFFu, m = (cfg >> 8) & 0xFFu, g = (cfg >> 16) & 0xFFu, parts = cfg >> 24;
+    if (m < 1 || m > 5) return false;
+    if (form == SUM_AFFINE || form == SUM_FAST_COMPLETE || form == SUM_COMPLETE) return g == 1 && parts == 0;
+    if (form == SUM_SPLIT_LANES) return g == 1 && (parts == 2 || parts == 4);
+    if (form == SUM_GROUP) return (g == 2 || g == 4) && parts == 0;
+    if (form == SUM_SPLIT_GROUP) return (parts == 2 || parts == 4) && (g == 8 || g == 16 || g == 32 || g == 64) && 2 * m * parts <= g;
+    return false;
 }
 
 // Evaluates one record.  `bytes` (nbytes long) is the byte-buffer side input of the byte ops, read at offset in[2].
@@ -355,6 +573,71 @@ HD void prim_eval(u32 op, const u32* in, u32* out, const uint8_t* bytes, size_t 
     case OP_DRAW_SCALAR: {   // key at in[4 .. 12), stream in[12 .. 14), counter in[14 .. 16) (low word first)
         const u64 stream = (u64)x[8] | ((u64)x[9] << 32), counter = (u64)x[10] | ((u64)x[11] << 32);
         draw_scalar_words(out, x, stream, counter);
+        break;
+    }
+    case OP_ACCUM: {
+        const u32 kind = in[2] & 0xFFu, ns = (in[2] >> 8) & 0xFFu, raw = (in[2] >> 16) & 0xFFu, probe = in[2] >> 24;
+        if (kind > 1u || ns > PRIM_ACC_STEPS || raw > 1u || (probe != PRIM_ACC_NOPROBE && probe >= ns)) { st = ST_BAD_PARAM; break; }
+#pragma nounroll
+        for (u32 s = 0; s < ns; s++) {
+            const u32 b = acc_step(in, s);
+            if ((b >> 4) > ACC_MADD || (b & 8u) || (kind == 1u && (b >> 4) == ACC_DBL)) st = ST_BAD_PARAM;
+        }
+        if (st != ST_OK) break;
+        if (kind == 0u) accum_jacobian(in, out, ns, raw != 0, probe);
+        else accum_xyzz(in, out, ns, raw != 0, probe);
+        break;
+    }
+    case OP_RECODE: {
+        if (in[3] > 1u) { st = ST_BAD_PARAM; break; }
+        switch (in[2]) {
+        case 1: recode_case<1>(in, out, in[3] != 0); break;
+        case 2: recode_case<2>(in, out, in[3] != 0); break;
+        case 3: recode_case<3>(in, out, in[3] != 0); break;
+        case 4: recode_case<4>(in, out, in[3] != 0); break;
+        case 5: recode_case<5>(in, out, in[3] != 0); break;
+        default: st = ST_BAD_PARAM;
+        }
+        break;
+    }
+    case OP_TABLE: {   // in[2] = parts | part << 8: the table of part `part` of a stream cut in `parts`; in[3] = first entry reported (1 or 9);
+                       // P affine at in[4 .. 24).  Out, for the eight entries e = in[3] + k: the stored words x[8], y[8] and beta x (aff_ld,
+                       // one multiplication) at out[24 k ..); out[192] = the doublings done first, out[193] = entries aff_ld did not return as stored
+        const u32 parts = in[2] & 0xFFu, part = (in[2] >> 8) & 0xFFu;
+        if ((parts != 1u && parts != 2u && parts != 4u && parts != 8u) || part >= parts || (in[2] >> 16) || (in[3] != 1u && in[3] != 9u)) {
+            st = ST_BAD_PARAM;
+            break;
+        }
+        apt P;
+        ld_fe(P.x, x, 1); ld_fe(P.y, x + 10, 1);
+        apt_packed tab[16];
+        const atab_ref tb = {tab, 1};
+        const int pre = 5 * split_begin((int)parts, (int)part);
+        affine_table_one(tb, P, pre);
+        fe beta;
+        glv_beta(beta);
+        u32 differ = 0;
+#pragma nounroll
+        for (int k = 0; k < 8; k++) {
+            const int e = (int)in[3] + k;
+            aff_src a;
+            aff_ld(a, tb, e);
+            u32 back[8];
+            fe bx;
+            u32* o = out + 24 * k;
+#pragma unroll
+            for (int i = 0; i < 8; i++) { o[i] = tab[e - 1].x[i]; o[8 + i] = tab[e - 1].y[i]; }
+            fe_to_w8(back, a.x);
+#pragma unroll
+            for (int i = 0; i < 8; i++) differ |= back[i] ^ o[i];
+            fe_to_w8(back, a.y);
+#pragma unroll
+            for (int i = 0; i < 8; i++) differ |= back[i] ^ o[8 + i];
+            fe_mul(bx, a.x, beta);
+            fe_to_w8(o + 16, bx);
+        }
+        out[192] = (u32)pre;
+        out[193] = differ ? 1u : 0u;
         break;
     }
     default:

@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <vector>
+
 #include "prims_core.h"
 
 #define PRIMS_API extern "C" __attribute__((visibility("default")))
@@ -24,6 +26,40 @@ PRIMS_API int prims_run_host(const uint32_t* in, uint32_t* out, size_t n, const 
     for (size_t r = 0; r < n; r++) {
         const uint32_t* rin = in + r * PRIM_IN_WORDS;
         prims::prim_eval(rin[0], rin, out + r * PRIM_OUT_WORDS, bytes, nbytes);
+    }
+    return 0;
+}
+
+// The one-lane forms of the variable-base sums (prims_core.h: SumForm), one record after another with a workspace of its own (N = 1).
+template <int M>
+static void sums_host(uint32_t cfg, const uint32_t* in, uint32_t* out, size_t n) {
+    const uint32_t form = cfg & 0xFFu, parts = cfg >> 24, np = parts ? parts : 1;
+    std::vector<uint32_t> pts(16 * M), tscr(BPPP_TSCR_PER_POINT * M * 10);
+    std::vector<bppp::apt_packed> atab((size_t)np * M * 16);
+    const prims::SumWs w = {1, pts.data(), tscr.data(), atab.data()};
+    for (size_t r = 0; r < n; r++) {
+        const uint32_t* rec = in + r * SUM_IN_WORDS;
+        uint32_t* o = out + r * SUM_OUT_WORDS;
+        if (rec[0] != cfg) { o[SUM_OUT_WORDS - 1] = prims::ST_BAD_PARAM; continue; }
+        if (form == prims::SUM_SPLIT_LANES) {
+            for (int slot = 0; slot < (int)parts * M; slot++) prims::sum_table_one<M>(w, 0, rec, slot, (int)parts);
+        } else {
+            prims::sum_tables_build<M>(w, 0, rec);
+        }
+        prims::sum_one_lane<M>(form, (int)parts, w, 0, rec, o);
+        o[SUM_OUT_WORDS - 1] = prims::ST_OK;
+    }
+}
+PRIMS_API int prims_sum_words(int which) { return which == 0 ? SUM_IN_WORDS : SUM_OUT_WORDS; }
+// n records of one configuration (cfg = prims::sum_cfg).  Returns 0, or -1 for a configuration the host cannot run.
+PRIMS_API int prims_run_sums_host(uint32_t cfg, const uint32_t* in, uint32_t* out, size_t n) {
+    if (!prims::sum_cfg_ok(cfg) || (cfg & 0xFFu) >= prims::SUM_GROUP) return -1;
+    switch ((cfg >> 8) & 0xFFu) {
+    case 1: sums_host<1>(cfg, in, out, n); break;
+    case 2: sums_host<2>(cfg, in, out, n); break;
+    case 3: sums_host<3>(cfg, in, out, n); break;
+    case 4: sums_host<4>(cfg, in, out, n); break;
+    default: sums_host<5>(cfg, in, out, n); break;
     }
     return 0;
 }

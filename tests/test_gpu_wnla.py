@@ -154,3 +154,74 @@ def test_wnla_prove_byte_identical_and_verifies(ng, nh, B):
         assert st2[0] == 1 and not st2[1:].any() and not pr2[0].any() and (pr2[1:] == pr[1:]).all() and (pl2[1:] == pl[1:]).all()
     finally:
         w.close()
+
+
+_COINCIDENT = {}
+
+
+def _coincident_case():
+    import wnla_cases
+    if "case" not in _COINCIDENT:
+        _COINCIDENT["case"] = wnla_cases.make_coincident(base=40, copies=2)
+    return _COINCIDENT["case"]
+
+
+def _sec1(points):
+    from bp_pp_amd import wire
+    flat = points.reshape(-1, 64)
+    return np.frombuffer(b"".join(wire.compress_point(bytes(v)) for v in flat), np.uint8).reshape(points.shape[:-1] + (33,)).copy()
+
+
+@pytest.mark.parametrize("group", ["0", "2", "4", "none"])
+def test_accepted_instances_with_coincident_points(group, monkeypatch):
+    """Valid WNLA instances whose points coincide (wnla_cases.make_coincident: everything the identity, identity round points beside
+    real ones, first-round X = R over repeated generators; the fixture asserts the oracle's accept and the coincidence in the proof
+    bytes), 80 instances with ordinary ones between them, through the round sums on one, two or four lanes per instance
+    (BPPP_GENERIC_LANE_GROUP / BPPP_NO_LANE_GROUPS as in test_c0_points_that_meet_in_the_window_sum): every instance is accepted with
+    status 0, and its copy with one flipped bit in a final scalar is rejected.  Under the default setting also through
+    verify_batch_rlc and the SEC1 entry point (the identity as 33 zero bytes).
+
+    The window digits of a round's two scalars come from a hash, so whether an instance with X = R meets the exceptional addition of
+    the incomplete accumulator cannot be chosen here; tests/test_prims.py (test_sums_one_lane, test_sums_lane_groups) is the coverage
+    of that path that is certain.  This test shows that accepted inputs with coincident points survive every launch form end to end."""
+    import torch
+    if torch.cuda.device_count() == 0:
+        pytest.fail("needs a GPU")
+    from bp_pp_amd.wnla import WeightNormLinearArgument
+    monkeypatch.delenv("BPPP_GENERIC_LANE_GROUP", raising=False)
+    monkeypatch.delenv("BPPP_NO_LANE_GROUPS", raising=False)
+    if group == "none":
+        monkeypatch.setenv("BPPP_NO_LANE_GROUPS", "1")
+    elif group != "0":
+        monkeypatch.setenv("BPPP_GENERIC_LANE_GROUP", group)
+    case = _coincident_case()
+    B = case["commitments"].shape[0]
+    assert B == 80
+    args = dict(commitments=case["commitments"], c=case["c"], rho=case["rho"], mu=case["mu"], proof_r=case["proof_r"],
+                proof_x=case["proof_x"], proof_l=case["proof_l"], proof_n=case["proof_n"])
+    pl = case["proof_l"].copy(); pl[:, 0, 31] ^= 1                 # every instance tampered: the verdict of each is its own
+    pn = case["proof_n"].copy(); pn[::2, -1, 30] ^= 0x20           # every second one: rejected ones beside accepted ones
+    w = WeightNormLinearArgument(case["g"], case["gv"], case["hv"], device=0, fb_window_bits=16)
+    try:
+        acc, st = w.verify_batch(case["label"], **args)
+        assert acc.tolist() == [1] * B and not st.any(), [case["kind"][b] for b in range(B) if not acc[b]]
+        acc, st = w.verify_batch(case["label"], **dict(args, proof_l=pl))
+        assert acc.tolist() == [0] * B and not st.any()
+        acc, st = w.verify_batch(case["label"], **dict(args, proof_n=pn))
+        assert acc.tolist() == [b % 2 for b in range(B)] and not st.any()
+        if group == "0":
+            seed = bytes(range(11, 43))
+            acc, st = w.verify_batch_rlc(case["label"], seed=seed, **args)
+            assert acc.tolist() == [1] * B and not st.any(), [case["kind"][b] for b in range(B) if not acc[b]]
+            acc, st = w.verify_batch_rlc(case["label"], seed=seed, **dict(args, proof_n=pn))
+            assert acc.tolist() == [b % 2 for b in range(B)] and not st.any()
+            s1 = dict(commitments33=_sec1(case["commitments"]), c=case["c"], rho=case["rho"], mu=case["mu"],
+                      proof_r33=_sec1(case["proof_r"]), proof_x33=_sec1(case["proof_x"]), proof_l=case["proof_l"], proof_n=case["proof_n"])
+            zero_b = case["kind"].index("zero")
+            assert not s1["commitments33"][zero_b].any() and not s1["proof_r33"][zero_b].any()
+            acc, st = w.verify_batch_sec1(case["label"], **s1)
+            assert acc.tolist() == [1] * B and not st.any(), [case["kind"][b] for b in range(B) if not acc[b]]
+            acc, st = w.verify_batch_sec1(case["label"], **dict(s1, proof_n=pn))
+            assert acc.tolist() == [b % 2 for b in range(B)] and not st.any()
+    finally:
+        w.close()

@@ -11,7 +11,20 @@ Operands enter as raw limb vectors at the bounds of each function's contract (ma
 record is checked three ways, all exact: its value against the big-integer reference, its raw output words against what the
 function promises (magnitude-1 limbs after a product, canonical after fe_normalize, below n for every scalar), and its raw words
 against the other builds (identical bits, not merely congruent).  On the device the record set runs shuffled (wavefronts mix op
-codes and byte offsets) and sorted by op code (uniform wavefronts); both runs must agree word for word."""
+codes and byte offsets) and sorted by op code (uniform wavefronts); both runs must agree word for word.
+
+Three families go past single calls.  `accum`: programs of up to 12 steps (ptj_dbl, ptj_madd / ptz_madd with a skip bit) over the
+incomplete Jacobian and XYZZ accumulators and their conversion, from the empty accumulator or raw limbs at the magnitude bounds,
+with acc = q and acc = -q at the first, a middle and the last step: where no exceptional addition occurred the result is the
+big-integer sum, where one did Z (ZZ) is 0 mod p after that step and every later one.  `recode`: glv_recode5, glv_window_digits and
+glv_digit_of for glv_words<1 .. 5>: the 26 digits rebuild the signed half-scalar of glv_model and stay within the 16 table entries.
+`table`: affine_table_one for every number of doublings split_begin yields, entry by entry, with the beta-frame twin.
+
+The variable-base SUMS have records and kernels of their own (prims_core.h: SumForm): straus_affine, straus_affine_fast +
+straus_affine_complete, straus_affine_complete and straus_split_lane on one lane (all builds), straus_affine_g4<M, G> and
+straus_affine_split<M, G, PARTS> on their real lane groups (device), over tables built by affine_tables_build / affine_table_one.
+Every sum is compared with sum_i k_i P_i of the oracle, for equal, opposite and identity points too, so a fallback that returned a
+wrong point fails here; the fast forms' flag is compared with a group-element model of the same lane."""
 import math
 import random
 import struct
@@ -26,7 +39,8 @@ from prims import build as PB
 P, N, LAM, BETA = O.P, O.N, O.LAMBDA, O.BETA
 ND = 2**256 - N
 M26, M22 = (1 << 26) - 1, (1 << 22) - 1
-IN_W, OUT_W = 176, 168
+IN_W, OUT_W = 176, 200
+SUM_IN_W, SUM_OUT_W = 128, 80
 
 # op codes: prims_core.h enum Op
 FE_MUL, FE_SQR, FE_MUL2_ADD, FE_MUL_SMALL, FE_ADD, FE_SUB_M, FE_NEG_M, FE_NORMALIZE = range(1, 9)
@@ -35,8 +49,10 @@ SC_ADD, SC_SUB, SC_NEG, SC_MUL, SC_SQR, SC_REDUCE512, DRAW_REDUCE512, SC_INV, SC
 BE32_TO_LIMBS, FE_FROM_BE, SC_FROM_BE, SEC1_DECOMPRESS, LIMBS_TO_BE32 = range(48, 53)
 PT_ADD, PT_DBL, PT_MADD_NONID, PT_MADD = range(64, 68)
 GLV, DRAW_SCALAR = 80, 81
+ACCUM, RECODE, TABLE = 96, 97, 98
 
-FAMILIES = ("fp_products", "fp_linear", "fp_normalize", "fn", "fn_wrap", "inversion", "bytes_sec1", "group", "glv", "draw")
+FAMILIES = ("fp_products", "fp_linear", "fp_normalize", "fn", "fn_wrap", "inversion", "bytes_sec1", "group", "glv", "draw",
+            "accum", "recode", "table")
 
 # ---------------------------------------------------------------- limb vectors
 P_LIMBS = [0x3FFFC2F, 0x3FFFFBF] + [M26] * 7 + [M22]                 # p itself, 26-bit limbs
@@ -145,6 +161,7 @@ class Cases:
     def __init__(self):
         self.recs, self.meta = [], []
         self.bytes = bytearray(64)      # offsets are taken mod 16 against a 64-byte aligned buffer (both host and device)
+        self.same_probe = []            # (record, record): two accumulator programs whose probed raw limbs must be identical
 
     def add(self, family, op, words=(), mags=(), p2=0, p3=0, check=None, desc=""):
         r = [0] * IN_W
@@ -598,14 +615,19 @@ def glv_model(k):
     return r1, r2
 
 
-def _glv(C, rg):
-    F = "glv"
+def _glv_scalars(rg):
     a1, b1 = 0x3086D221A7D46BCDE86C90E49284EB15, -0xE4437ED6010E88286F547FA90ABFE4C3
     a2, b2 = 0x114CA50F7A8E2F3F657C1108D9D44CFD8, 0x3086D221A7D46BCDE86C90E49284EB15
     corners = [((u * a1 + v * a2) // 2 + (u * b1 + v * b2) // 2 * LAM + d) % N for u in (-1, 1) for v in (-1, 1) for d in range(-3, 4)]
     structured = [(i * N) // 64 + j for i in range(64) for j in (-1, 0, 1)] + [(1 << i) % N for i in range(0, 256, 7)]
     ks = [0, 1, 2, N - 1, N // 2, LAM, N - LAM, 2**128, 2**255] + corners + [x % N for x in structured] + \
          [rg.randrange(N) for _ in range(200)]
+    return ks
+
+
+def _glv(C, rg):
+    F = "glv"
+    ks = _glv_scalars(rg)
 
     def chk(o, k):
         k1, k2 = wval(o[0:5]), wval(o[5:10])
@@ -618,6 +640,276 @@ def _glv(C, rg):
         assert (s1 % N, s2 % N) == (r1, r2), "the rounded lattice split"
     for k in ks:
         C.add(F, GLV, w8(k), check=lambda o, k=k: chk(o, k), desc="glv_decompose")
+
+
+# ---------------------------------------------------------------- accumulator programs (ptj_dbl, ptj_madd, ptz_madd, ptj_to_pt, ptz_to_pt)
+JAC, XYZZ = 0, 1
+NOPROBE = 0xFF
+OFF5 = sum(16 << (5 * i) for i in range(26))
+
+
+def rep_top(x, m):
+    """x mod p with every limb within one magnitude-1 step of the bound of magnitude m."""
+    base = maxv(m - 1) if m > 1 else [0] * 10
+    return vadd(limbs((x - val(base)) % P), base)
+
+
+def negrep(y):
+    """y as fe_neg_m<1> of the canonical limbs of -y leaves it: 4p - (p - y), magnitude 2 (a table entry taken with a negative digit)."""
+    return [4 * pl - l for pl, l in zip(P_LIMBS, limbs((P - y) % P))]
+
+
+def endo(p):
+    return None if p is None else (BETA * p[0] % P, p[1])
+
+
+def acc_model(steps, ops, start):
+    """The accumulator as a group element: after every step (sum, empty, met an exceptional addition)."""
+    S, empty, bad, trace = start, start is None, False, []
+    for st in steps:
+        if st[0] == "d":
+            if not empty and not bad:
+                S = O.pt_add(S, S)
+        elif not st[2]:
+            q = ops[st[1]]
+            if empty:
+                S, empty = q, False
+            elif not bad:
+                if S[0] == q[0]:
+                    bad = True            # acc = q or acc = -q: H = 0 (P = 0), Z3 (ZZ3) = 0 from here on
+                else:
+                    S = O.pt_add(S, q)
+        trace.append((S, empty, bad))
+    return trace
+
+
+def _accum(C, rg):
+    F = "accum"
+    rp = lambda: O.pt_mul(O.G, rg.randrange(1, N))
+
+    def add(kind, steps, ops, desc, start=None, probe=NOPROBE, zmag=1):
+        assert len(steps) <= 12 and len(ops) <= 4
+        sb = [0] * 12
+        for i, st in enumerate(steps):
+            sb[i] = 0 if st[0] == "d" else (st[1] | (int(st[2]) << 2) | (1 << 4))
+        words = [sum(sb[4 * w + k] << (8 * k) for k in range(4)) for w in range(3)] + [0]
+        for k in range(4):
+            q = ops[k] if k < len(ops) else O.G
+            words += limbs(q[0]) + (negrep(q[1]) if (k + len(steps)) & 1 else limbs(q[1]))
+        mags = ()
+        if start is not None:
+            z = rg.randrange(1, P)
+            if kind == JAC:
+                mags = (6, 3, 2)
+                words += rep_top(start[0] * z * z, 6) + rep_top(start[1] * z**3, 3) + rep_top(z, 2)
+            else:
+                mags = (6, 3, zmag, zmag)
+                words += rep_top(start[0] * z * z, 6) + rep_top(start[1] * z**3, 3) + rep_top(z * z, zmag) + rep_top(z**3, zmag)
+        trace = acc_model(steps, ops, start)
+        # Z of the Jacobian law: a product doubled (2) or a product (1); ZZ of the XYZZ law: a product (1)
+        # after an addition that was carried out, afterwards 1; a skipped step keeps the raw start's (zmag)
+        added = [any(st[0] == "a" and not st[2] for st in steps[:s_ + 1]) for s_ in range(len(steps))]
+        zbound = [2 if kind == JAC else (1 if a else zmag) for a in added]
+
+        def chk(o):
+            for s_, (S, empty, bad) in enumerate(trace):
+                z_ = o[31 + 10 * s_:41 + 10 * s_]
+                assert mag_ok(z_, zbound[s_]), f"Z magnitude after step {s_}"
+                if bad:
+                    assert val(z_) % P == 0, f"Z = 0 after step {s_} (exceptional addition before)"
+                elif not empty:
+                    assert val(z_) % P != 0, f"Z != 0 after step {s_}"
+            S, empty, bad = trace[-1] if trace else (start, start is None, False)
+            assert int(o[30]) == int(empty), "empty"
+            for c in range(3):
+                assert mag_ok(o[10 * c:10 * c + 10], 1), f"converted coordinate {c} magnitude"
+            X, Y, Z = (val(o[10 * c:10 * c + 10]) % P for c in range(3))
+            if bad:
+                return                    # the sum is re-done by the caller: only the zero Z is promised
+            if empty:
+                assert (X, Y, Z) == (0, 1, 0), "identity of the empty accumulator"
+            else:
+                zi = pow(Z, -1, P)
+                assert (X * zi % P, Y * zi % P) == S, "value"
+            if probe != NOPROBE:
+                bounds = (6, 3, 2) if kind == JAC else (6, 3, zmag, zmag)
+                for c, b in enumerate(bounds):
+                    assert mag_ok(o[151 + 10 * c:161 + 10 * c], b), f"raw coordinate {c} magnitude"
+        C.add(F, ACCUM, words, mags, p2=kind | (len(steps) << 8) | (int(start is not None) << 16) | (probe << 24), check=chk, desc=desc)
+        return len(C.recs) - 1, trace
+
+    D, A = ("d",), (lambda i, skip=False: ("a", i, skip))
+    for rnd in range(6):
+        Pn = [rp() for _ in range(4)]
+        # -- Jacobian
+        add(JAC, [A(0), D, D, D, D, D, A(1), A(2, True), D, D, A(3)], Pn, "ptj chain")
+        add(JAC, [A(0), D, D, D, D, D, A(1), D, D, D, D, D], Pn, "ptj 5-doubling windows")
+        add(JAC, [A(0, True), A(1, True), D, A(2), D, A(3)], Pn, "ptj skips on the empty accumulator, then an addition")
+        add(JAC, [A(0)], Pn, "ptj first addition: the operand itself")
+        add(JAC, [A(1), A(0, True)], Pn, "ptj first addition, then a skip")
+        add(JAC, [], Pn, "ptj empty program")
+        mid = [A(0), D, A(1), A(2, True), D, A(3)]
+        i, _ = add(JAC, mid, Pn, "ptj skip in the middle (probe before)", probe=2)
+        j, _ = add(JAC, mid, Pn, "ptj skip in the middle (probe at)", probe=3)
+        C.same_probe.append((i, j))
+        for sign in (1, -1):
+            sg = (lambda q: q) if sign == 1 else O.pt_neg
+            tag = "acc = q" if sign == 1 else "acc = -q"
+            _, tr = add(JAC, [A(0), A(1), D, A(2), A(3, True), D, A(2)], [Pn[0], sg(Pn[0]), Pn[2], Pn[3]], f"ptj {tag} at the first step")
+            assert tr[1][2] and all(t[2] for t in tr[1:])
+            k = 1 + rnd % 5
+            Q = O.pt_mul(Pn[0], 2**k)
+            _, tr = add(JAC, [A(0)] + [D] * k + [A(1), D, A(2), A(3, True), A(2), D], [Pn[0], sg(Q), Pn[2], Pn[3]],
+                        f"ptj {tag} in the middle, after {k} doublings, more points follow")
+            assert not tr[k][2] and all(t[2] for t in tr[k + 1:])
+            _, tr = add(JAC, [A(0), A(2)] + [D] * 5 + [A(1)], [Pn[0], sg(O.pt_mul(O.pt_add(Pn[0], Pn[2]), 32)), Pn[2]],
+                        f"ptj {tag} at the last step, after 5 doublings")
+            assert not tr[-2][2] and tr[-1][2]
+            _, tr = add(JAC, [A(0), D, A(1)], [sg(Pn[1]), O.pt_mul(Pn[1], 2)], f"ptj {tag} from a raw start", start=Pn[1])
+            assert tr[0][2]
+        _, tr = add(JAC, [A(0), A(1), D, A(2)], [Pn[0], endo(Pn[0]), endo(O.pt_mul(O.pt_add(Pn[0], endo(Pn[0])), 2))],
+                    "ptj operand beta x: same y, not exceptional")
+        assert not any(t[2] for t in tr)
+        add(JAC, [D, A(0), D, D, D, D, D, A(1), A(2, True), D, A(3)], Pn, "ptj raw start at the magnitude bounds", start=rp())
+        add(JAC, [A(0, True), D, A(1)], Pn, "ptj raw start, skip first", start=rp(), probe=0)
+        # -- XYZZ
+        add(XYZZ, [A(0), A(1), A(2, True), A(3), A(0), A(2)], Pn, "ptz chain")
+        add(XYZZ, [A(0, True), A(1, True), A(2), A(3)], Pn, "ptz skips on the empty accumulator, then an addition")
+        add(XYZZ, [A(0)], Pn, "ptz first addition: the operand itself")
+        add(XYZZ, [], Pn, "ptz empty program")
+        mid = [A(0), A(1), A(2, True), A(3)]
+        i, _ = add(XYZZ, mid, Pn, "ptz skip in the middle (probe before)", probe=1)
+        j, _ = add(XYZZ, mid, Pn, "ptz skip in the middle (probe at)", probe=2)
+        C.same_probe.append((i, j))
+        for sign in (1, -1):
+            sg = (lambda q: q) if sign == 1 else O.pt_neg
+            tag = "acc = q" if sign == 1 else "acc = -q"
+            _, tr = add(XYZZ, [A(0), A(1), A(2), A(3, True), A(2)], [Pn[0], sg(Pn[0]), Pn[2], Pn[3]], f"ptz {tag} at the first step")
+            assert all(t[2] for t in tr[1:])
+            _, tr = add(XYZZ, [A(0), A(1), A(2), A(3), A(0, True), A(3)], [Pn[0], Pn[1], sg(O.pt_add(Pn[0], Pn[1])), Pn[3]],
+                        f"ptz {tag} in the middle, more points follow")
+            assert not tr[1][2] and all(t[2] for t in tr[2:])
+            _, tr = add(XYZZ, [A(0), A(1), A(3), A(2)], [Pn[0], Pn[1], sg(O.pt_add(O.pt_add(Pn[0], Pn[1]), Pn[3])), Pn[3]],
+                        f"ptz {tag} at the last step")
+            assert not tr[-2][2] and tr[-1][2]
+            _, tr = add(XYZZ, [A(0), A(1)], [sg(Pn[1]), Pn[2]], f"ptz {tag} from a raw start", start=Pn[1], zmag=1 + rnd % 2)
+            assert tr[0][2]
+        _, tr = add(XYZZ, [A(0), A(1), A(2)], [Pn[0], endo(Pn[0]), Pn[2]], "ptz operand beta x: same y, not exceptional")
+        assert not any(t[2] for t in tr)
+        add(XYZZ, [A(0), A(1), A(2, True), A(3)], Pn, "ptz raw start at the magnitude bounds", start=rp(), probe=2, zmag=1 + rnd % 2)
+    # a run of XYZZ programs of ONE shape (four additions, no raw start): wavefronts of the sorted device run made of these alone execute
+    # ptz_madd with every lane active, and its wave_any(skip) branch is taken because SOME lanes skip
+    Pn = [rp() for _ in range(4)]
+    for k in range(130):
+        skips = [(k * 7 + 3 * t_) % 5 == 0 for t_ in range(4)]
+        add(XYZZ, [A(t_, skips[t_]) for t_ in range(4)], Pn, "ptz uniform wavefront, mixed skips")
+
+
+def _recode(C, rg):
+    F = "recode"
+
+    def digits_check(o, st, signed_half):
+        h = abs(signed_half)
+        assert wval(o[5 * st:5 * st + 5]) == h + OFF5, f"stream {st}: glv_recode5 words"
+        total = 0
+        for i in range(26):
+            b = (int(o[50 + 7 * st + i // 4]) >> (8 * (i % 4))) & 0xFF
+            mag, neg = b & 0x7F, b >> 7
+            assert mag <= 16, f"stream {st} window {i}: digit magnitude {mag} beyond the 16 table entries"
+            total += (-mag if neg else mag) << (5 * i)
+        assert total == signed_half, f"stream {st}: the 26 digits do not rebuild the half-scalar"
+
+    ks = _glv_scalars(random.Random(1008))
+    n0, groups = 0, []
+    while n0 < len(ks):                         # groups of 1, 2, .. 5, 1, .. scalars, each scalar in exactly one group (the last wraps round)
+        M = 1 + len(groups) % 5
+        groups.append([(n0 + j) % len(ks) for j in range(M)])
+        n0 += M
+    assert {i for grp in groups for i in grp} == set(range(len(ks))), "every scalar of the _glv list is recoded"
+    for idx in groups:
+        M = len(idx)
+        grp = [ks[i] for i in idx]
+
+        def chk(o, grp=grp):
+            for j, k in enumerate(grp):
+                r1, r2 = glv_model(k)
+                s1, s2 = (r1 if r1 < 2**129 else r1 - N), (r2 if r2 < 2**129 else r2 - N)
+                assert (s1 + s2 * LAM) % N == k
+                assert int(o[120 + 2 * j]) == int(s1 < 0) and int(o[121 + 2 * j]) == int(s2 < 0), "sign flags"
+                digits_check(o, 2 * j, s1)
+                digits_check(o, 2 * j + 1, s2)
+        C.add(F, RECODE, sum((w8(k) for k in grp), []), p2=M, p3=1, check=chk, desc=f"recode M={M} from scalars")
+    top = 2**128 - 1
+    nib = [int(c * 32, 16) for c in "078F"]
+    mixed = [int("".join(rg.choice("078F") for _ in range(32)), 16) for _ in range(24)]
+    win = [sum(v << (5 * i) for i in range(26)) & top for v in (15, 16, 17, 31, 1)]                 # every 5-bit window at one value
+    carry = [top - (1 << b) for b in (0, 4, 5, 64, 120, 124, 125, 127)] + [(1 << b) - 1 for b in (120, 124, 125, 126, 127)] + \
+            [(top - OFF5) % 2**128, (top - OFF5 + 1) % 2**128, (2**130 - 1 - OFF5) % 2**128, 2**127, 2**125, 2**125 - 16]
+    halves = [0, top] + nib + mixed + win + carry + [rg.getrandbits(128) for _ in range(20)]
+    pairs = [(0, h) for h in halves[:12]] + [(h, 0) for h in halves[:12]] + [(top, h) for h in halves[:8]] + [(h, top) for h in halves[:8]] + \
+            [(0, 0), (top, top), (0, top), (top, 0)] + [(halves[i], halves[-1 - i]) for i in range(len(halves))]
+    n0, groups = 0, []
+    while n0 < len(pairs):
+        M = 1 + len(groups) % 5
+        groups.append([(n0 + j) % len(pairs) for j in range(M)])
+        n0 += M
+    assert {i for grp in groups for i in grp} == set(range(len(pairs))), "every pair of half-scalars is recoded"
+    for idx in groups:
+        M = len(idx)
+        grp = [pairs[i] for i in idx]
+        signs = [(i & 1, (i >> 1) & 1) for i in idx]
+        words = []
+        for (h1, h2), (n1, n2) in zip(grp, signs):
+            for h in (h1, h2):
+                words += [((h + OFF4) >> (32 * i)) & 0xFFFFFFFF for i in range(5)]
+            words += [n1, n2]
+
+        def chk(o, grp=grp, signs=signs):
+            for j, ((h1, h2), (n1, n2)) in enumerate(zip(grp, signs)):
+                assert int(o[120 + 2 * j]) == n1 and int(o[121 + 2 * j]) == n2, "sign flags"
+                digits_check(o, 2 * j, -h1 if n1 else h1)
+                digits_check(o, 2 * j + 1, -h2 if n2 else h2)
+        C.add(F, RECODE, words, p2=M, p3=0, check=chk, desc=f"recode M={M} from half-scalars")
+
+
+def split_begin(parts, part):
+    """The test's own copy of straus_core.h's split_begin (the records name a cut and the dispatcher calls the C one; out[192] must
+    agree with this one): the first window of part `part` of a 26-window stream cut in `parts`.  Production cuts a stream in 2 or 4
+    (BPPP_SPLIT_PARTS_MAX); any other count falls into the 4-part branch, with 26 for every part past the fourth."""
+    if parts == 1:
+        return 0 if part == 0 else 26
+    if parts == 2:
+        return (0, 13, 26)[min(part, 2)]
+    return (0, 7, 14, 20, 26)[min(part, 4)]
+
+
+def _table(C, rg):
+    F = "table"
+    # 8 parts is no production cut: it reuses the 4-part branch and adds 130 doublings (part >= 4), a table no caller builds but a
+    # well-formed input to affine_table_one
+    cuts = [(1, 0), (2, 0), (2, 1), (4, 0), (4, 1), (4, 2), (4, 3), (8, 0), (8, 1), (8, 2), (8, 3), (8, 4), (8, 7)]
+    assert {5 * split_begin(*c) for c in cuts} == {0, 35, 65, 70, 100, 130}
+    for name, pnt in (("G", O.G), ("random point", O.pt_mul(O.G, rg.randrange(1, N))), ("identity sentinel", None)):
+        for parts, part in cuts:
+            pre = 5 * split_begin(parts, part)
+            base = None if pnt is None else O.pt_mul(pnt, 2**pre)
+            for first in (1, 9):
+                def chk(o, base=base, first=first, pre=pre):
+                    assert int(o[192]) == pre, "doublings done first"
+                    assert int(o[193]) == 0, "aff_ld returns the stored words"
+                    for k in range(8):
+                        x, y, bx = (wval(o[24 * k + 8 * c:24 * k + 8 * c + 8]) for c in range(3))
+                        if base is None:
+                            assert (x, y, bx) == (0, 0, 0), f"entry {first + k} of the sentinel's table is the sentinel"
+                            continue
+                        e = O.pt_mul(base, first + k)
+                        assert (x, y) == e, f"entry {first + k}"
+                        assert bx == BETA * x % P, f"entry {first + k}: beta x"
+                        if k == (first + pre) % 8:
+                            assert (bx, y) == O.pt_mul(e, LAM), f"entry {first + k}: the beta-frame twin is lambda times the entry"
+                xy = limbs(pnt[0]) + limbs(pnt[1]) if pnt else [0] * 20
+                C.add(F, TABLE, xy, (1, 1), p2=parts | (part << 8), p3=first, check=chk,
+                      desc=f"affine_table_one {name}, part {part} of {parts} ({pre} doublings), entries {first}..{first + 7}")
 
 
 def _draw(C, rg):
@@ -641,7 +933,8 @@ def cases():
     global _CASES
     if _CASES is None:
         C = Cases()
-        for i, gen in enumerate((_fe_products, _fe_linear, _fe_normalize, _fn, _fn_wrap, _inversion, _bytes, _group, _glv, _draw)):
+        for i, gen in enumerate((_fe_products, _fe_linear, _fe_normalize, _fn, _fn_wrap, _inversion, _bytes, _group, _glv, _draw,
+                                 _accum, _recode, _table)):
             gen(C, random.Random(1000 + i))
         _CASES = C
     return _CASES
@@ -736,6 +1029,316 @@ def test_same_bits_everywhere(backend):
         diff = np.nonzero((out != _SORTED[backend]).any(axis=1))[0]
         assert len(diff) == 0, f"shuffled vs sorted device runs: {len(diff)} records differ, first: " + \
             "; ".join(f"#{i} {C.meta[i][2]}" for i in diff[:10])
+
+
+def test_skipped_step_keeps_the_raw_limbs(backend):
+    """A skipped addition in the middle of an accumulator program leaves every raw limb as it was: the same program probed before and
+    at the skipped step."""
+    out = outputs(backend)
+    C = cases()
+    assert len(C.same_probe) >= 12
+    for i, j in C.same_probe:
+        assert int(out[i, OUT_W - 1]) == 0 and int(out[j, OUT_W - 1]) == 0
+        assert out[i, 151:191].any(), C.meta[i][2]
+        assert (out[i, 151:191] == out[j, 151:191]).all(), f"#{i} / #{j} {C.meta[j][2]}"
+
+
+def test_dispatcher_rejects_out_of_range_records(backend):
+    """The new ops keep the dispatcher's guards: a step count, step code, probe index, recoding size or table part out of range is
+    answered with ST_BAD_PARAM (2) and no evaluation."""
+    why = PB.unavailable(backend)
+    if why:
+        pytest.skip(f"{backend} backend skipped: {why}")
+    xy = limbs(O.GX) + limbs(O.GY)
+    bad = [(ACCUM, JAC | (13 << 8) | (NOPROBE << 24), 0, []),              # 13 steps
+           (ACCUM, 2 | (1 << 8) | (NOPROBE << 24), 0, [1 << 4]),            # no such accumulator
+           (ACCUM, JAC | (1 << 8) | (1 << 24), 0, [1 << 4]),                # probe past the program
+           (ACCUM, JAC | (1 << 8) | (NOPROBE << 24), 0, [2 << 4]),          # no such step
+           (ACCUM, XYZZ | (1 << 8) | (NOPROBE << 24), 0, [0]),              # the XYZZ accumulator has no doubling
+           (RECODE, 0, 1, []), (RECODE, 6, 1, []), (RECODE, 2, 2, []),
+           (TABLE, 3, 1, xy), (TABLE, 2 | (2 << 8), 1, xy), (TABLE, 1, 5, xy)]
+    recs = np.zeros((len(bad), IN_W), np.uint32)
+    for r, (op, p2, p3, words) in zip(recs, bad):
+        r[0], r[2], r[3] = op, p2, p3
+        r[4:4 + len(words)] = words
+    out = _run(PB.load(backend), recs, bytes(64))
+    assert out[:, OUT_W - 1].tolist() == [2] * len(bad)
+    assert not out[:, :OUT_W - 1].any()
+
+
+def test_sorted_run_mixes_skips_in_a_wavefront():
+    """The record set itself: in the device run sorted by op code, some wavefront is made of XYZZ programs of one shape alone with
+    skipping and adding lanes side by side (ptz_madd's wave_any(skip) branch under a full exec mask), and some wavefront holds such
+    lanes next to programs of another shape (the same branch under a partial one)."""
+    C = cases()
+    recs = np.array(C.recs, dtype=np.uint32)
+    order = np.argsort(recs[:, 0], kind="stable")
+    full = partial = False
+    for w0 in range(0, len(order), 64):
+        wave = [recs[i] for i in order[w0:w0 + 64]]
+        zz = [r for r in wave if r[0] == ACCUM and (r[2] & 0xFF) == XYZZ]
+        if not zz:
+            continue
+        skip_at = [{s_ for s_ in range((int(r[2]) >> 8) & 0xFF) if (int(r[4 + s_ // 4]) >> (8 * (s_ % 4))) & 4} for r in zz]
+        mixed = any(any(s_ in a for a in skip_at) and not all(s_ in a for a in skip_at) for s_ in range(12))
+        one_shape = len(wave) == 64 and len(zz) == 64 and len({int(r[2]) for r in zz}) == 1
+        full |= mixed and one_shape
+        partial |= mixed and len({(int(r[0]), int(r[2])) for r in wave}) > 1
+    assert full and partial
+
+
+# ---------------------------------------------------------------- the variable-base sums on production-built tables, fallback included
+SUM_AFFINE, SUM_FAST_COMPLETE, SUM_SPLIT_LANES, SUM_COMPLETE, SUM_GROUP, SUM_SPLIT_GROUP = range(6)
+# (form, M, G, parts): the one-lane forms (host twins) and every lane-group form the verifiers instantiate (verify_core.h,
+# recip_core.h, wnla_core.h, prove_core.h: straus_affine_g4<2 | 5, 2 | 4>, straus_affine_split<2, 8, 2>, <2, 16, 4>, <5, 32, 2>, <5, 64, 4>)
+SUM_ONE_LANE = [(SUM_AFFINE, m, 1, 0) for m in (1, 2, 3, 4, 5)] + \
+               [(f, m, 1, 0) for f in (SUM_FAST_COMPLETE, SUM_COMPLETE) for m in (2, 5)] + \
+               [(SUM_SPLIT_LANES, m, 1, parts) for m in (2, 5) for parts in (2, 4)]
+SUM_GROUPS = [(SUM_GROUP, m, g, 0) for m in (2, 5) for g in (2, 4)] + \
+             [(SUM_SPLIT_GROUP, 2, 8, 2), (SUM_SPLIT_GROUP, 2, 16, 4), (SUM_SPLIT_GROUP, 5, 32, 2), (SUM_SPLIT_GROUP, 5, 64, 4)]
+
+
+def sum_cfg(cfg):
+    form, m, g, parts = cfg
+    return form | (m << 8) | (g << 16) | (parts << 24)
+
+
+def signed_halves(k):
+    r1, r2 = glv_model(k)
+    return (r1 if r1 < 2**129 else r1 - N), (r2 if r2 < 2**129 else r2 - N)
+
+
+def stream_digits(h):
+    """The 26 signed 5-bit digits of the signed half-scalar h, lowest window first."""
+    w = abs(h) + OFF5
+    return [(((w >> (5 * i)) & 31) - 16) * (-1 if h < 0 else 1) for i in range(26)]
+
+
+def lane_meets_exception(streams, windows):
+    """One lane of a sum as group elements: `streams` = [(point, digits)], walked from the last of `windows` down with 5 doublings
+    between windows, skipping zero digits and identity points.  True when some addition finds acc = +-q (the incomplete law's exception)."""
+    acc = None
+    empty = True
+    for n_, i in enumerate(reversed(windows)):
+        if n_ and not empty:
+            acc = O.pt_mul(acc, 32)
+        for pnt, dg in streams:
+            if pnt is None or dg[i] == 0:
+                continue
+            q = O.pt_mul(pnt, abs(dg[i]))
+            q = O.pt_neg(q) if dg[i] < 0 else q
+            if empty:
+                acc, empty = q, False
+            elif acc is None or acc[0] == q[0]:
+                return True
+            else:
+                acc = O.pt_add(acc, q)
+    return False
+
+
+def sum_meets_exception(cfg, pts, ks):
+    """Whether the fast form of configuration cfg meets an exceptional addition on some lane, for M points / scalars."""
+    form, m, g, parts = cfg
+    streams = []
+    for pnt, k in zip(pts, ks):
+        h1, h2 = signed_halves(k)
+        streams += [(pnt, stream_digits(h1)), (endo(pnt), stream_digits(h2))]
+    if form in (SUM_AFFINE, SUM_FAST_COMPLETE):
+        return lane_meets_exception(streams, range(26))
+    if form == SUM_GROUP:
+        return any(lane_meets_exception(streams[q::g], range(26)) for q in range(g))
+    if form in (SUM_SPLIT_LANES, SUM_SPLIT_GROUP):
+        cut = lambda pnt, h: None if pnt is None else O.pt_mul(pnt, 2**(5 * split_begin(parts, h)))
+        return any(lane_meets_exception([(cut(pnt, h), dg[split_begin(parts, h):])], range(split_begin(parts, h + 1) - split_begin(parts, h)))
+                   for h in range(parts) for pnt, dg in streams)
+    return False
+
+
+_SUM_MEETS = {}
+
+
+def sum_meets(cfg, i):
+    """sum_meets_exception for record i of configuration cfg (computed once for all builds)."""
+    if (cfg, i) not in _SUM_MEETS:
+        _, pts, ks, _ = sum_records(cfg)[0][i]
+        _SUM_MEETS[(cfg, i)] = sum_meets_exception(cfg, pts, ks)
+    return _SUM_MEETS[(cfg, i)]
+
+
+def sum_inputs(m):
+    """(description, points, scalars, certain) for sums of m points (m <= 4 real ones; a fifth slot of the five-point forms holds the
+    identity with scalar 0).  certain: the one-lane fast form must report an exception -- equal or opposite points with equal scalars
+    in [2^120, 2^127) (or 1), whose lambda halves are zero, beside scalars below 2^60 (or 0), whose digits at k's first non-zero window
+    are zero: the accumulator holds d P alone when the second copy's d P (or -d P) arrives."""
+    rg = random.Random(4242 + m)
+    real = min(m, 4)
+    rp = lambda: O.pt_mul(O.G, rg.randrange(1, N))
+    rs = lambda: rg.randrange(1, N)
+    small = lambda: rg.randrange(2**120, 2**127)
+    pad = lambda pts, ks: (pts + [None] * (m - len(pts)), ks + [0] * (m - len(ks)))
+    out = []
+
+    def add(desc, pts, ks, certain=False):
+        pts, ks = pad(list(pts), list(ks))
+        out.append((desc, pts, ks, certain))
+
+    for _ in range(6):
+        add("distinct points and scalars", [rp() for _ in range(real)], [rs() for _ in range(real)])
+    for a in (0, 1, N - 1, LAM):
+        add(f"scalar {a if a < 2 else 'n - 1' if a == N - 1 else 'lambda'} everywhere", [rp() for _ in range(real)], [a] * real)
+        add("scalars 0, 1, n - 1, lambda", [rp() for _ in range(real)], [(0, 1, N - 1, LAM)[(j + a) % 4] for j in range(real)])
+    add("all points the identity", [None] * real, [rs() for _ in range(real)])
+    add("all scalars 0 and all points the identity", [None] * real, [0] * real)
+    for j in range(real):
+        pts = [rp() for _ in range(real)]
+        pts[j] = None
+        add(f"identity in slot {j} among real points", pts, [rs() for _ in range(real)])
+    if real >= 2:
+        for i in range(real):
+            for j in range(i + 1, real):
+                for sign in (1, -1):
+                    for k, certain in ((small(), True), (rs(), False), (1, True), (N - 1, False), (LAM, False)):
+                        # certain: the other points' scalars end below the window where k begins (0 beside k = 1)
+                        pts, ks = [rp() for _ in range(real)], [(rg.randrange(2**60) if k > 1 else 0) if certain else rs() for _ in range(real)]
+                        pts[j] = pts[i] if sign == 1 else O.pt_neg(pts[i])
+                        ks[i] = ks[j] = k
+                        add(f"slots {i} and {j}: {'the same point' if sign == 1 else 'P and -P'}, the same scalar", pts, ks, certain)
+    if real >= 3:
+        for n_same in range(3, real + 1):
+            for k, certain in ((small(), True), (rs(), False)):
+                pts, ks = [rp() for _ in range(real)], [rg.randrange(2**60) if certain else rs() for _ in range(real)]
+                for j in range(n_same):
+                    pts[j], ks[j] = pts[0], k
+                add(f"the same point and scalar in {n_same} slots", pts, ks, certain)
+    return out
+
+
+_SUM_IN, _SUM_OUT = {}, {}
+
+
+def sum_records(cfg):
+    m = cfg[1]
+    if m not in _SUM_IN:
+        _SUM_IN[m] = sum_inputs(m)
+    recs = np.zeros((len(_SUM_IN[m]), SUM_IN_W), np.uint32)
+    for r, (_, pts, ks, _) in zip(recs, _SUM_IN[m]):
+        r[0] = sum_cfg(cfg)
+        for j, (pnt, k) in enumerate(zip(pts, ks)):
+            if pnt is not None:
+                r[4 + 16 * j:4 + 16 * j + 16] = w8(pnt[0]) + w8(pnt[1])
+            r[84 + 8 * j:84 + 8 * j + 8] = w8(k)
+    return _SUM_IN[m], recs
+
+
+def sum_outputs(backend, cfg):
+    if (backend, cfg) not in _SUM_OUT:
+        why = PB.unavailable(backend)
+        if why:
+            pytest.skip(f"{backend} backend skipped: {why}")
+        L = PB.load(backend)
+        assert (L.prims_sum_words(0), L.prims_sum_words(1)) == (SUM_IN_W, SUM_OUT_W)
+        _, recs = sum_records(cfg)
+        out = np.zeros((len(recs), SUM_OUT_W), np.uint32)
+        rc = L.run_sums(sum_cfg(cfg), recs.ctypes.data, out.ctypes.data, len(recs))
+        assert rc == 0, f"run_sums returned {rc}"
+        _SUM_OUT[(backend, cfg)] = out
+    return _SUM_OUT[(backend, cfg)]
+
+
+_SUM_EXPECT = {}
+
+
+def sum_expected(m):
+    if m not in _SUM_EXPECT:
+        exp = []
+        for _, pts, ks, _ in sum_records((SUM_AFFINE, m, 1, 0))[0]:
+            total = None
+            for pnt, k in zip(pts, ks):
+                total = O.pt_add(total, O.pt_mul(pnt, k))
+            exp.append(total)
+        _SUM_EXPECT[m] = exp
+    return _SUM_EXPECT[m]
+
+
+def check_sums(backend, cfg):
+    form, m, g, parts = cfg
+    inputs, _ = sum_records(cfg)
+    out = sum_outputs(backend, cfg)
+    bad, fell_back = [], 0
+    for i, ((desc, pts, ks, certain), exp) in enumerate(zip(inputs, sum_expected(m))):
+        o = out[i]
+        try:
+            assert int(o[SUM_OUT_W - 1]) == 0, f"status {int(o[SUM_OUT_W - 1])}"
+            for c, b in enumerate((5, 2, 2)):
+                assert mag_ok(o[10 * c:10 * c + 10], b), f"coordinate {c} magnitude"
+            ax, ay = o[30:40], o[40:50]
+            assert reduced(ax) and reduced(ay), "pt_to_affine bound"
+            assert (val(ax) % P, val(ay) % P) == ((0, 0) if exp is None else exp), "sum != sum_i k_i P_i of the oracle"
+            assert int(o[72]) == 0, "lanes of the group disagree on the total"
+            if form in (SUM_GROUP, SUM_SPLIT_GROUP):
+                assert int(o[73]) == int(sum_meets(cfg, i)), \
+                    f"the device finds {'an' if int(o[73]) else 'no'} exceptional addition in the group, the group-element model the opposite"
+            if form not in (SUM_FAST_COMPLETE, SUM_SPLIT_LANES):
+                assert int(o[50]) == 2, "flag of a form that returns none"
+        except AssertionError as e:
+            bad.append(f"#{i} {desc}: {e}")
+        if form in (SUM_FAST_COMPLETE, SUM_SPLIT_LANES):
+            meets = sum_meets(cfg, i)
+            fell_back += meets
+            if form == SUM_FAST_COMPLETE and certain and not meets:
+                bad.append(f"#{i} {desc}: constructed to meet an exceptional addition, the model finds none")
+            if int(o[50]) != int(not meets):
+                bad.append(f"#{i} {desc}: fast form returned {int(o[50])}, the group-element model expects {int(not meets)}")
+    assert not bad, f"{len(bad)} of {len(inputs)} sums wrong for form {form} M={m} G={g} parts={parts} on {backend}:\n" + "\n".join(bad[:20])
+    return fell_back
+
+
+@pytest.mark.parametrize("cfg", SUM_ONE_LANE, ids=lambda c: "form%d-M%d-parts%d" % (c[0], c[1], c[3]))
+def test_sums_one_lane(backend, cfg):
+    """straus_affine, straus_affine_fast + straus_affine_complete, straus_affine_complete and the lanes of straus_split_lane on tables
+    built by affine_tables_build / affine_table_one: every sum equals sum_i k_i P_i of the oracle, coincident and identity points
+    included, and the fast forms' flag is the one a group-element model of the same lane predicts (false, with certainty, for equal
+    or opposite points with equal scalars below 2^127)."""
+    fell_back = check_sums(backend, cfg)
+    if cfg[0] == SUM_FAST_COMPLETE:
+        certain = sum(1 for rec in sum_records(cfg)[0] if rec[3])
+        assert certain >= 4 and fell_back >= certain, "the records built to take the fallback take it"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg", SUM_GROUPS, ids=lambda c: "form%d-M%d-G%d-parts%d" % c)
+def test_sums_lane_groups(cfg):
+    """straus_affine_g4<M, G> and straus_affine_split<M, G, PARTS> on their real lane groups, 64 / G independent sums per wavefront,
+    exceptional groups next to ordinary ones: every sum equals the oracle's, on every lane of the group.  The record set holds sums
+    whose streams meet in ONE lane (an exception, and the group-wide re-do) and sums whose streams meet across lanes or parts (the
+    complete additions of the shuffle tree).  Which is which follows from the group-element model, and the kernel reports for every
+    sum whether a lane of its group met an exceptional addition (recomputed beside the function under test: straus_affine_fast over
+    the lane's own streams, or straus_split_lane); the two must agree record by record, so the model cannot drift from the device.
+
+    The `if (bad)` block of straus_affine_split is NOT covered by result: a lane of a split sum walks one stream over one table, its
+    accumulator is 32 A Q against an entry d Q with |d| <= 16, and in a group of prime order these never meet.  No well-formed input
+    reaches that block; the test asserts that no record does."""
+    check_sums("gfx950", cfg)
+    if cfg[0] == SUM_GROUP:
+        # lane q of a group of G holds the streams q, q + G, ...: two points' streams share a lane when 2 M > G, and with G = 4 (two
+        # streams of a point, then the next point's) some pairs of points never do
+        inputs, _ = sum_records(cfg)
+        meets = [sum_meets(cfg, i) for i, rec in enumerate(inputs) if rec[3]]
+        assert meets.count(True) >= (4 if 2 * cfg[1] > cfg[2] else 0), "sums whose coincident streams share a lane"
+        assert meets.count(False) >= (4 if cfg[2] == 4 else 0), "sums whose coincident streams lie in different lanes"
+    else:
+        assert not any(sum_meets(cfg, i) for i in range(len(sum_records(cfg)[0]))), "a split lane never meets an exception"
+
+
+def test_sums_same_bits_everywhere(backend):
+    """The one-lane sums give identical raw words on every build."""
+    others = [b for b in ("gcc", "clang") if b != backend and PB.unavailable(b) is None]
+    if not others:
+        pytest.skip("no second build to compare with")
+    for cfg in SUM_ONE_LANE:
+        for other in others:
+            diff = np.nonzero((sum_outputs(backend, cfg) != sum_outputs(other, cfg)).any(axis=1))[0]
+            assert len(diff) == 0, f"{cfg} {backend} vs {other}: records {list(diff[:10])} differ"
 
 
 def test_limb_helpers():

@@ -123,3 +123,20 @@ def test_generic_prove_is_byte_identical_to_the_oracle(ng, nh, musq):
     assert not st.any()
     assert (pr == case["proof_r"]).all() and (px == case["proof_x"]).all()
     assert (pl == case["proof_l"]).all() and (pn == case["proof_n"]).all()
+
+
+def test_accepted_instances_with_coincident_points():
+    """wnla_cases.make_coincident on the host build of the device code: valid instances whose commitment and round points are the
+    identity, or whose first round has X = R, are accepted; one flipped bit in a final scalar rejects each of them."""
+    L = load()
+    case = wnla_cases.make_coincident(base=10, copies=1)
+    B = case["commitments"].shape[0]
+    tab, W = _table(L, case)
+    _, acc, st = _run(L, case, tab, W, commit=False)
+    assert acc.tolist() == [1] * B and not st.any()
+    pl = case["proof_l"].copy(); pl[:, 0, 31] ^= 1
+    _, acc, st = _run(L, case, tab, W, commit=False, proof_l=pl)
+    assert acc.tolist() == [0] * B and not st.any()
+    pn = case["proof_n"].copy(); pn[:, -1, 30] ^= 0x20
+    _, acc, st = _run(L, case, tab, W, commit=False, proof_n=pn)
+    assert acc.tolist() == [0] * B and not st.any()
