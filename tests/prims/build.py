@@ -5,7 +5,8 @@
   libbppp_prims_hip.so    hipcc gfx950 build (prims_device.hip) with the product's BASE_FLAGS: the code the GPU runs
 
 Each library exports the dispatcher (prims_run_host / prims_run_device) and the variable-base sums (prims_run_sums_host: the one-lane
-forms; prims_run_sums_device: those and the lane-group forms).  A library is rebuilt when it is missing or older than any bp_pp_amd/csrc/*.h or tests/prims/* source."""
+forms; prims_run_sums_device: those and the lane-group forms) and the transcript primitives (prims_run_transcript_host: the register
+sponge; prims_run_transcript_device: that and the LDS sponge, in the uniform and the grouped launch layout).  A library is rebuilt when it is missing or older than any bp_pp_amd/csrc/*.h or tests/prims/* source."""
 import ctypes as C
 import glob
 import os
@@ -95,6 +96,12 @@ def load(backend):
     run_sums.argtypes = [C.c_uint32, vp, vp, sz]
     run_sums.restype = C.c_int
     L.run_sums = run_sums
+    L.prims_transcript_words.argtypes = [C.c_int]
+    L.prims_transcript_words.restype = C.c_int
+    run_tr = L.prims_run_transcript_device if backend == "gfx950" else L.prims_run_transcript_host
+    run_tr.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz]
+    run_tr.restype = C.c_int
+    L.run_transcript = run_tr
     if backend != "gfx950":
         L.prims_is_clang.restype = C.c_int
     return L

@@ -10,6 +10,7 @@
 // so the FE_CHECK asserts of field.h guard the contract of every call.  The device build carries no magnitude.
 //
 // The variable-base sums (straus_core.h) have a second record format and entry points of their own, further down: SumForm.
+// The transcript primitives (merlin.h) have a third, with a program per launch, at the end: TrStep.
 #pragma once
 #include "../../bp_pp_amd/csrc/field.h"
 #include "../../bp_pp_amd/csrc/modinv.h"
@@ -644,6 +645,264 @@ HD void prim_eval(u32 op, const u32* in, u32* out, const uint8_t* bytes, size_t 
         st = ST_BAD_OP;
     }
     out[PRIM_OUT_WORDS - 1] = st;
+}
+
+// ================================================================ the TRANSCRIPT primitives (merlin.h, verify_ws.h: app_point, the 203-byte state)
+// A third record format and entry points of its own: one launch runs ONE program of at most TR_MAX_STEPS steps over n records, because the
+// sponge's byte position has to be uniform over a wavefront (merlin.h: st_uniform) and the launch layout is therefore part of the test.
+//   program   TR_PROG_WORDS words: the number of steps, then (kind, label id, parameter) per step
+//   states    n x 203 bytes, the layout of strobe_from_bytes / strobe_to_bytes
+//   record    TR_IN_WORDS words: in[0 .. 64) 256 message bytes | in[64 .. 144) four affine points, x then y as 10 canonical limbs each
+//             (all zero: the identity) | in[144 .. 148) two u64 (low word first) | in[148 .. 150) the u64 of TS_ROTL64 | in[150] the word of
+//             TS_ABSORB_CHUNK
+//   output    TR_OUT_WORDS words: out[0 .. 51) the 203 state bytes after the program (strobe_to_bytes; byte 202 = the flags of the last
+//             operation begun, the input's where the program begins none) | out[51] status | out[52 ..) what the steps produced, one after
+//             the other: squeezed bytes packed little-endian into whole words, a challenge as its 8 words and the canonical flag
+// A state strobe_from_bytes refuses is answered with TR_BAD_STATE and not evaluated; a program that breaks a bound with ST_BAD_PARAM.
+#define TR_MAX_STEPS 8
+#define TR_PROG_WORDS (1 + 3 * TR_MAX_STEPS)
+#define TR_IN_WORDS 152
+#define TR_PROD_WORDS 128
+#define TR_OUT_WORDS (52 + TR_PROD_WORDS)
+#define TR_MSG_BYTES 256
+enum TrStep : u32 {
+    // raw steps
+    TS_KECCAK_F = 1,       // keccak_f1600 on the 25 state words
+    TS_KECCAK_RC,          // keccak_rc(par), par < 24: 2 words
+    TS_ROTL64,             // rotl64(v, par), 1 <= par <= 63: 2 words
+    TS_ABSORB_CHUNK,       // strobe_absorb_chunk(word, par), 1 <= par <= 4
+    TS_RUN_F,              // strobe_run_f
+    TS_SQUEEZE,            // strobe_squeeze of par <= 200 bytes
+    TS_META_AD,            // strobe_meta_ad / strobe_ad of the first (par & 0xFFFF) <= 256 message bytes, `more` = par >> 16 (register sponge)
+    TS_AD,
+    TS_PRF,                // strobe_prf of par <= 200 bytes (register sponge)
+    // transcript steps (label id: TR_LABELS_*)
+    TS_APPEND_MEM = 16,    // t_append of the first par <= 200 message bytes (register sponge)
+    TS_APPEND_WORDS,       // t_append_words<NW = 9> of the first 9 message words, par <= 36 bytes
+    TS_APPEND_U64,         // t_append_u64 of u64 number par < 2
+    TS_APP_POINT,          // app_point of point number par < 4
+    TS_GET_CHALLENGE,      // t_get_challenge: 9 words
+    TS_CHALLENGE_BYTES,    // t_challenge_bytes of par <= 200 bytes; LDS sponge: the same challenge header (t_op_absorb), then strobe_squeeze
+};
+enum TrForm : u32 { TR_REGS = 0, TR_LDS = 1 };                     // strobe | strobe_lds (device only)
+enum TrLayout : u32 { TR_UNIFORM = 0, TR_GROUPED = 1 };            // device: body called directly | inside for_each_position_group
+enum TrStatus : u32 { TR_BAD_STATE = 4, TR_BAD_LAYOUT = 5 };       // beside Status
+// Labels are compile-time arrays: a fixed list, by id.  ANY: every transcript step takes them (the product's short labels and test labels of
+// length 1, 2, 3, 5, 6, so that L mod 4 takes every value); POINT: app_point only; CHAL: t_get_challenge only (the rest of the labels that the
+// protocols' longest sequences use).
+#define TR_LABELS_ANY(X) X(0, "dom-sep") X(1, "l.sz") X(2, "n.sz") X(3, "wnla_challenge") X(4, "circuit_rho") X(5, "reciprocal_challenge") \
+    X(6, "a") X(7, "bc") X(8, "def") X(9, "ghijk") X(10, "lmnopq")
+#define TR_LABELS_POINT(X) X(11, "wnla_com") X(12, "wnla_x") X(13, "wnla_r") X(14, "reciprocal_commitment") X(15, "commitment_cl") \
+    X(16, "commitment_cr") X(17, "commitment_co") X(18, "commitment_v") X(19, "commitment_cs")
+#define TR_LABELS_CHAL(X) X(20, "circuit_lambda") X(21, "circuit_beta") X(22, "circuit_delta") X(23, "circuit_tau")
+#define TR_N_ANY 11
+#define TR_N_POINT 20
+#define TR_N_LABELS 24
+// calls f(label) with label number `lab` as the literal itself; CLS bit 0: the POINT labels too, bit 1: the CHAL labels too
+template <int CLS, typename F>
+HD void tr_with_label(u32 lab, F&& f) {
+    switch (lab) {
+#define TR_X(i, s) case i: f(s); break;
+        TR_LABELS_ANY(TR_X)
+#undef TR_X
+    default:
+        if constexpr ((CLS & 1) != 0) {
+            switch (lab) {
+#define TR_X(i, s) case i: f(s); break;
+                TR_LABELS_POINT(TR_X)
+#undef TR_X
+            default: break;
+            }
+        }
+        if constexpr ((CLS & 2) != 0) {
+            switch (lab) {
+#define TR_X(i, s) case i: f(s); break;
+                TR_LABELS_CHAL(TR_X)
+#undef TR_X
+            default: break;
+            }
+        }
+    }
+}
+HD bool tr_label_ok(u32 kind, u32 lab) {
+    if (lab < TR_N_ANY) return true;
+    if (lab < TR_N_POINT) return kind == TS_APP_POINT;
+    return lab < TR_N_LABELS && kind == TS_GET_CHALLENGE;
+}
+// words a step appends to the record's products
+HD u32 tr_step_words(u32 kind, u32 par) {
+    switch (kind) {
+    case TS_KECCAK_RC: case TS_ROTL64: return 2;
+    case TS_SQUEEZE: case TS_PRF: case TS_CHALLENGE_BYTES: return (par + 3) / 4;
+    case TS_GET_CHALLENGE: return 9;
+    default: return 0;
+    }
+}
+// the bounds of a program, for the sponge form that is to run it
+HD bool tr_prog_ok(const u32* prog, u32 form) {
+    const u32 ns = prog[0];
+    if (ns > TR_MAX_STEPS || form > TR_LDS) return false;
+    u32 words = 0;
+#pragma nounroll
+    for (u32 s = 0; s < ns; s++) {
+        const u32 kind = prog[1 + 3 * s], lab = prog[2 + 3 * s], par = prog[3 + 3 * s];
+        bool ok;
+        switch (kind) {
+        case TS_KECCAK_F: case TS_RUN_F: ok = par == 0; break;
+        case TS_KECCAK_RC: ok = par < 24; break;
+        case TS_ROTL64: ok = par >= 1 && par <= 63; break;
+        case TS_ABSORB_CHUNK: ok = par >= 1 && par <= 4; break;
+        case TS_SQUEEZE: ok = par <= 200; break;
+        case TS_META_AD: case TS_AD: ok = form == TR_REGS && (par & 0xFFFFu) <= TR_MSG_BYTES && (par >> 16) <= 1; break;
+        case TS_PRF: ok = form == TR_REGS && par <= 200; break;
+        case TS_APPEND_MEM: ok = form == TR_REGS && par <= 200; break;
+        case TS_APPEND_WORDS: ok = par <= 36; break;
+        case TS_APPEND_U64: ok = par < 2; break;
+        case TS_APP_POINT: ok = par < 4; break;
+        case TS_GET_CHALLENGE: ok = par == 0; break;
+        case TS_CHALLENGE_BYTES: ok = par <= 200; break;
+        default: ok = false;
+        }
+        if (kind < TS_APPEND_MEM) ok = ok && lab == 0;
+        else ok = ok && tr_label_ok(kind, lab);
+        if (!ok) return false;
+        words += tr_step_words(kind, par);
+    }
+    return words <= TR_PROD_WORDS;
+}
+HD u64 tr_rotl64(u64 v, u32 r) {     // rotl64 takes a compile-time amount: one call per amount
+    u64 o = v;
+    switch (r) {
+#define TR_R(i) case i: o = rotl64(v, i); break;
+#define TR_R8(b) TR_R(b) TR_R(b + 1) TR_R(b + 2) TR_R(b + 3) TR_R(b + 4) TR_R(b + 5) TR_R(b + 6) TR_R(b + 7)
+        TR_R(1) TR_R(2) TR_R(3) TR_R(4) TR_R(5) TR_R(6) TR_R(7)
+        TR_R8(8) TR_R8(16) TR_R8(24) TR_R8(32) TR_R8(40) TR_R8(48) TR_R8(56)
+#undef TR_R8
+#undef TR_R
+    default: break;
+    }
+    return o;
+}
+HD void tr_keccak_f(strobe& s) { keccak_f1600(s.st); }
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void tr_keccak_f(strobe_lds& s) { keccak_f1600_lds(s.col); }
+#endif
+// the steps only the register sponge has (memory operands, strobe& signatures)
+HD void tr_step_regs(strobe& t, u32 kind, u32 lab, u32 par, const uint8_t* msg, u32* prod, u32& flags) {
+    uint8_t buf[200];
+    if (kind == TS_META_AD) { strobe_meta_ad(t, msg, par & 0xFFFFu, (par >> 16) != 0); if (!(par >> 16)) flags = 16 | 2; }
+    else if (kind == TS_AD) { strobe_ad(t, msg, par & 0xFFFFu, (par >> 16) != 0); if (!(par >> 16)) flags = 2; }
+    else if (kind == TS_PRF) {
+#pragma nounroll
+        for (u32 i = 0; i < 200; i++) buf[i] = 0;
+        strobe_prf(t, buf, par);
+        st_bytes(prod, buf, (int)par);
+        flags = 1 | 2 | 4;
+    } else if (kind == TS_APPEND_MEM) {
+        tr_with_label<0>(lab, [&](const auto& label) { t_append(t, label, msg, par); });
+        flags = 2;
+    } else {     // TS_CHALLENGE_BYTES
+#pragma nounroll
+        for (u32 i = 0; i < 200; i++) buf[i] = 0;
+        tr_with_label<0>(lab, [&](const auto& label) { t_challenge_bytes(t, label, buf, par); });
+        st_bytes(prod, buf, (int)par);
+        flags = 1 | 2 | 4;
+    }
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void tr_step_regs(strobe_lds& t, u32 kind, u32 lab, u32 par, const uint8_t*, u32* prod, u32& flags) {
+    if (kind != TS_CHALLENGE_BYTES) return;     // tr_prog_ok lets nothing else through
+    uint8_t buf[200];
+#pragma nounroll
+    for (u32 i = 0; i < 200; i++) buf[i] = 0;
+    tr_with_label<0>(lab, [&](const auto& label) { t_op_absorb(t, label, par, 1, [](u32) -> u32 { return 0; }); });
+    strobe_squeeze(t, buf, par);
+    st_bytes(prod, buf, (int)par);
+    flags = 1 | 2 | 4;
+}
+#endif
+// One step on either sponge form.  `prod` is where the step's products go.
+template <typename S>
+HD void tr_step(S& t, u32 kind, u32 lab, u32 par, const u32* rec, u32* prod, u32& flags) {
+    switch (kind) {
+    case TS_KECCAK_F: tr_keccak_f(t); break;
+    case TS_KECCAK_RC: { const u64 c = keccak_rc((int)par); prod[0] = (u32)c; prod[1] = (u32)(c >> 32); break; }
+    case TS_ROTL64: {
+        const u64 o = tr_rotl64((u64)rec[148] | ((u64)rec[149] << 32), par);
+        prod[0] = (u32)o; prod[1] = (u32)(o >> 32);
+        break;
+    }
+    case TS_ABSORB_CHUNK: {
+        const u32 mask = par >= 4 ? 0xFFFFFFFFu : ((1u << (8 * par)) - 1u);     // the contract: unused high bytes zero
+        strobe_absorb_chunk(t, rec[150] & mask, par);
+        break;
+    }
+    case TS_RUN_F: strobe_run_f(t); break;
+    case TS_SQUEEZE: {
+        uint8_t buf[200];
+#pragma nounroll
+        for (u32 i = 0; i < 200; i++) buf[i] = 0;
+        strobe_squeeze(t, buf, par);
+        st_bytes(prod, buf, (int)par);
+        break;
+    }
+    case TS_APPEND_WORDS: {
+        u32 mw[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) mw[k] = rec[k];
+        tr_with_label<0>(lab, [&](const auto& label) { t_append_words(t, label, mw, par); });
+        flags = 2;
+        break;
+    }
+    case TS_APPEND_U64: {
+        const u64 x = (u64)rec[144 + 2 * par] | ((u64)rec[145 + 2 * par] << 32);
+        tr_with_label<0>(lab, [&](const auto& label) { t_append_u64(t, label, x); });
+        flags = 2;
+        break;
+    }
+    case TS_APP_POINT: {
+        apt a;
+        ld_fe(a.x, rec + 64 + 20 * par, 1);
+        ld_fe(a.y, rec + 74 + 20 * par, 1);
+        tr_with_label<1>(lab, [&](const auto& label) { app_point(t, label, a); });
+        flags = 2;
+        break;
+    }
+    case TS_GET_CHALLENGE: {
+        sc c;
+        bool ok = false;
+        sc_set_u32(c, 0);
+        tr_with_label<2>(lab, [&](const auto& label) { ok = t_get_challenge(t, label, c); });
+        st_sc(prod, c);
+        prod[8] = ok ? 1u : 0u;
+        flags = 1 | 2 | 4;
+        break;
+    }
+    default: tr_step_regs(t, kind, lab, par, (const uint8_t*)rec, prod, flags); break;
+    }
+}
+// the program over one sponge that is loaded already; returns the flags of the last operation begun
+template <typename S>
+HD u32 tr_run_program(S& t, const u32* prog, const u32* rec, u32* out, u32 flags) {
+    u32 cur = 52;
+#pragma nounroll
+    for (u32 s = 0; s < prog[0]; s++) {
+        const u32 kind = prog[1 + 3 * s], lab = prog[2 + 3 * s], par = prog[3 + 3 * s];
+        tr_step(t, kind, lab, par, rec, out + cur, flags);
+        cur += tr_step_words(kind, par);
+    }
+    return flags;
+}
+// One record on the register sponge (every build).  The caller has checked the program (tr_prog_ok).
+HD void tr_eval_regs(const u32* prog, const uint8_t* state, const u32* rec, u32* out) {
+    strobe t;
+    if (!strobe_from_bytes(t, state)) { out[51] = TR_BAD_STATE; return; }
+    const u32 flags = tr_run_program(t, prog, rec, out, state[202]);
+    uint8_t b[204];
+    b[203] = 0;
+    strobe_to_bytes(b, t, flags);
+    st_bytes(out, b, 204);
+    out[51] = ST_OK;
 }
 
 }  // namespace prims

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "prims_core.h"
+#include "../../bp_pp_amd/csrc/kernels.h"     // for_each_position_group
 
 #define PRIMS_API extern "C" __attribute__((visibility("default")))
 
@@ -166,5 +167,103 @@ PRIMS_API int prims_run_sums_device(uint32_t cfg, const uint32_t* in, uint32_t* 
     if (w.pts) (void)hipFree(w.pts);
     if (w.tscr) (void)hipFree(w.tscr);
     if (w.atab) (void)hipFree(w.atab);
+    return (int)e;
+}
+
+// ---- the transcript primitives (prims_core.h: TrStep): one program over n records, one record per lane, in 64-thread blocks.
+// TR_UNIFORM calls the body directly: every lane of a wavefront must start at the same byte position (a wavefront that does not is
+// answered with TR_BAD_LAYOUT and not run: mixed positions outside the grouping wrapper break the functions' precondition).
+// TR_GROUPED runs the body inside for_each_position_group(preloaded_position_key(..)), as the product's kernels do.
+struct TrProg { uint32_t w[TR_PROG_WORDS]; };
+// what a lane does before its body: the program's bounds, and for the uniform layout the state and the wavefront's positions
+__device__ __forceinline__ bool tr_lane_begin(const TrProg& prog, uint32_t form, uint32_t layout, const uint8_t* st, uint32_t* o) {
+    if (!prims::tr_prog_ok(prog.w, form)) { o[51] = prims::ST_BAD_PARAM; return false; }
+    if (layout == prims::TR_GROUPED) return true;
+    if (!(st[200] < BPPP_STROBE_R && st[201] <= BPPP_STROBE_R)) { o[51] = prims::TR_BAD_STATE; return false; }
+    const uint32_t pos = st[200];
+    if (__any(pos != (uint32_t)__builtin_amdgcn_readfirstlane((int)pos))) { o[51] = prims::TR_BAD_LAYOUT; return false; }
+    return true;
+}
+__global__ __launch_bounds__(64) void k_transcript_regs(TrProg prog, uint32_t layout, const uint8_t* states, const uint32_t* in, uint32_t* out,
+                                                        size_t n) {
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint8_t* st = states + r * BPPP_TRANSCRIPT_STATE_BYTES;
+    const uint32_t* rec = in + r * TR_IN_WORDS;
+    uint32_t* o = out + r * TR_OUT_WORDS;
+    if (!tr_lane_begin(prog, prims::TR_REGS, layout, st, o)) return;
+    if (layout == prims::TR_UNIFORM) prims::tr_eval_regs(prog.w, st, rec, o);
+    else bppp::for_each_position_group(bppp::preloaded_position_key(states, n, r), [&]() { prims::tr_eval_regs(prog.w, st, rec, o); });
+}
+// the LDS sponge: each lane's column is sponge + threadIdx.x (k_verify_phase1); the state goes back through ws_st_transcript's word layout
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void tr_eval_lds(const TrProg& prog, const uint8_t* st, const uint32_t* rec, uint32_t* o, uint32_t* col,
+                                            uint32_t* tstate, size_t n, size_t r) {
+    bppp::strobe t0;
+    if (!bppp::strobe_from_bytes(t0, st)) { o[51] = prims::TR_BAD_STATE; return; }
+    bppp::strobe_lds t;
+    t.col = col;
+    bppp::strobe_lds_load(t, t0);
+    const uint32_t flags = prims::tr_run_program(t, prog.w, rec, o, st[202]);
+    bppp::ws_st_transcript(tstate, n, r, t);
+    bppp::strobe back;
+    bppp::ws_ld_transcript(back, tstate, n, r);
+    uint8_t b[204];
+    b[203] = 0;
+    bppp::strobe_to_bytes(b, back, flags);
+    prims::st_bytes(o, b, 204);
+    o[51] = prims::ST_OK;
+}
+#endif
+__global__ __launch_bounds__(64) void k_transcript_lds(TrProg prog, uint32_t layout, const uint8_t* states, const uint32_t* in, uint32_t* out,
+                                                       uint32_t* tstate, size_t n) {
+    __shared__ uint32_t sponge[50 * BPPP_LDS_STRIDE];
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint8_t* st = states + r * BPPP_TRANSCRIPT_STATE_BYTES;
+    const uint32_t* rec = in + r * TR_IN_WORDS;
+    uint32_t* o = out + r * TR_OUT_WORDS;
+    if (!tr_lane_begin(prog, prims::TR_LDS, layout, st, o)) return;
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t* col = sponge + threadIdx.x;
+    if (layout == prims::TR_UNIFORM) tr_eval_lds(prog, st, rec, o, col, tstate, n, r);
+    else bppp::for_each_position_group(bppp::preloaded_position_key(states, n, r), [&]() { tr_eval_lds(prog, st, rec, o, col, tstate, n, r); });
+#else
+    (void)sponge; (void)tstate;
+#endif
+}
+
+PRIMS_API int prims_transcript_words(int which) { return which == 0 ? TR_IN_WORDS : which == 1 ? TR_OUT_WORDS : TR_PROG_WORDS; }
+// n records through one program (TR_PROG_WORDS words) on one sponge form and launch layout.  Returns the first HIP error.
+PRIMS_API int prims_run_transcript_device(const uint32_t* prog, uint32_t form, uint32_t layout, const uint8_t* states, const uint32_t* in,
+                                          uint32_t* out, size_t n) {
+    if (n == 0) return 0;
+    if (form > prims::TR_LDS || layout > prims::TR_GROUPED) return (int)hipErrorInvalidValue;
+    TrProg p;
+    for (int i = 0; i < TR_PROG_WORDS; i++) p.w[i] = prog[i];
+    const size_t st_sz = n * BPPP_TRANSCRIPT_STATE_BYTES, in_sz = n * TR_IN_WORDS * sizeof(uint32_t), out_sz = n * TR_OUT_WORDS * sizeof(uint32_t);
+    const size_t ts_sz = n * 52 * sizeof(uint32_t);
+    uint8_t* dstates = nullptr;
+    uint32_t *din = nullptr, *dout = nullptr, *dts = nullptr;
+    hipError_t e = hipMalloc((void**)&dstates, st_sz);
+    if (e == hipSuccess) e = hipMalloc((void**)&din, in_sz);
+    if (e == hipSuccess) e = hipMalloc((void**)&dout, out_sz);
+    if (e == hipSuccess) e = hipMalloc((void**)&dts, ts_sz);
+    if (e == hipSuccess) e = hipMemcpy(dstates, states, st_sz, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(din, in, in_sz, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dout, 0, out_sz);
+    if (e == hipSuccess) e = hipMemset(dts, 0, ts_sz);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((n + 63) / 64));
+        if (form == prims::TR_REGS) hipLaunchKernelGGL(k_transcript_regs, grid, dim3(64), 0, 0, p, layout, dstates, din, dout, n);
+        else hipLaunchKernelGGL(k_transcript_lds, grid, dim3(64), 0, 0, p, layout, dstates, din, dout, dts, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, dout, out_sz, hipMemcpyDeviceToHost);
+    if (dstates) (void)hipFree(dstates);
+    if (din) (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    if (dts) (void)hipFree(dts);
     return (int)e;
 }

@@ -63,3 +63,18 @@ PRIMS_API int prims_run_sums_host(uint32_t cfg, const uint32_t* in, uint32_t* ou
     }
     return 0;
 }
+
+// The transcript primitives (prims_core.h: TrStep), one record after another on the register sponge -- the only form the host has; the
+// launch layouts are a device matter.  Returns 0, or -1 for a form the host cannot run.
+PRIMS_API int prims_transcript_words(int which) { return which == 0 ? TR_IN_WORDS : which == 1 ? TR_OUT_WORDS : TR_PROG_WORDS; }
+PRIMS_API int prims_run_transcript_host(const uint32_t* prog, uint32_t form, uint32_t layout, const uint8_t* states, const uint32_t* in,
+                                        uint32_t* out, size_t n) {
+    if (form != prims::TR_REGS || layout > prims::TR_GROUPED) return -1;
+    const bool ok = prims::tr_prog_ok(prog, form);
+    for (size_t r = 0; r < n; r++) {
+        uint32_t* o = out + r * TR_OUT_WORDS;
+        if (!ok) { o[51] = prims::ST_BAD_PARAM; continue; }
+        prims::tr_eval_regs(prog, states + r * BPPP_TRANSCRIPT_STATE_BYTES, in + r * TR_IN_WORDS, o);
+    }
+    return 0;
+}

@@ -24,7 +24,10 @@ The variable-base SUMS have records and kernels of their own (prims_core.h: SumF
 straus_affine_complete, straus_affine_complete and straus_split_lane on one lane (all builds), straus_affine_g4<M, G> and
 straus_affine_split<M, G, PARTS> on their real lane groups (device), over tables built by affine_tables_build / affine_table_one.
 Every sum is compared with sum_i k_i P_i of the oracle, for equal, opposite and identity points too, so a fallback that returned a
-wrong point fails here; the fast forms' flag is compared with a group-element model of the same lane."""
+wrong point fails here; the fast forms' flag is compared with a group-element model of the same lane.
+
+The TRANSCRIPT primitives (merlin.h: Keccak-f, the STROBE steps, the merlin operations; app_point; for_each_position_group) are a third
+family with records, entry points and launch layouts of their own (prims_core.h: TrStep), tested by tests/test_prims_transcript.py."""
 import math
 import random
 import struct
