@@ -35,12 +35,21 @@ EXPORTS = [
     "bppp_u64_prove_batch_sec1", "bppp_u64_prove_batch_sec1_device",
     "bppp_u64_verify_one", "bppp_u64_verify_one_transcript", "bppp_u64_prove_one", "bppp_u64_prove_one_transcript",
     "bppp_ctx_get_coalesce_stats", "bppp_ctx_get_option", "bppp_u64_plan", "bppp_plan_describe", "bppp_reciprocal_verify_one", "bppp_reciprocal_verify_one_transcript",
+    # the RLC mode and the single-proof front end over the wire form (bound in lib() only when present: RLC_SEC1_EXPORTS)
+    "bppp_u64_verify_batch_rlc_sec1", "bppp_u64_verify_batch_rlc_sec1_device", "bppp_reciprocal_verify_batch_rlc_sec1",
+    "bppp_reciprocal_verify_batch_rlc_sec1_device", "bppp_circuit_verify_batch_rlc_sec1", "bppp_circuit_verify_batch_rlc_sec1_device",
+    "bppp_wnla_verify_batch_rlc_sec1", "bppp_wnla_verify_batch_rlc_sec1_device",
+    "bppp_u64_verify_one_sec1", "bppp_u64_verify_one_sec1_transcript", "bppp_reciprocal_verify_one_sec1",
+    "bppp_reciprocal_verify_one_sec1_transcript",
     "bppp_reciprocal_verify_batch_sec1", "bppp_reciprocal_verify_batch_sec1_device", "bppp_circuit_verify_batch_sec1",
     "bppp_circuit_verify_batch_sec1_device", "bppp_wnla_verify_batch_sec1", "bppp_wnla_verify_batch_sec1_device",
     "bppp_reciprocal_prove_batch_sec1", "bppp_circuit_prove_batch_sec1", "bppp_wnla_prove_batch_sec1",
     "bppp_draw_scalars", "bppp_draw_scalars_device", "bppp_u64_prove_batch_seeded", "bppp_u64_prove_batch_seeded_device",
     "bppp_u64_prove_batch_seeded_sharded", "bppp_reciprocal_prove_batch_seeded", "bppp_circuit_prove_batch_seeded",
 ]
+
+# the entry points of the wire form's RLC mode and single-proof front end (a subset of EXPORTS)
+RLC_SEC1_EXPORTS = [name for name in EXPORTS if name.endswith(("_rlc_sec1", "_rlc_sec1_device")) or "_one_sec1" in name]
 
 _lib = None
 
@@ -210,6 +219,23 @@ def lib():
         L.bppp_wnla_prove_batch_sec1.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp]
         for name in EXPORTS[-16:-7]:
             getattr(L, name).restype = i32
+    # the wire form in RLC mode (the exact wire twins' argument lists and a 32-byte seed; the u64 device form has d_reject_count in
+    # place of the trace) and in the single-proof front end (the 64-byte *_one lists over 33-byte rows)
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_u64_verify_batch_rlc_sec1"):
+        L.bppp_u64_verify_batch_rlc_sec1.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, u8p]
+        L.bppp_u64_verify_batch_rlc_sec1_device.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, vp, u8p]
+        L.bppp_reciprocal_verify_batch_rlc_sec1.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, u8p]
+        L.bppp_reciprocal_verify_batch_rlc_sec1_device.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, u8p]
+        L.bppp_circuit_verify_batch_rlc_sec1.argtypes = [vp, vp, u8p, sz, sz, vp, vp, sz, sz, sz, vp, vp, u8p]
+        L.bppp_circuit_verify_batch_rlc_sec1_device.argtypes = [vp, vp, u8p, sz, sz, vp, vp, sz, sz, sz, vp, vp, u8p]
+        L.bppp_wnla_verify_batch_rlc_sec1.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, u8p]
+        L.bppp_wnla_verify_batch_rlc_sec1_device.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, u8p]
+        L.bppp_u64_verify_one_sec1.argtypes = [vp, u8p, sz, vp, vp, vp, vp]
+        L.bppp_u64_verify_one_sec1_transcript.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.bppp_reciprocal_verify_one_sec1.argtypes = [vp, u8p, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        L.bppp_reciprocal_verify_one_sec1_transcript.argtypes = [vp, vp, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        for name in RLC_SEC1_EXPORTS:
+            getattr(L, name).restype = i32
     # the seeded provers: (seed, stream_base) in place of rnd
     if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_draw_scalars"):
         u64 = C.c_uint64
@@ -227,6 +253,15 @@ def lib():
     L.bppp_last_error.restype = C.c_char_p
     _lib = L
     return L
+
+
+def symbol(name: str):
+    """An entry point of the loaded library; a library that lacks it (an A/B build of an earlier ABI loaded through BPPP_LIB) is an
+    error, never another path."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise NotImplementedError(f"the loaded libbppp_hip.so does not export {name} (built from an earlier include/bppp.h)")
+    return fn
 
 
 def check(rc: int):

@@ -18,6 +18,7 @@ static const size_t RND_BYTES = 52 * 32;
 struct RecipShape {          // the runtime shape of a generic reciprocal verify request (bppp_reciprocal_verify_batch's arguments)
     size_t nd = 0, np = 0, rounds = 0, nl = 0, nn = 0;
     size_t proof_bytes() const { return 64 * (5 + 2 * rounds) + 32 * (nl + nn); }
+    size_t wire_proof_bytes() const { return 33 * (5 + 2 * rounds) + 32 * (nl + nn); }
     bool operator==(const RecipShape& o) const { return nd == o.nd && np == o.np && rounds == o.rounds && nl == o.nl && nn == o.nn; }
 };
 struct bppp_front {
@@ -25,14 +26,18 @@ struct bppp_front {
     bool prove;
     bool recip = false;          // ReciprocalRangeProofProtocol::verify at runtime dimensions (rows: commitment, proof, transcript)
     RecipShape rs;
+    // the rows' format: false = 64-byte points, true = the wire form (33-byte SEC1 points; verify only).  A front end gathers rows of ONE
+    // format, so a sealed batch is one batched call: wire rows are expanded on the device by the batched wire-form verifier
+    bool sec1 = false;
     size_t max;
     std::vector<bppp_ctx*> lanes;
     Coalescer<bppp_front> co;
 
-    static CoalesceShape shape_of(bool prove) {
+    static CoalesceShape shape_of(bool prove, bool sec1) {
         CoalesceShape s;
         if (!prove) {               // in: commitment, proof, transcript | out: accept, status, transcript after verify
-            s.n_in = 3; s.in_stride[0] = 64; s.in_stride[1] = BPPP_U64_PROOF_BYTES; s.in_stride[2] = SB;
+            s.n_in = 3; s.in_stride[0] = sec1 ? BPPP_POINT_SEC1_BYTES : 64; s.in_stride[1] = sec1 ? BPPP_U64_PROOF_SEC1_BYTES : BPPP_U64_PROOF_BYTES;
+            s.in_stride[2] = SB;
             s.n_out = 3; s.out_stride[0] = 1; s.out_stride[1] = sizeof(int32_t); s.out_stride[2] = SB;
         } else {                    // in: x, s, the 52 draws, transcript | out: proof, commitment, status, transcript after prove
             s.n_in = 4; s.in_stride[0] = 8; s.in_stride[1] = 32; s.in_stride[2] = RND_BYTES; s.in_stride[3] = SB;
@@ -40,17 +45,18 @@ struct bppp_front {
         }
         return s;
     }
-    static CoalesceShape shape_of_recip(const RecipShape& r) {
+    static CoalesceShape shape_of_recip(const RecipShape& r, bool sec1) {
         CoalesceShape s;
-        s.n_in = 3; s.in_stride[0] = 64; s.in_stride[1] = r.proof_bytes(); s.in_stride[2] = SB;
+        s.n_in = 3; s.in_stride[0] = sec1 ? BPPP_POINT_SEC1_BYTES : 64; s.in_stride[1] = sec1 ? r.wire_proof_bytes() : r.proof_bytes(); s.in_stride[2] = SB;
         s.n_out = 3; s.out_stride[0] = 1; s.out_stride[1] = sizeof(int32_t); s.out_stride[2] = SB;
         return s;
     }
     CtShare ct;                  // the parent's "ct_prover" state when this front end was asked for (read under the parent's lock: fronts_of)
-    bppp_front(bppp_ctx* p, bool prove_, size_t max_, long wait_us, int nlanes, const CtShare& ct_)
-        : parent(p), prove(prove_), max(max_), co(this, shape_of(prove_), max_, wait_us, nlanes, BPPP_ERR_CLOSED, BPPP_ERR_NOMEM), ct(ct_) {}
-    bppp_front(bppp_ctx* p, const RecipShape& r, size_t max_, long wait_us, int nlanes, const CtShare& ct_)
-        : parent(p), prove(false), recip(true), rs(r), max(max_), co(this, shape_of_recip(r), max_, wait_us, nlanes, BPPP_ERR_CLOSED, BPPP_ERR_NOMEM), ct(ct_) {}
+    bppp_front(bppp_ctx* p, bool prove_, bool sec1_, size_t max_, long wait_us, int nlanes, const CtShare& ct_)
+        : parent(p), prove(prove_), sec1(sec1_), max(max_), co(this, shape_of(prove_, sec1_), max_, wait_us, nlanes, BPPP_ERR_CLOSED, BPPP_ERR_NOMEM), ct(ct_) {}
+    bppp_front(bppp_ctx* p, const RecipShape& r, bool sec1_, size_t max_, long wait_us, int nlanes, const CtShare& ct_)
+        : parent(p), prove(false), recip(true), rs(r), sec1(sec1_), max(max_),
+          co(this, shape_of_recip(r, sec1_), max_, wait_us, nlanes, BPPP_ERR_CLOSED, BPPP_ERR_NOMEM), ct(ct_) {}
 
     // ---- Backend of the coalescer
     void* alloc_staging(size_t bytes) {
@@ -72,8 +78,13 @@ struct bppp_front {
     int run(int lane, size_t n, uint8_t* const in[], uint8_t* const out[]) {
         bppp_ctx* c = lanes[lane];
         CtxLock lock_(c);
-        if (recip)      // the generic verifier's host-buffer entry point over the pinned rows (it stages, runs and waits by itself)
+        if (recip) {    // the generic verifier's host-buffer entry point over the pinned rows (it stages, runs and waits by itself)
+            if (sec1)
+                return recip_verify_sec1_transcript_host(c, n, in[2], n, rs.nd, rs.np, in[0], in[1], rs.rounds, rs.nl, rs.nn, out[0], (int32_t*)out[1], out[2]);
             return bppp_reciprocal_verify_batch_transcript(c, n, in[2], n, rs.nd, rs.np, in[0], in[1], rs.rounds, rs.nl, rs.nn, out[0], (int32_t*)out[1], out[2]);
+        }
+        if (sec1)       // wire rows: staged, expanded on the device and verified with the rows' transcripts (it waits, and quiesces on failure, itself)
+            return verify_sec1_transcript_host(c, n, in[2], n, in[0], in[1], out[0], (int32_t*)out[1], out[2]);
         const int rc = run_locked(c, n, in, out);
         // a failed call must not leave copies in flight over staging rows that the next batch is about to overwrite
         if (rc != BPPP_OK) quiesce(c);
@@ -140,6 +151,10 @@ struct bppp_front {
                 if (4 * (max < S ? max : S) > vt) vt = 4 * (max < S ? max : S);
                 if (2 * (max < 4 * S ? max : 4 * S) > vt) vt = 2 * (max < 4 * S ? max : 4 * S);
                 if (rc == BPPP_OK) rc = ensure_vtab_capacity(ch, vt);
+                if (rc == BPPP_OK && sec1) {      // wire rows: their staging and the expanded batch, for a full batch (bppp_u64.hip: verify_sec1_host_impl)
+                    rc = ensure_io(ch, max * (size_t)(BPPP_POINT_SEC1_BYTES + BPPP_U64_PROOF_SEC1_BYTES + 1 + sizeof(int32_t) + 2 * SB) + 64);
+                    if (rc == BPPP_OK) rc = ensure_buffer(ch, ch->d_expand, ch->expand_bytes, max * (size_t)(64 + BPPP_U64_PROOF_BYTES));
+                }
             }
             if (rc != BPPP_OK) return rc;
         }
@@ -155,8 +170,8 @@ struct bppp_front {
 // "coalesce_*" options.  Callers hold a shared_ptr while they are inside, so a teardown never frees a front end under a caller.
 struct bppp_fronts {
     std::mutex mu;
-    std::shared_ptr<bppp_front> f[2];     // 0 verify, 1 prove
-    std::vector<std::shared_ptr<bppp_front>> generic;     // reciprocal verify, one per shape in use (at most BPPP_MAX_GENERIC_FRONTS)
+    std::shared_ptr<bppp_front> f[3];     // 0 verify, 1 prove, 2 verify over wire rows
+    std::vector<std::shared_ptr<bppp_front>> generic;     // reciprocal verify, one per (shape, row format) in use (at most BPPP_MAX_GENERIC_FRONTS)
     bool closed = false;
 };
 static const size_t BPPP_MAX_GENERIC_FRONTS = 4;
@@ -191,7 +206,7 @@ static int get_front(bppp_ctx* c, int which, std::shared_ptr<bppp_front>& out) {
         std::shared_ptr<bppp_front> f;
         int rc;
         try {
-            f = std::make_shared<bppp_front>(c, which == 1, (size_t)o.max, o.us, o.lanes, o.ct);
+            f = std::make_shared<bppp_front>(c, which == 1, which == 2, (size_t)o.max, o.us, o.lanes, o.ct);
             rc = f->start();
         } catch (...) { rc = BPPP_ERR_NOMEM; }      // (nothing may throw across the C ABI)
         if (rc != BPPP_OK) return rc;
@@ -200,22 +215,22 @@ static int get_front(bppp_ctx* c, int which, std::shared_ptr<bppp_front>& out) {
     out = fs->f[which];
     return BPPP_OK;
 }
-static int get_recip_front(bppp_ctx* c, const RecipShape& r, std::shared_ptr<bppp_front>& out) {
+static int get_recip_front(bppp_ctx* c, const RecipShape& r, bool sec1, std::shared_ptr<bppp_front>& out) {
     FrontOptions o;
     bppp_fronts* fs = fronts_of(c, o);
     if (!fs) return c->fronts_closed.load() ? BPPP_ERR_CLOSED : BPPP_ERR_NOMEM;
     std::lock_guard<std::mutex> lk(fs->mu);
     if (fs->closed) return BPPP_ERR_CLOSED;
     for (auto& f : fs->generic)
-        if (f->rs == r) { out = f; return BPPP_OK; }
-    if (fs->generic.size() >= BPPP_MAX_GENERIC_FRONTS) {
+        if (f->rs == r && f->sec1 == sec1) { out = f; return BPPP_OK; }
+    if (fs->generic.size() >= BPPP_MAX_GENERIC_FRONTS) {      // (a shape used in both row formats counts twice: include/bppp.h)
         g_last_error = "too many different reciprocal shapes in single-proof use on one context";
         return BPPP_ERR_INVALID_ARG;
     }
     std::shared_ptr<bppp_front> f;
     int rc;
     try {
-        f = std::make_shared<bppp_front>(c, r, (size_t)o.max, o.us, o.lanes, o.ct);
+        f = std::make_shared<bppp_front>(c, r, sec1, (size_t)o.max, o.us, o.lanes, o.ct);
         rc = f->start();
         if (rc == BPPP_OK) fs->generic.push_back(f);
     } catch (...) { rc = BPPP_ERR_NOMEM; }
@@ -232,7 +247,7 @@ void bppp_fronts_teardown(bppp_ctx* c, bool final) {
         fs = c->fronts;
     }
     if (!fs) return;
-    std::shared_ptr<bppp_front> old[2 + BPPP_MAX_GENERIC_FRONTS];       // (no allocation on this path)
+    std::shared_ptr<bppp_front> old[3 + BPPP_MAX_GENERIC_FRONTS];       // (no allocation on this path)
     size_t n_old = 0;
     {
         std::lock_guard<std::mutex> lk(fs->mu);
@@ -315,9 +330,32 @@ int bppp_u64_prove_one(bppp_ctx* c, const uint8_t* label, size_t label_len, uint
     void* out[4] = {proof, commitment, status, nullptr};
     return submit_retry(c, 1, in, out);
 }
+// the same two over a wire row (33-byte commitment, 525-byte proof): the rows join the context's wire-form front end
+int bppp_u64_verify_one_sec1_transcript(bppp_ctx* c, uint8_t state[203], const uint8_t commitment33[33], const uint8_t proof525[525],
+                                        uint8_t* accept, int32_t* status) {
+    if (!c || !state || !commitment33 || !proof525 || !accept) return BPPP_ERR_INVALID_ARG;
+    OneCaller entered_(c);      // before anything else of the context is read (bppp_ctx_destroy waits for the count)
+    if (c->ng != 16 || c->nh != 32 || !state_ok(state)) return BPPP_ERR_INVALID_ARG;
+    const void* in[4] = {commitment33, proof525, state, nullptr};
+    void* out[4] = {accept, status, state, nullptr};
+    return submit_retry(c, 2, in, out);
+}
+int bppp_u64_verify_one_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, const uint8_t commitment33[33], const uint8_t proof525[525],
+                             uint8_t* accept, int32_t* status) {
+    if (!c || !label_ok(label, label_len) || !commitment33 || !proof525 || !accept) return BPPP_ERR_INVALID_ARG;
+    OneCaller entered_(c);      // before anything else of the context is read (bppp_ctx_destroy waits for the count)
+    if (c->ng != 16 || c->nh != 32) return BPPP_ERR_INVALID_ARG;
+    uint8_t st[SB];
+    int rc = bppp_transcript_new(label, label_len, st);
+    if (rc != BPPP_OK) return rc;
+    const void* in[4] = {commitment33, proof525, st, nullptr};
+    void* out[4] = {accept, status, nullptr, nullptr};
+    return submit_retry(c, 2, in, out);
+}
 // ReciprocalRangeProofProtocol::verify (reciprocal.rs:98-107) for ONE instance at runtime dimensions, from any number of threads
+// (sec1: the row is in the wire form -- 33-byte commitment, proof of 33 P + 32 S bytes -- and joins that format's front end of its shape)
 static int recip_one(bppp_ctx* c, uint8_t* state_io, const uint8_t* state_in, size_t dim_nd, size_t dim_np, const uint8_t* commitment,
-                     const uint8_t* proof, size_t rounds, size_t nl, size_t nn, uint8_t* accept, int32_t* status) {
+                     const uint8_t* proof, size_t rounds, size_t nl, size_t nn, uint8_t* accept, int32_t* status, bool sec1 = false) {
     if (!c || !commitment || !proof || !accept) return BPPP_ERR_INVALID_ARG;
     OneCaller inside(c);        // before anything else of the context is read (bppp_ctx_destroy waits for the count)
     // the shape must be one the context's generators can serve (bppp_generic.hip: recip_verify_check_args) before a front end is made for it
@@ -330,7 +368,7 @@ static int recip_one(bppp_ctx* c, uint8_t* state_io, const uint8_t* state_in, si
     for (;;) {
         if (inside.closed()) return BPPP_ERR_CLOSED;
         std::shared_ptr<bppp_front> f;
-        int rc = get_recip_front(c, r, f);
+        int rc = get_recip_front(c, r, sec1, f);
         if (rc != BPPP_OK) return rc;
         rc = f->co.submit(in, out);
         if (rc != BPPP_ERR_CLOSED) return rc;
@@ -349,8 +387,22 @@ int bppp_reciprocal_verify_one_transcript(bppp_ctx* c, uint8_t state[203], size_
     if (!state || !state_ok(state)) return BPPP_ERR_INVALID_ARG;
     return recip_one(c, state, state, dim_nd, dim_np, commitment, proof, rounds, nl, nn, accept, status);
 }
+int bppp_reciprocal_verify_one_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t dim_nd, size_t dim_np,
+                                    const uint8_t commitment33[33], const uint8_t* proof33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                    int32_t* status) {
+    if (!label_ok(label, label_len)) return BPPP_ERR_INVALID_ARG;
+    uint8_t st[SB];
+    int rc = bppp_transcript_new(label, label_len, st);
+    if (rc != BPPP_OK) return rc;
+    return recip_one(c, nullptr, st, dim_nd, dim_np, commitment33, proof33, rounds, nl, nn, accept, status, true);
+}
+int bppp_reciprocal_verify_one_sec1_transcript(bppp_ctx* c, uint8_t state[203], size_t dim_nd, size_t dim_np, const uint8_t commitment33[33],
+                                               const uint8_t* proof33, size_t rounds, size_t nl, size_t nn, uint8_t* accept, int32_t* status) {
+    if (!state || !state_ok(state)) return BPPP_ERR_INVALID_ARG;
+    return recip_one(c, state, state, dim_nd, dim_np, commitment33, proof33, rounds, nl, nn, accept, status, true);
+}
 int bppp_ctx_get_coalesce_stats(bppp_ctx* c, int which, uint64_t out[8]) {
-    if (!c || !out || which < 0 || which > 1) return BPPP_ERR_INVALID_ARG;
+    if (!c || !out || which < 0 || which > 2) return BPPP_ERR_INVALID_ARG;
     for (int i = 0; i < 8; i++) out[i] = 0;
     bppp_fronts* fs;
     {

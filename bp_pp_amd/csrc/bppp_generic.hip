@@ -1490,7 +1490,8 @@ static size_t recip_sec1_exp_bytes(size_t n, size_t rounds, size_t nl, size_t nn
 }
 // arguments checked; d_exp: recip_sec1_exp_bytes in the wire buffer
 static int recip_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np, const uint8_t* d_com33,
-                          const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status, uint8_t* d_exp) {
+                          const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status, uint8_t* d_exp,
+                          const uint8_t* rlc_seed) {
     const size_t P = 5 + 2 * rounds, S = nl + nn, o_p = align16(n * 64);
     WireMap m;
     wire_map_init(m, n);
@@ -1499,34 +1500,48 @@ static int recip_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, s
     // on c->stream: a call split into parts forks them from c->stream behind this (ev_twin_fork in recip_verify_device_entry)
     int rc = wire_launch(m, true, c->stream);
     if (rc != BPPP_OK) return rc;
-    return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, nullptr, nullptr);
+    return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, rlc_seed, nullptr);
 }
-int bppp_reciprocal_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
-                                             const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
-                                             void* d_accept, void* d_status) {
-    CtxLock lock_(c);
+// rlc_seed (the *_rlc_sec1 entry points of all three verifiers): the expansion is the same launch; what runs behind it is the 64-byte
+// RLC twin's pipeline on the expanded bytes, so a flagged instance is kept out of the weighted sums exactly as there
+static int recip_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                  const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                                  void* d_accept, void* d_status, const uint8_t* rlc_seed) {
     if (!c || !label_ok(label, label_len) || !d_commitments33 || !d_proofs33 || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
     int rc = recip_verify_check_args(c, dim_nd, dim_np, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
     if (recip_is_u64_shape(c, dim_nd, dim_np, rounds, nl, nn))      // the u64 wire form is the same 33 + 525 bytes: its own expand kernel
-        return verify_sec1_device_impl(c, label, label_len, n, d_commitments33, d_proofs33, d_accept, d_status, nullptr, nullptr);
+        return verify_sec1_device_impl(c, label, label_len, n, d_commitments33, d_proofs33, d_accept, d_status, nullptr, nullptr, rlc_seed);
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
     rc = ensure_buffer(c, c->d_wire, c->wire_bytes, recip_sec1_exp_bytes(n, rounds, nl, nn));
     if (rc != BPPP_OK) return rc;
     return recip_sec1_run(c, label, label_len, n, dim_nd, dim_np, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, rounds, nl, nn,
-                          d_accept, d_status, c->d_wire);
+                          d_accept, d_status, c->d_wire, rlc_seed);
 }
-int bppp_reciprocal_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
-                                      const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
-                                      int32_t* status) {
+int bppp_reciprocal_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                             const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                                             void* d_accept, void* d_status) {
     CtxLock lock_(c);
+    return recip_sec1_device_impl(c, label, label_len, n, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status, nullptr);
+}
+int bppp_reciprocal_verify_batch_rlc_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                                 const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                                                 void* d_accept, void* d_status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return recip_sec1_device_impl(c, label, label_len, n, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status, seed);
+}
+static int recip_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                int32_t* status, const uint8_t* rlc_seed) {
     if (!c || !label_ok(label, label_len) || !commitments33 || !proofs33 || !accept) return BPPP_ERR_INVALID_ARG;
     int rc = recip_verify_check_args(c, dim_nd, dim_np, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
     if (n == 0) return BPPP_OK;
     if (recip_is_u64_shape(c, dim_nd, dim_np, rounds, nl, nn))
-        return bppp_u64_verify_batch_sec1(c, label, label_len, n, commitments33, proofs33, accept, status);
+        return rlc_seed ? bppp_u64_verify_batch_rlc_sec1(c, label, label_len, n, commitments33, proofs33, accept, status, rlc_seed)
+                        : bppp_u64_verify_batch_sec1(c, label, label_len, n, commitments33, proofs33, accept, status);
     HIP_TRY(hipSetDevice(c->device));
     const size_t pb = wire_proof_bytes(5 + 2 * rounds, nl + nn);
     const size_t o_c = 0, o_p = align16(n * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_e = align16(o_s + n * 4),
@@ -1538,8 +1553,70 @@ int bppp_reciprocal_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t 
     hipStream_t s = c->stream;
     HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * 33, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
-    rc = recip_sec1_run(c, label, label_len, n, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, d + o_e);
+    rc = recip_sec1_run(c, label, label_len, n, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, d + o_e, rlc_seed);
     if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPPP_OK;
+}
+int bppp_reciprocal_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                      const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                      int32_t* status) {
+    CtxLock lock_(c);
+    return recip_sec1_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, nullptr);
+}
+int bppp_reciprocal_verify_batch_rlc_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                          const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn,
+                                          uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return recip_sec1_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, seed);
+}
+// the single-proof front end's batched call over wire rows (bppp_coalesce.hip: bppp_reciprocal_verify_one_sec1): the callers' transcripts
+// in (1 or n), each instance's advanced transcript out -- bppp_reciprocal_verify_batch_transcript over the wire form.  Staging and the
+// expanded inputs in the wire buffer, the workspace in the device entry points' grow-only buffer: no allocation once a front end is warm
+int recip_verify_sec1_transcript_host(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, size_t dim_nd, size_t dim_np,
+                                      const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn,
+                                      uint8_t* accept, int32_t* status, uint8_t* states_out) {
+    CtxLock lock_(c);
+    if (!c || !states || !commitments33 || !proofs33 || !accept) return BPPP_ERR_INVALID_ARG;
+    int rc = recip_verify_check_args(c, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (n == 0) return BPPP_OK;
+    const HostTranscripts tx = {states, n_states, states_out};
+    rc = check_host_transcripts(&tx, n);
+    if (rc != BPPP_OK) return rc;
+    if (recip_is_u64_shape(c, dim_nd, dim_np, rounds, nl, nn))
+        return verify_sec1_transcript_host(c, n, states, n_states, commitments33, proofs33, accept, status, states_out);
+    HIP_TRY(hipSetDevice(c->device));
+    rc = ensure_straus_capacity(c, n);
+    if (rc != BPPP_OK) return rc;
+    const size_t P = 5 + 2 * rounds, S = nl + nn, pb = wire_proof_bytes(P, S), e_p = align16(n * 64);
+    const size_t o_c = 0, o_p = align16(n * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_ti = align16(o_s + n * 4),
+                 o_to = align16(o_ti + n_states * 203), o_e = align16(o_to + (states_out ? n * 203 : 0)),
+                 total = o_e + recip_sec1_exp_bytes(n, rounds, nl, nn);
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
+    if (rc != BPPP_OK) return rc;
+    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, recip_verify_ws_bytes(c, n, dim_nd, dim_np, rounds, false));
+    if (rc != BPPP_OK) return rc;
+    WireQuiesce guard{c};
+    uint8_t* d = c->d_wire;
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * 33, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_ti, states, n_states * 203, hipMemcpyHostToDevice, s));
+    WireMap m;
+    wire_map_init(m, n);
+    wire_map_add(m, false, d + o_c, 33, d + o_e, 64, 1);
+    wire_add_proof(m, d + o_p, d + o_e + e_p, P, S);
+    rc = wire_launch(m, true, s);
+    if (rc != BPPP_OK) return rc;
+    const TranscriptIo dtio = {d + o_ti, n_states, states_out ? d + o_to : nullptr, 0};
+    rc = recip_verify_device_impl(c, nullptr, 0, n, dim_nd, dim_np, d + o_e, d + o_e + e_p, rounds, nl, nn, d + o_a, (int32_t*)(d + o_s),
+                                  c->d_gws, &dtio, nullptr);
+    if (rc != BPPP_OK) return rc;
+    if (states_out) HIP_TRY(hipMemcpyAsync(states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1551,7 +1628,8 @@ static size_t circuit_sec1_exp_bytes(size_t n, size_t k, size_t rounds, size_t n
     return align16(n * k * 64) + n * (64 * (4 + 2 * rounds) + 32 * (nl + nn));
 }
 static int circuit_sec1_run(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n, const uint8_t* d_com33,
-                            const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* d_accept, int32_t* d_status, uint8_t* d_exp) {
+                            const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* d_accept, int32_t* d_status, uint8_t* d_exp,
+                            const uint8_t* rlc_seed) {
     const size_t k = (size_t)q->cd.k, P = 4 + 2 * rounds, S = nl + nn, o_p = align16(n * k * 64);
     WireMap m;
     wire_map_init(m, n);
@@ -1559,12 +1637,11 @@ static int circuit_sec1_run(bppp_ctx* c, const bppp_circuit* q, const uint8_t* l
     wire_add_proof(m, d_proofs33, d_exp + o_p, P, S);
     int rc = wire_launch(m, true, c->stream);
     if (rc != BPPP_OK) return rc;
-    return circuit_verify_host_impl(c, q, label, label_len, n, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, nullptr, true);
+    return circuit_verify_host_impl(c, q, label, label_len, n, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, nullptr, true, rlc_seed);
 }
-int bppp_circuit_verify_batch_sec1_device(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
-                                          const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
-                                          void* d_accept, void* d_status) {
-    CtxLock lock_(c);
+static int circuit_sec1_device_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                    const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                                    void* d_accept, void* d_status, const uint8_t* rlc_seed) {
     int rc = circuit_verify_check(c, q, label, label_len, d_commitments33, d_proofs33, d_accept, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
     if (n == 0) return BPPP_OK;
@@ -1572,12 +1649,24 @@ int bppp_circuit_verify_batch_sec1_device(bppp_ctx* c, const bppp_circuit* q, co
     rc = ensure_buffer(c, c->d_wire, c->wire_bytes, circuit_sec1_exp_bytes(n, (size_t)q->cd.k, rounds, nl, nn));
     if (rc != BPPP_OK) return rc;
     return circuit_sec1_run(c, q, label, label_len, n, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, rounds, nl, nn,
-                            (uint8_t*)d_accept, (int32_t*)d_status, c->d_wire);
+                            (uint8_t*)d_accept, (int32_t*)d_status, c->d_wire, rlc_seed);
 }
-int bppp_circuit_verify_batch_sec1(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
-                                   const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
-                                   int32_t* status) {
+int bppp_circuit_verify_batch_sec1_device(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                          const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                                          void* d_accept, void* d_status) {
     CtxLock lock_(c);
+    return circuit_sec1_device_impl(c, q, label, label_len, n, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status, nullptr);
+}
+int bppp_circuit_verify_batch_rlc_sec1_device(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                              const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                                              void* d_accept, void* d_status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return circuit_sec1_device_impl(c, q, label, label_len, n, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status, seed);
+}
+static int circuit_sec1_host_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                  const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                  int32_t* status, const uint8_t* rlc_seed) {
     int rc = circuit_verify_check(c, q, label, label_len, commitments33, proofs33, accept, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
     if (n == 0) return BPPP_OK;
@@ -1592,19 +1681,33 @@ int bppp_circuit_verify_batch_sec1(bppp_ctx* c, const bppp_circuit* q, const uin
     hipStream_t s = c->stream;
     HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * k * 33, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
-    rc = circuit_sec1_run(c, q, label, label_len, n, d + o_c, d + o_p, rounds, nl, nn, d + o_a, (int32_t*)(d + o_s), d + o_e);
+    rc = circuit_sec1_run(c, q, label, label_len, n, d + o_c, d + o_p, rounds, nl, nn, d + o_a, (int32_t*)(d + o_s), d + o_e, rlc_seed);
     if (rc != BPPP_OK) return rc;
     HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return BPPP_OK;
 }
+int bppp_circuit_verify_batch_sec1(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                   const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                   int32_t* status) {
+    CtxLock lock_(c);
+    return circuit_sec1_host_impl(c, q, label, label_len, n, commitments33, proofs33, rounds, nl, nn, accept, status, nullptr);
+}
+int bppp_circuit_verify_batch_rlc_sec1(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
+                                       const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn,
+                                       uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return circuit_sec1_host_impl(c, q, label, label_len, n, commitments33, proofs33, rounds, nl, nn, accept, status, seed);
+}
 
 // ---- WeightNormLinearArgument (the commitment and proof.r / proof.x are points; proof.l / proof.n scalars, taken as they are)
 static size_t wnla_sec1_exp_bytes(size_t n, size_t rounds) { return align16(n * 64) + 2 * align16(n * rounds * 64); }
 static int wnla_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* d_com33, const uint8_t* d_c,
                          const uint8_t* d_rho, const uint8_t* d_mu, size_t rounds, const uint8_t* d_r33, const uint8_t* d_x33, const uint8_t* d_l,
-                         size_t nl, const uint8_t* d_n, size_t nn, uint8_t* d_accept, int32_t* d_status, uint8_t* d_exp) {
+                         size_t nl, const uint8_t* d_n, size_t nn, uint8_t* d_accept, int32_t* d_status, uint8_t* d_exp,
+                         const uint8_t* rlc_seed) {
     const size_t o_r = align16(n * 64), o_x = o_r + align16(n * rounds * 64);
     WireMap m;
     wire_map_init(m, n);
@@ -1616,13 +1719,12 @@ static int wnla_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, si
     int rc = wire_launch(m, true, c->stream);
     if (rc != BPPP_OK) return rc;
     return wnla_run(c, false, label, label_len, n, d_exp, d_c, d_rho, d_mu, rounds, d_exp + o_r, d_exp + o_x, d_l, nl, d_n, nn, nullptr,
-                    d_accept, d_status, nullptr, true);
+                    d_accept, d_status, nullptr, true, rlc_seed);
 }
-int bppp_wnla_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33,
-                                       const void* d_c, const void* d_rho, const void* d_mu, size_t rounds, const void* d_proof_r33,
-                                       const void* d_proof_x33, const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn,
-                                       void* d_accept, void* d_status) {
-    CtxLock lock_(c);
+static int wnla_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33,
+                                 const void* d_c, const void* d_rho, const void* d_mu, size_t rounds, const void* d_proof_r33,
+                                 const void* d_proof_x33, const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn,
+                                 void* d_accept, void* d_status, const uint8_t* rlc_seed) {
     int rc = wnla_verify_check(c, label, label_len, d_commitments33, d_c, d_rho, d_mu, rounds, d_proof_r33, d_proof_x33, d_proof_l, nl, d_proof_n,
                                nn, d_accept);
     if (rc != BPPP_OK) return rc;
@@ -1633,13 +1735,29 @@ int bppp_wnla_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t
     if (rc != BPPP_OK) return rc;
     return wnla_sec1_run(c, label, label_len, n, (const uint8_t*)d_commitments33, (const uint8_t*)d_c, (const uint8_t*)d_rho, (const uint8_t*)d_mu,
                          rounds, (const uint8_t*)d_proof_r33, (const uint8_t*)d_proof_x33, (const uint8_t*)d_proof_l, nl, (const uint8_t*)d_proof_n,
-                         nn, (uint8_t*)d_accept, (int32_t*)d_status, c->d_wire);
+                         nn, (uint8_t*)d_accept, (int32_t*)d_status, c->d_wire, rlc_seed);
 }
-int bppp_wnla_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
-                                const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r33,
-                                const uint8_t* proof_x33, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
-                                uint8_t* accept, int32_t* status) {
+int bppp_wnla_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33,
+                                       const void* d_c, const void* d_rho, const void* d_mu, size_t rounds, const void* d_proof_r33,
+                                       const void* d_proof_x33, const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn,
+                                       void* d_accept, void* d_status) {
     CtxLock lock_(c);
+    return wnla_sec1_device_impl(c, label, label_len, n, d_commitments33, d_c, d_rho, d_mu, rounds, d_proof_r33, d_proof_x33, d_proof_l, nl,
+                                 d_proof_n, nn, d_accept, d_status, nullptr);
+}
+int bppp_wnla_verify_batch_rlc_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33,
+                                           const void* d_c, const void* d_rho, const void* d_mu, size_t rounds, const void* d_proof_r33,
+                                           const void* d_proof_x33, const void* d_proof_l, size_t nl, const void* d_proof_n, size_t nn,
+                                           void* d_accept, void* d_status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return wnla_sec1_device_impl(c, label, label_len, n, d_commitments33, d_c, d_rho, d_mu, rounds, d_proof_r33, d_proof_x33, d_proof_l, nl,
+                                 d_proof_n, nn, d_accept, d_status, seed);
+}
+static int wnla_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
+                               const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r33,
+                               const uint8_t* proof_x33, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
+                               uint8_t* accept, int32_t* status, const uint8_t* rlc_seed) {
     int rc = wnla_verify_check(c, label, label_len, commitments33, cvec, rho, mu, rounds, proof_r33, proof_x33, proof_l, nl, proof_n, nn, accept);
     if (rc != BPPP_OK) return rc;
     if (!wnla_shape_ok(rounds, nl, nn)) return BPPP_ERR_INVALID_ARG;
@@ -1668,12 +1786,29 @@ int bppp_wnla_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_
     HIP_TRY(up(o_l, proof_l, n * nl * 32));
     HIP_TRY(up(o_n, proof_n, n * nn * 32));
     rc = wnla_sec1_run(c, label, label_len, n, d + o_com, d + o_c, d + o_rho, d + o_mu, rounds, d + o_r, d + o_x, d + o_l, nl, d + o_n, nn,
-                       d + o_a, (int32_t*)(d + o_s), d + o_e);
+                       d + o_a, (int32_t*)(d + o_s), d + o_e, rlc_seed);
     if (rc != BPPP_OK) return rc;
     HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return BPPP_OK;
+}
+int bppp_wnla_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
+                                const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r33,
+                                const uint8_t* proof_x33, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
+                                uint8_t* accept, int32_t* status) {
+    CtxLock lock_(c);
+    return wnla_sec1_host_impl(c, label, label_len, n, commitments33, cvec, rho, mu, rounds, proof_r33, proof_x33, proof_l, nl, proof_n, nn,
+                               accept, status, nullptr);
+}
+int bppp_wnla_verify_batch_rlc_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
+                                    const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r33,
+                                    const uint8_t* proof_x33, const uint8_t* proof_l, size_t nl, const uint8_t* proof_n, size_t nn,
+                                    uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return wnla_sec1_host_impl(c, label, label_len, n, commitments33, cvec, rho, mu, rounds, proof_r33, proof_x33, proof_l, nl, proof_n, nn,
+                               accept, status, seed);
 }
 
 // ---- provers: the 64-byte provers' impls with sec1 = true (33-byte commitments in, 33-byte proof points out)

@@ -792,7 +792,9 @@ int bppp_u64_prove_batch(bppp_ctx* c, const uint8_t* label, size_t label_len, si
 }
 
 int verify_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33, const void* d_proofs525,
-                            void* d_accept, void* d_status, void* d_trace, void* d_reject_count) {
+                            void* d_accept, void* d_status, void* d_trace, void* d_reject_count, const uint8_t* rlc_seed,
+                            const VerifyTranscripts* tx) {
+    // rlc_seed / tx: handed on to verify_device_impl as they are (the RLC mode; the callers' own transcripts, one per proof or one for all)
     if (!c || !d_commitments33 || !d_proofs525 || !d_accept) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -806,38 +808,75 @@ int verify_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     const unsigned blocks = (unsigned)((n * 16 + 255) / 256);
     k_sec1_expand<<<blocks, 256, 0, c->stream>>>(d_c64, d_p928, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs525, n);
     HIP_TRY(hipGetLastError());
-    return verify_device_impl(c, label, label_len, n, d_c64, d_p928, d_accept, d_status, d_trace, d_reject_count, nullptr, nullptr);
+    return verify_device_impl(c, label, label_len, n, d_c64, d_p928, d_accept, d_status, d_trace, d_reject_count, rlc_seed, tx);
 }
 int bppp_u64_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33,
                                       const void* d_proofs525, void* d_accept, void* d_status, void* d_trace, void* d_reject_count) {
     CtxLock lock_(c);
-    return verify_sec1_device_impl(c, label, label_len, n, d_commitments33, d_proofs525, d_accept, d_status, d_trace, d_reject_count);
+    return verify_sec1_device_impl(c, label, label_len, n, d_commitments33, d_proofs525, d_accept, d_status, d_trace, d_reject_count, nullptr, nullptr);
+}
+// the RLC mode over the wire form: the same expansion in front of bppp_u64_verify_batch_rlc_device's pipeline.  An undecodable point is
+// the off-curve (1, 0) by then, phase 1 flags its proof, and a flagged proof has weight zero in the bucket stage (bucket_core.h:
+// bkt_prepare) and makes its chunk unusable in the chunk stage (rlc_core.h), so it never enters a weighted sum.
+int bppp_u64_verify_batch_rlc_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33,
+                                          const void* d_proofs525, void* d_accept, void* d_status, void* d_reject_count, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return verify_sec1_device_impl(c, label, label_len, n, d_commitments33, d_proofs525, d_accept, d_status, nullptr, d_reject_count, seed, nullptr);
 }
 
-int bppp_u64_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
-                               const uint8_t* proofs525, uint8_t* accept, int32_t* status) {
-    CtxLock lock_(c);
+// host buffers in the wire form: staged in the context's I/O buffer, expanded and verified on the device.  rlc_seed: the RLC mode;
+// states (n_states = 1 or n) / states_out: the callers' transcripts instead of the label (verify_sec1_transcript_host)
+static int verify_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
+                                 const uint8_t* proofs525, uint8_t* accept, int32_t* status, const uint8_t* rlc_seed, const uint8_t* states,
+                                 size_t n_states, uint8_t* states_out) {
     if (!c || !commitments33 || !proofs525 || !accept) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
+    const size_t SB = BPPP_TRANSCRIPT_STATE_BYTES;
     const size_t o_c = 0, o_p = o_c + n * 33, o_a = o_p + n * (size_t)BPPP_U64_PROOF_SEC1_BYTES, o_s = (o_a + n + 3) / 4 * 4,
-                 total = o_s + n * sizeof(int32_t);
+                 o_ti = align16(o_s + n * sizeof(int32_t)), o_to = align16(o_ti + (states ? n_states * SB : 0)),
+                 total = o_to + (states_out ? n * SB : 0);
     int rc = ensure_io(c, total);
     if (rc != BPPP_OK) return rc;
     uint8_t* d = c->d_io;
     hipError_t e = hipMemcpyAsync(d + o_c, commitments33, n * 33, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_p, proofs525, n * (size_t)BPPP_U64_PROOF_SEC1_BYTES, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && states) e = hipMemcpyAsync(d + o_ti, states, n_states * SB, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        rc = bppp_u64_verify_batch_sec1_device(c, label, label_len, n, d + o_c, d + o_p, d + o_a, d + o_s, nullptr, nullptr);
+        const VerifyTranscripts tx = {d + o_ti, n_states, states_out ? d + o_to : nullptr};
+        rc = verify_sec1_device_impl(c, label, label_len, n, d + o_c, d + o_p, d + o_a, d + o_s, nullptr, nullptr, rlc_seed, states ? &tx : nullptr);
         if (rc == BPPP_OK) {
             e = hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess && status) e = hipMemcpyAsync(status, d + o_s, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && states_out) e = hipMemcpyAsync(states_out, d + o_to, n * SB, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         }
     }
     if (e != hipSuccess || rc != BPPP_OK) quiesce(c);
     if (e != hipSuccess) { g_last_error = std::string("verify_batch_sec1: ") + hipGetErrorString(e); return BPPP_ERR_HIP; }
     return rc;
+}
+int bppp_u64_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
+                               const uint8_t* proofs525, uint8_t* accept, int32_t* status) {
+    CtxLock lock_(c);
+    return verify_sec1_host_impl(c, label, label_len, n, commitments33, proofs525, accept, status, nullptr, nullptr, 0, nullptr);
+}
+int bppp_u64_verify_batch_rlc_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
+                                   const uint8_t* proofs525, uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return verify_sec1_host_impl(c, label, label_len, n, commitments33, proofs525, accept, status, seed, nullptr, 0, nullptr);
+}
+// the single-proof front end's batched call over wire rows (bppp_coalesce.hip): one pre-loaded transcript per row in, each row's
+// advanced transcript out (the input state for a row flagged BPPP_ST_BAD_ENCODING, as in bppp_u64_verify_batch_transcript)
+int verify_sec1_transcript_host(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, const uint8_t* commitments33,
+                                const uint8_t* proofs525, uint8_t* accept, int32_t* status, uint8_t* states_out) {
+    CtxLock lock_(c);
+    if (!states || (n_states != 1 && n_states != n)) return BPPP_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n_states; i++)
+        if (states[203 * i + 200] >= BPPP_STROBE_R || states[203 * i + 201] > BPPP_STROBE_R) return BPPP_ERR_INVALID_ARG;
+    return verify_sec1_host_impl(c, nullptr, 0, n, commitments33, proofs525, accept, status, nullptr, states, n_states, states_out);
 }
 
 // ---- the prover's output in the wire format (33-byte commitments, 525-byte proofs): proved into the context's 64-byte staging

@@ -532,7 +532,15 @@ int verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size
                        const VerifyTranscripts* tx);
 // bppp_u64.hip: SEC1-compressed inputs expanded into the context's buffer, then verify_device_impl
 int verify_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33, const void* d_proofs525,
-                            void* d_accept, void* d_status, void* d_trace, void* d_reject_count);
+                            void* d_accept, void* d_status, void* d_trace, void* d_reject_count, const uint8_t* rlc_seed = nullptr,
+                            const VerifyTranscripts* tx = nullptr);
+// bppp_u64.hip / bppp_generic.hip: the wire form with the callers' transcripts over HOST buffers (states: 1 or n x 203 in, n x 203 out or
+// null) -- what a sealed batch of the single-proof front end's wire rows runs; stages, runs and waits by itself
+int verify_sec1_transcript_host(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, const uint8_t* commitments33,
+                                const uint8_t* proofs525, uint8_t* accept, int32_t* status, uint8_t* states_out);
+int recip_verify_sec1_transcript_host(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, size_t dim_nd, size_t dim_np,
+                                      const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn,
+                                      uint8_t* accept, int32_t* status, uint8_t* states_out);
 // bppp_u64.hip: the u64 prover over device buffers, asynchronous on c->stream (the caller holds the context's lock)
 int prove_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_x, const void* d_s, const void* d_rnd,
                       void* d_proofs, void* d_commitments, void* d_status, const VerifyTranscripts* tx);

@@ -192,10 +192,26 @@ class U64RangeProofProtocol:
             _capi.check(L.bppp_u64_prove_one_transcript(self._ctx, transcript._buf, x, bytes(s), bytes(rnd), proof, com, C.byref(st)))
         return proof.raw, com.raw, int(st.value)
 
+    def verify_one_sec1(self, v33: bytes, proof525: bytes, transcript) -> Tuple[bool, int]:
+        """verify_one over a wire row (33-byte SEC1 commitment, 525-byte proof: bppp_u64_verify_one_sec1[_transcript]): the row joins
+        the context's wire-form front end, whose sealed batches are decompressed on the device.  Callers of verify_one and of this
+        may share the protocol object.  Returns (accept, status); an undecodable point gives status BPPP_ST_BAD_ENCODING and leaves
+        a Transcript untouched."""
+        v33, proof525 = bytes(v33), bytes(proof525)
+        if len(v33) != 33 or len(proof525) != 525:
+            raise ValueError(f"commitment is 33 bytes and a u64 wire proof 525 bytes (got {len(v33)}, {len(proof525)})")
+        acc, st = C.c_uint8(0), C.c_int32(0)
+        if isinstance(transcript, (bytes, bytearray)):
+            _capi.check(_capi.symbol("bppp_u64_verify_one_sec1")(self._ctx, bytes(transcript), len(transcript), v33, proof525,
+                                                                 C.byref(acc), C.byref(st)))
+        else:
+            _capi.check(_capi.symbol("bppp_u64_verify_one_sec1_transcript")(self._ctx, transcript._buf, v33, proof525, C.byref(acc), C.byref(st)))
+        return bool(acc.value), int(st.value)
+
     def coalesce_stats(self, which: str = "verify") -> dict:
-        """Counters of the single-proof front end (bppp_ctx_get_coalesce_stats)."""
+        """Counters of the single-proof front end (bppp_ctx_get_coalesce_stats): "verify", "prove" or "verify_sec1"."""
         out = (C.c_uint64 * 8)()
-        _capi.check(_capi.lib().bppp_ctx_get_coalesce_stats(self._ctx, 1 if which == "prove" else 0, out))
+        _capi.check(_capi.lib().bppp_ctx_get_coalesce_stats(self._ctx, {"verify": 0, "prove": 1, "verify_sec1": 2}[which], out))
         return dict(zip(("requests", "batches", "largest_batch", "sealed_full", "sealed_deadline", "run_us", "fill_wait_us"), (int(v) for v in out)))
 
     def verify_batch(self, commitments, proofs, label: bytes) -> Tuple[np.ndarray, np.ndarray]:
@@ -279,6 +295,28 @@ class U64RangeProofProtocol:
         _capi.check(_capi.lib().bppp_u64_verify_batch_sec1(self._ctx, label, len(label), n, commitments33.ctypes.data,
                                                            proofs525.ctypes.data, accept.ctypes.data, status.ctypes.data))
         return accept, status
+
+    def verify_batch_rlc_sec1(self, commitments33, proofs525, label: bytes, seed: bytes) -> Tuple[np.ndarray, np.ndarray]:
+        """verify_batch_sec1 in the RLC mode (bppp_u64_verify_batch_rlc_sec1): the wire form decompressed on the device in front of
+        verify_batch_rlc's pipeline; results equal verify_batch_rlc on the expanded input with the same seed."""
+        if len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        commitments33 = _as_u8(commitments33, (-1, 33))
+        n = commitments33.shape[0]
+        proofs525 = _as_u8(proofs525, (n, 525))
+        accept, status = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32)
+        _capi.check(_capi.symbol("bppp_u64_verify_batch_rlc_sec1")(self._ctx, label, len(label), n, commitments33.ctypes.data,
+                                                                   proofs525.ctypes.data, accept.ctypes.data, status.ctypes.data, bytes(seed)))
+        return accept, status
+
+    def verify_batch_rlc_sec1_device(self, label: bytes, n: int, d_commitments33: int, d_proofs525: int, d_accept: int, seed: bytes,
+                                     d_status: int = 0, d_reject_count: int = 0) -> None:
+        """verify_batch_rlc_device over the wire form resident on the device (raw device addresses); asynchronous on the context's
+        stream (bppp_u64_verify_batch_rlc_sec1_device)."""
+        if len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        _capi.check(_capi.symbol("bppp_u64_verify_batch_rlc_sec1_device")(self._ctx, label, len(label), n, d_commitments33, d_proofs525,
+                                                                          d_accept, d_status or None, d_reject_count or None, bytes(seed)))
 
     # ---- prove (u64_proof.rs:57-82)
     def prove(self, x: int, s: bytes, label: bytes, rnd: bytes) -> bytes:

@@ -227,3 +227,61 @@ def generic_sec1_to_json(proof33: bytes, rounds: int, nl: int, nn: int, reciproc
 
 def json_to_generic_sec1(text: str) -> bytes:
     return doc_to_sec1_proof(json.loads(text))
+
+
+# ---------------------------------------------------------------- batches: what the device does to wire-form input
+# The *_sec1 entry points expand their input on the device before the 64-byte pipeline runs (csrc/verify_core.h:
+# sec1_decompress_to_xy64).  These helpers are that expansion and its inverse on the host, over whole batches, so that a wire-form call
+# can be compared with the 64-byte call on `expand(...)` of the same bytes.  Unlike decompress_point they never raise: a point k256's
+# from_bytes would refuse (a tag other than 02 / 03 on a non-zero encoding, x >= p, x^3 + 7 not a square -- `02 || 0` among them)
+# becomes the off-curve point (1, 0), which the verifiers flag BPPP_ST_BAD_ENCODING; 33 zero bytes are the identity, 64 zero bytes.
+OFF_CURVE_XY64 = (1).to_bytes(32, "big") + bytes(32)
+
+
+def decodable(sec1: bytes) -> bool:
+    """Whether k256's `AffinePoint::from_bytes` accepts these 33 bytes (the identity's 33 zero bytes included)."""
+    try:
+        decompress_point(bytes(sec1))
+    except ValueError:
+        return False
+    return True
+
+
+def expand_point(sec1: bytes) -> bytes:
+    """33 bytes -> the 64 bytes the device expands them to: the point, the identity, or the off-curve (1, 0) for an undecodable one."""
+    try:
+        return decompress_point(bytes(sec1))
+    except ValueError:
+        return OFF_CURVE_XY64
+
+
+def _rows(buf, row_bytes: int):
+    import numpy as np
+    arr = np.frombuffer(bytes(buf), dtype=np.uint8) if isinstance(buf, (bytes, bytearray)) else np.ascontiguousarray(buf, dtype=np.uint8)
+    if arr.size % row_bytes:
+        raise ValueError(f"{arr.size} bytes are not rows of {row_bytes}")
+    return arr.reshape(-1, row_bytes)
+
+
+def expand(rows33, n_points: int, n_scalars: int = 0):
+    """A batch in the wire form -- rows of n_points 33-byte points followed by n_scalars 32-byte scalars (a proof: proof_points(kind,
+    rounds) and nl + nn; commitments: 1, or k for a circuit; a WNLA r / x array: rounds) -- to the 64-byte form, uint8
+    [n, 64 n_points + 32 n_scalars], as the device expands it (expand_point per point, scalars copied)."""
+    import numpy as np
+    src = _rows(rows33, 33 * n_points + 32 * n_scalars)
+    out = np.zeros((src.shape[0], 64 * n_points + 32 * n_scalars), np.uint8)
+    out[:, 64 * n_points:] = src[:, 33 * n_points:]
+    for i in range(src.shape[0]):
+        row = src[i].tobytes()
+        out[i, :64 * n_points] = np.frombuffer(b"".join(expand_point(row[33 * j:33 * j + 33]) for j in range(n_points)), np.uint8)
+    return out
+
+
+def pack(rows64, n_points: int, n_scalars: int = 0):
+    """Inverse of expand for well-formed input: a batch in the 64-byte form to the wire form, uint8 [n, 33 n_points + 32 n_scalars]."""
+    import numpy as np
+    src = _rows(rows64, 64 * n_points + 32 * n_scalars)
+    out = np.zeros((src.shape[0], 33 * n_points + 32 * n_scalars), np.uint8)
+    for i in range(src.shape[0]):
+        out[i] = np.frombuffer(generic_abi_to_sec1(src[i].tobytes(), n_points), np.uint8)
+    return out

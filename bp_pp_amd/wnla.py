@@ -240,6 +240,34 @@ class WeightNormLinearArgument:
                                                                    d_proof_r33, d_proof_x33, d_proof_l, nl, d_proof_n, nn, d_accept,
                                                                    d_status or None))
 
+    def verify_batch_rlc_sec1(self, label: bytes, commitments33, c, rho, mu, proof_r33, proof_x33, proof_l, proof_n, seed: bytes):
+        """verify_batch_sec1 in the RLC mode (bppp_wnla_verify_batch_rlc_sec1): results equal verify_batch_rlc on the expanded input
+        with the same seed.  -> (accept, status)"""
+        seed = _rlc_seed(seed)
+        fn = _capi.symbol("bppp_wnla_verify_batch_rlc_sec1")
+        commitments33 = _u8(commitments33, (-1, 33))
+        B = commitments33.shape[0]
+        c = _u8(c, (B, self.nh, 32))
+        rho, mu = _u8(rho, (B, 32)), _u8(mu, (B, 32))
+        proof_r33, proof_x33 = _u8(proof_r33, (B, -1, 33)), _u8(proof_x33, (B, -1, 33))
+        if proof_r33.shape[1] != proof_x33.shape[1]:
+            return np.zeros(B, np.uint8), np.zeros(B, np.int32)          # wnla.rs:76-78
+        proof_l, proof_n = _u8(proof_l, (B, -1, 32)), _u8(proof_n, (B, -1, 32))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(fn(self._ctx, label, len(label), B, commitments33.ctypes.data, c.ctypes.data, rho.ctypes.data, mu.ctypes.data,
+                       proof_r33.shape[1], proof_r33.ctypes.data, proof_x33.ctypes.data, proof_l.ctypes.data, proof_l.shape[1],
+                       proof_n.ctypes.data, proof_n.shape[1], acc.ctypes.data, st.ctypes.data, seed))
+        return acc, st
+
+    def verify_batch_rlc_sec1_device(self, label: bytes, n: int, d_commitments33: int, d_c: int, d_rho: int, d_mu: int, rounds: int,
+                                     d_proof_r33: int, d_proof_x33: int, d_proof_l: int, nl: int, d_proof_n: int, nn: int, d_accept: int,
+                                     d_status: int, seed: bytes) -> None:
+        """verify_batch_rlc_device over 33-byte points (raw device pointers; d_status 0 = none), asynchronous on the context's stream."""
+        seed = _rlc_seed(seed)
+        _capi.check(_capi.symbol("bppp_wnla_verify_batch_rlc_sec1_device")(self._ctx, label, len(label), n, d_commitments33, d_c, d_rho, d_mu,
+                                                                           rounds, d_proof_r33, d_proof_x33, d_proof_l, nl, d_proof_n, nn,
+                                                                           d_accept, d_status or None, seed))
+
     def prove_batch_sec1(self, label: bytes, commitments33, c, rho, mu, l, n):
         """prove_batch with 33-byte points in and out: commitments [B, 33] -> (proof_r [B, rounds, 33], proof_x, proof_l, proof_n,
         status); an undecodable commitment gives BPPP_ST_BAD_ENCODING and a zeroed proof."""
@@ -373,6 +401,46 @@ class ReciprocalRangeProofProtocol:
         """verify_batch_device over 33-byte points (raw device addresses); asynchronous on the context's stream."""
         _capi.check(_capi.lib().bppp_reciprocal_verify_batch_sec1_device(self._w._ctx, label, len(label), n, self.dim_nd, self.dim_np,
                                                                          d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status))
+
+    def verify_batch_rlc_sec1(self, label: bytes, commitments33, proofs33, rounds: int, nl: int, nn: int, seed: bytes):
+        """verify_batch_sec1 in the RLC mode (bppp_reciprocal_verify_batch_rlc_sec1): results equal verify_batch_rlc on the expanded
+        input with the same seed.  -> (accept, status)"""
+        seed = _rlc_seed(seed)
+        fn = _capi.symbol("bppp_reciprocal_verify_batch_rlc_sec1")
+        commitments33 = _u8(commitments33, (-1, 33))
+        B = commitments33.shape[0]
+        proofs33 = _u8(proofs33, (B, 33 * (5 + 2 * rounds) + 32 * (nl + nn)))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(fn(self._w._ctx, label, len(label), B, self.dim_nd, self.dim_np, commitments33.ctypes.data, proofs33.ctypes.data,
+                       rounds, nl, nn, acc.ctypes.data, st.ctypes.data, seed))
+        return acc, st
+
+    def verify_batch_rlc_sec1_device(self, label: bytes, n: int, d_commitments33: int, d_proofs33: int, rounds: int, nl: int, nn: int,
+                                     d_accept: int, d_status: int, seed: bytes) -> None:
+        """verify_batch_rlc_device over 33-byte points (raw device addresses); asynchronous on the context's stream."""
+        seed = _rlc_seed(seed)
+        _capi.check(_capi.symbol("bppp_reciprocal_verify_batch_rlc_sec1_device")(self._w._ctx, label, len(label), n, self.dim_nd, self.dim_np,
+                                                                                 d_commitments33, d_proofs33, rounds, nl, nn, d_accept,
+                                                                                 d_status, seed))
+
+    def verify_one_sec1(self, commitment33: bytes, proof33: bytes, rounds: int, nl: int, nn: int, transcript):
+        """verify_one over a wire row (33-byte commitment, proof of 33 (5 + 2 rounds) + 32 (nl + nn) bytes:
+        bppp_reciprocal_verify_one_sec1[_transcript]); the row joins the wire-form front end of its shape.  -> (accept, status)"""
+        import ctypes as C
+        commitment33, proof33 = bytes(commitment33), bytes(proof33)
+        want = 33 * (5 + 2 * rounds) + 32 * (nl + nn)      # what the C side reads from the proof pointer (include/bppp.h)
+        if len(commitment33) != 33 or len(proof33) != want:
+            raise ValueError(f"commitment is 33 bytes and this shape's wire proof {want} bytes (got {len(commitment33)}, {len(proof33)})")
+        acc, st = C.c_uint8(0), C.c_int32(0)
+        if isinstance(transcript, (bytes, bytearray)):
+            _capi.check(_capi.symbol("bppp_reciprocal_verify_one_sec1")(self._w._ctx, bytes(transcript), len(transcript), self.dim_nd,
+                                                                        self.dim_np, commitment33, proof33, rounds, nl, nn, C.byref(acc),
+                                                                        C.byref(st)))
+        else:
+            _capi.check(_capi.symbol("bppp_reciprocal_verify_one_sec1_transcript")(self._w._ctx, transcript._buf, self.dim_nd, self.dim_np,
+                                                                                   commitment33, proof33, rounds, nl, nn, C.byref(acc),
+                                                                                   C.byref(st)))
+        return bool(acc.value), int(st.value)
 
     def prove_batch_sec1(self, label: bytes, commitments33, x, s, digits, m, rnd):
         """prove_batch with 33-byte points in and out: commitments [B, 33] -> (proofs [B, 33 (5 + 2 rounds) + 32 (nl + nn)], status,
@@ -636,6 +704,27 @@ class ArithmeticCircuit:
         """verify_batch_device over 33-byte points (raw device pointers), asynchronous on the context's stream."""
         _capi.check(_capi.lib().bppp_circuit_verify_batch_sec1_device(self._w._ctx, self._circuit, label, len(label), n, d_commitments33,
                                                                       d_proofs33, rounds, nl, nn, d_accept, d_status or None))
+
+    def verify_batch_rlc_sec1(self, label: bytes, commitments33, proofs33, rounds: int, nl: int, nn: int, seed: bytes):
+        """verify_batch_sec1 in the RLC mode (bppp_circuit_verify_batch_rlc_sec1): results equal verify_batch_rlc on the expanded input
+        with the same seed.  -> (accept, status)"""
+        seed = _rlc_seed(seed)
+        fn = _capi.symbol("bppp_circuit_verify_batch_rlc_sec1")
+        commitments33 = _u8(commitments33, (-1, self.k, 33))
+        B = commitments33.shape[0]
+        proofs33 = _u8(proofs33, (B, 33 * (4 + 2 * rounds) + 32 * (nl + nn)))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(fn(self._w._ctx, self._circuit, label, len(label), B, commitments33.ctypes.data, proofs33.ctypes.data, rounds, nl, nn,
+                       acc.ctypes.data, st.ctypes.data, seed))
+        return acc, st
+
+    def verify_batch_rlc_sec1_device(self, label: bytes, n: int, d_commitments33: int, d_proofs33: int, rounds: int, nl: int, nn: int,
+                                     d_accept: int, d_status: int, seed: bytes) -> None:
+        """verify_batch_rlc_device over 33-byte points (raw device pointers; d_status 0 = none), asynchronous on the context's stream."""
+        seed = _rlc_seed(seed)
+        _capi.check(_capi.symbol("bppp_circuit_verify_batch_rlc_sec1_device")(self._w._ctx, self._circuit, label, len(label), n,
+                                                                              d_commitments33, d_proofs33, rounds, nl, nn, d_accept,
+                                                                              d_status or None, seed))
 
     def prove_batch_sec1(self, label: bytes, v_commitments33, v, s_v, w_l, w_r, w_o, rnd):
         """prove_batch with 33-byte points in and out: v_commitments [B, k, 33] -> (proofs [B, 33 (4 + 2 rounds) + 32 (nl + nn)],

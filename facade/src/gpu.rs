@@ -116,6 +116,42 @@ impl U64RangeProofProtocolGpu {
         Ok(get_u64_proof(&proof).expect("library emitted an invalid proof"))
     }
 
+    // ------------------------------------------------------------------------------------------------------------------------
+    // The wire form: what a caller of the crate holds after `SerializableProof::from(&proof)` and serialization -- every point the
+    // 33 bytes of `AffinePoint::to_bytes()` (the identity 33 zero bytes; serde's one-byte "00" widened by the caller), every scalar
+    // 32 bytes: 525 bytes per u64 proof, 33 per commitment.  The points are decompressed on the GPU; a point `from_bytes` would
+    // refuse makes the answer `false` (status BPPP_ST_BAD_ENCODING), as the deserialization error would have on the CPU.
+
+    /// `verify(&self, v, proof, t)` for ONE proof held as wire bytes, from any number of threads (bppp_u64_verify_one_sec1_transcript):
+    /// joins the library's wire-form front end.  `t` is advanced as the reference's verify leaves it, and left untouched when a point
+    /// does not decode.
+    pub fn verify_sec1(&self, v33: &[u8; 33], proof525: &[u8; 525], t: &mut Transcript) -> Result<bool, GpuError> {
+        let mut st8 = tstate::to_bytes(t);
+        let (mut acc, mut st) = (0u8, 0i32);
+        check(unsafe { bppp_u64_verify_one_sec1_transcript(self.ctx, st8.as_mut_ptr(), v33.as_ptr(), proof525.as_ptr(), &mut acc, &mut st) })?;
+        if st & BPPP_ST_DEGENERATE != 0 {
+            return Err(GpuError::ReferenceWouldPanic { index: 0 });
+        }
+        *t = tstate::from_bytes(&st8);
+        Ok(acc == 1)
+    }
+
+    /// n x `verify(v, proof, &mut Transcript::new(label))` over wire bytes (vs33: n x 33, proofs525: n x 525) in the library's
+    /// random-linear-combination mode (bppp_u64_verify_batch_rlc_sec1): the fastest batch verifier on the form callers hold.  `seed`:
+    /// 32 bytes of OS randomness drawn AFTER the proofs are fixed; accept bits stay per proof (include/bppp.h).
+    pub fn verify_rlc_sec1(&self, label: &'static [u8], vs33: &[u8], proofs525: &[u8], seed: &[u8; 32]) -> Result<Vec<bool>, GpuError> {
+        assert!(vs33.len() % 33 == 0 && proofs525.len() == vs33.len() / 33 * U64_PROOF_SEC1_BYTES);
+        let n = vs33.len() / 33;
+        let (mut acc, mut st) = (vec![0u8; n], vec![0i32; n]);
+        check(unsafe {
+            bppp_u64_verify_batch_rlc_sec1(self.ctx, label.as_ptr(), label.len(), n, vs33.as_ptr(), proofs525.as_ptr(), acc.as_mut_ptr(), st.as_mut_ptr(), seed.as_ptr())
+        })?;
+        if let Some(i) = st.iter().position(|s| s & BPPP_ST_DEGENERATE != 0) {
+            return Err(GpuError::ReferenceWouldPanic { index: i });
+        }
+        Ok(acc.iter().map(|a| *a == 1).collect())
+    }
+
     /// `U64RangeProofProtocol::commit_value(&self, x, s) -> ProjectivePoint` (u64_proof.rs:37-39).
     pub fn commit_value(&self, x: u64, s: &Scalar) -> ProjectivePoint {
         self.commit_value_batch(&[x], std::slice::from_ref(s)).expect("bppp: GPU commit failed").remove(0)

@@ -224,6 +224,19 @@ BPPP_API int bppp_u64_verify_batch_sec1(bppp_ctx* ctx, const uint8_t* label, siz
 BPPP_API int bppp_u64_verify_batch_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
                                                const void* d_commitments, const void* d_proofs, void* d_accept, void* d_status,
                                                void* d_trace, void* d_reject_count);
+/* The random-linear-combination mode (bppp_u64_verify_batch_rlc[_device] above) over the wire form: the arguments of
+ * bppp_u64_verify_batch_sec1[_device] (no trace), then the seed (NULL: BPPP_ERR_INVALID_ARG); the device form also takes
+ * d_reject_count.  The points are expanded on the device, on the context's stream, in front of the RLC pipeline: return code, accept
+ * bits and statuses are exactly those of the 64-byte RLC call on the expanded input with the same seed, and "last_rlc_superchunk",
+ * "last_rlc_chunk" and "rlc_reject_ppm" behave as for it.  An undecodable point flags its proof BPPP_ST_BAD_ENCODING; a flagged proof
+ * is never accepted, has weight zero in the bucket stage and sends its chunk to the exact check, so it enters no weighted sum and
+ * cannot change the verdict of another proof of its chunk or superchunk. */
+BPPP_API int bppp_u64_verify_batch_rlc_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                            const uint8_t* commitments /* n x 33 */, const uint8_t* proofs /* n x 525 */,
+                                            uint8_t* accept /* n */, int32_t* status /* n or NULL */, const uint8_t seed[32]);
+BPPP_API int bppp_u64_verify_batch_rlc_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                                   const void* d_commitments, const void* d_proofs, void* d_accept, void* d_status,
+                                                   void* d_reject_count, const uint8_t seed[32]);
 
 /* U64RangeProofProtocol::prove (u64_proof.rs:57-82) for n independent values, fresh `Transcript::new(label)` per proof.
  * rnd holds, per proof, the 52 scalars the reference draws with `Scalar::generate_biased(rng)` in its draw order
@@ -284,9 +297,27 @@ BPPP_API int bppp_reciprocal_verify_one(bppp_ctx* ctx, const uint8_t* label, siz
 BPPP_API int bppp_reciprocal_verify_one_transcript(bppp_ctx* ctx, uint8_t state[203], size_t dim_nd, size_t dim_np, const uint8_t commitment[64],
                                                    const uint8_t* proof, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
                                                    int32_t* status /* or NULL */);
+/* The verifying single-proof calls over a WIRE row (bppp_u64_verify_batch_sec1: 33-byte commitment, 525-byte proof; reciprocal: 33-byte
+ * commitment, proof of 33 (5 + 2 rounds) + 32 (nl + nn) bytes).  Semantics word for word as above: the answer is the batched wire-form
+ * entry point's for that row, an undecodable row flags only itself (BPPP_ST_BAD_ENCODING, its transcript untouched), shared failures
+ * are shared, bppp_ctx_destroy drains.  Wire rows and 64-byte rows may be submitted to the same context at the same time: each row format
+ * has its own front end (its own staging, dispatchers and `coalesce_lanes` contexts), so a sealed batch holds rows of one format and the
+ * points of a wire batch are decompressed on the device by one launch.  HOW THE FORMATS COUNT: the u64 calls have one front end per
+ * format, outside the limit; of the reciprocal calls every (shape, row format) pair in use is one of the context's FOUR generic front
+ * ends -- a shape served in both formats takes two of the four, and a fifth pair is refused with BPPP_ERR_INVALID_ARG. */
+BPPP_API int bppp_u64_verify_one_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, const uint8_t commitment33[33],
+                                      const uint8_t proof525[525], uint8_t* accept, int32_t* status /* or NULL */);
+BPPP_API int bppp_u64_verify_one_sec1_transcript(bppp_ctx* ctx, uint8_t state[203], const uint8_t commitment33[33], const uint8_t proof525[525],
+                                                 uint8_t* accept, int32_t* status /* or NULL */);
+BPPP_API int bppp_reciprocal_verify_one_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t dim_nd, size_t dim_np,
+                                             const uint8_t commitment33[33], const uint8_t* proof33, size_t rounds, size_t nl, size_t nn,
+                                             uint8_t* accept, int32_t* status /* or NULL */);
+BPPP_API int bppp_reciprocal_verify_one_sec1_transcript(bppp_ctx* ctx, uint8_t state[203], size_t dim_nd, size_t dim_np,
+                                                        const uint8_t commitment33[33], const uint8_t* proof33, size_t rounds, size_t nl,
+                                                        size_t nn, uint8_t* accept, int32_t* status /* or NULL */);
 /* Counters of the front end since it was created: out = {requests, batches, largest batch, batches sealed full, batches sealed by the
  * deadline, microseconds its dispatchers spent inside batched calls, microseconds they waited for callers' row copies, 0}; which = 0
- * verify, 1 prove.  All zero before the first call. */
+ * verify, 1 prove, 2 verify over wire rows (the u64 front ends).  All zero before the first call. */
 BPPP_API int bppp_ctx_get_coalesce_stats(bppp_ctx* ctx, int which, uint64_t out[8]);
 
 /* U64RangeProofProtocol::commit_value (u64_proof.rs:37-39): out[i] = x[i]*g + s[i]*h_vec[0], host pointers. */
@@ -678,6 +709,39 @@ BPPP_API int bppp_circuit_verify_batch_rlc(bppp_ctx* ctx, const bppp_circuit* ci
 BPPP_API int bppp_circuit_verify_batch_rlc_device(bppp_ctx* ctx, const bppp_circuit* circuit, const uint8_t* label, size_t label_len,
                                                   size_t n, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
                                                   size_t nn, void* d_accept, void* d_status, const uint8_t seed[32]);
+
+/* The RLC mode of the three generic verifiers over the WIRE form: the arguments of bppp_{reciprocal,circuit,wnla}_verify_batch_sec1[_device],
+ * then the seed (NULL: BPPP_ERR_INVALID_ARG).  The expansion of the exact wire-form entry points (one launch on the context's stream)
+ * runs in front of the 64-byte RLC twin's pipeline: return code, accept bits and statuses are exactly the twin's for the expanded input
+ * and the same seed -- so, for valid proofs, also the exact wire-form call's -- and so are its rules: the reciprocal (16, 16) u64 shape
+ * takes bppp_u64_verify_batch_rlc_sec1's path; a circuit or WNLA call of n < 8 runs the exact final sum and reports "last_rlc_chunk" =
+ * 0.  An instance with an undecodable point is flagged BPPP_ST_BAD_ENCODING by phase 1, gets weight zero in the bucket stage and makes
+ * its chunk of 8 unusable (re-checked exactly, instance by instance): it is in no weighted sum and changes nobody else's verdict.  The
+ * device forms are asynchronous on the context's stream; the host forms stage in the context's grow-only buffers as their exact twins do. */
+BPPP_API int bppp_reciprocal_verify_batch_rlc_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
+                                                   size_t dim_np, const uint8_t* commitments33 /* n x 33 */, const uint8_t* proofs33, size_t rounds,
+                                                   size_t nl, size_t nn, uint8_t* accept /* n */, int32_t* status /* n or NULL */,
+                                                   const uint8_t seed[32]);
+BPPP_API int bppp_reciprocal_verify_batch_rlc_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
+                                                          size_t dim_np, const void* d_commitments33, const void* d_proofs33, size_t rounds,
+                                                          size_t nl, size_t nn, void* d_accept, void* d_status, const uint8_t seed[32]);
+BPPP_API int bppp_circuit_verify_batch_rlc_sec1(bppp_ctx* ctx, const bppp_circuit* circuit, const uint8_t* label, size_t label_len, size_t n,
+                                                const uint8_t* commitments33 /* n x k x 33 */, const uint8_t* proofs33, size_t rounds, size_t nl,
+                                                size_t nn, uint8_t* accept /* n */, int32_t* status /* n or NULL */, const uint8_t seed[32]);
+BPPP_API int bppp_circuit_verify_batch_rlc_sec1_device(bppp_ctx* ctx, const bppp_circuit* circuit, const uint8_t* label, size_t label_len,
+                                                       size_t n, const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl,
+                                                       size_t nn, void* d_accept, void* d_status, const uint8_t seed[32]);
+BPPP_API int bppp_wnla_verify_batch_rlc_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                             const uint8_t* commitments33 /* n x 33 */, const uint8_t* c /* n x nh x 32 */,
+                                             const uint8_t* rho /* n x 32 */, const uint8_t* mu /* n x 32 */, size_t rounds,
+                                             const uint8_t* proof_r33 /* n x rounds x 33 */, const uint8_t* proof_x33 /* n x rounds x 33 */,
+                                             const uint8_t* proof_l /* n x nl x 32 */, size_t nl, const uint8_t* proof_n /* n x nn x 32 */,
+                                             size_t nn, uint8_t* accept /* n */, int32_t* status /* n or NULL */, const uint8_t seed[32]);
+BPPP_API int bppp_wnla_verify_batch_rlc_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                                    const void* d_commitments33, const void* d_c, const void* d_rho, const void* d_mu,
+                                                    size_t rounds, const void* d_proof_r33, const void* d_proof_x33, const void* d_proof_l,
+                                                    size_t nl, const void* d_proof_n, size_t nn, void* d_accept, void* d_status,
+                                                    const uint8_t seed[32]);
 
 /* ---- Seeded provers: the prover's random scalars drawn on the device from a ChaCha20 seed ----
  * The `rnd` forms above take the prover's random scalars from the caller (52 per u64 proof, 20 + 2 dim_nd per reciprocal instance,
