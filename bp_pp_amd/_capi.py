@@ -9,7 +9,7 @@ from . import _build
 
 OK = 0
 ERR_NO_DEVICE, ERR_INVALID_ARG, ERR_HIP, ERR_ENCODING, ERR_NOMEM, ERR_RCCL, ERR_CLOSED = -1, -2, -3, -4, -5, -6, -7
-ST_BAD_ENCODING, ST_DEGENERATE = 1, 2
+ST_BAD_ENCODING, ST_DEGENERATE, ST_OUT_OF_RANGE = 1, 2, 4
 POINT_BYTES, SCALAR_BYTES, U64_PROOF_BYTES, U64_TRACE_BYTES = 64, 32, 928, 704
 
 # every symbol include/bppp.h declares (tests/test_capi_symbols.py checks the header against this list and the .so)
@@ -47,6 +47,12 @@ EXPORTS = [
     "bppp_draw_scalars", "bppp_draw_scalars_device", "bppp_u64_prove_batch_seeded", "bppp_u64_prove_batch_seeded_device",
     "bppp_u64_prove_batch_seeded_sharded", "bppp_reciprocal_prove_batch_seeded", "bppp_circuit_prove_batch_seeded",
 ]
+# the generic proofs' wire form and the seeded provers, as lib() binds them (the two runs at the end of the list above)
+WIRE_GENERIC_EXPORTS, SEEDED_EXPORTS = EXPORTS[-16:-7], EXPORTS[-7:]
+# the reciprocal prover from integers (include/bppp.h: "Range proofs from integers at any width")
+VALUES_EXPORTS = ["bppp_reciprocal_prove_values_batch", "bppp_reciprocal_prove_values_batch_seeded",
+                  "bppp_reciprocal_prove_values_batch_device", "bppp_reciprocal_prove_values_batch_seeded_device"]
+EXPORTS += VALUES_EXPORTS
 
 # the entry points of the wire form's RLC mode and single-proof front end (a subset of EXPORTS)
 RLC_SEC1_EXPORTS = [name for name in EXPORTS if name.endswith(("_rlc_sec1", "_rlc_sec1_device")) or "_one_sec1" in name]
@@ -217,7 +223,7 @@ def lib():
         L.bppp_reciprocal_prove_batch_sec1.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bppp_circuit_prove_batch_sec1.argtypes = [vp, vp, u8p, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.bppp_wnla_prove_batch_sec1.argtypes = [vp, u8p, sz, sz, vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp]
-        for name in EXPORTS[-16:-7]:
+        for name in WIRE_GENERIC_EXPORTS:
             getattr(L, name).restype = i32
     # the wire form in RLC mode (the exact wire twins' argument lists and a 32-byte seed; the u64 device form has d_reject_count in
     # place of the trace) and in the single-proof front end (the 64-byte *_one lists over 33-byte rows)
@@ -246,7 +252,16 @@ def lib():
         L.bppp_u64_prove_batch_seeded_sharded.argtypes = [vp, u8p, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
         L.bppp_reciprocal_prove_batch_seeded.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, vp, vp, vp, u8p, u64, vp, vp]
         L.bppp_circuit_prove_batch_seeded.argtypes = [vp, vp, u8p, sz, sz, vp, vp, vp, vp, vp, vp, u8p, u64, vp, vp]
-        for name in EXPORTS[-7:]:
+        for name in SEEDED_EXPORTS:
+            getattr(L, name).restype = i32
+    # the reciprocal prover from integers: x, s and rnd or (seed, stream_base) in, proofs and commitments out
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_reciprocal_prove_values_batch"):
+        u64 = C.c_uint64
+        L.bppp_reciprocal_prove_values_batch.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.bppp_reciprocal_prove_values_batch_seeded.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        L.bppp_reciprocal_prove_values_batch_device.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.bppp_reciprocal_prove_values_batch_seeded_device.argtypes = [vp, u8p, sz, sz, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        for name in VALUES_EXPORTS:
             getattr(L, name).restype = i32
     L.bppp_strerror.argtypes = [i32]
     L.bppp_strerror.restype = C.c_char_p

@@ -1362,32 +1362,71 @@ int bppp_circuit_prove_batch_transcript(bppp_ctx* c, const bppp_circuit* q, size
     return circuit_prove_impl(c, q, nullptr, 0, &tx, n, v_commitments, v, s_v, w_l, w_r, w_o, rnd, proofs, status);
 }
 
-// ReciprocalRangeProofProtocol::prove (reciprocal.rs:110-146) for runtime dim_nd / dim_np.
+// The reciprocal circuit's pattern for (dim_nd, dim_np) in device memory.  The first prove call of a shape on a context builds it on
+// the host, allocates and uploads it (a synchronous copy: the host vectors live on this frame); every later call finds it here, so no
+// prove call waits for its stream on account of the pattern, and the device-resident forms stay asynchronous.
+static int recip_pattern_get(bppp_ctx* c, size_t nd, size_t np, RecipPatternDev& out) {
+    for (const RecipPatternDev& rp : c->recip_patterns)
+        if (rp.nd == nd && rp.np == np) { out = rp; return BPPP_OK; }
+    RecipPattern P;
+    recip_pattern_build(P, nd, np);
+    const CircuitHostData& hd = P.hd;
+    RecipPatternDev rp;
+    std::memset(&rp, 0, sizeof rp);
+    rp.nd = nd; rp.np = np; rp.nw = P.dims[5];
+    size_t off = 0;
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes + 16); };
+    rp.cpl = take(hd.cpl.size() * 4); rp.rl = take(hd.rl.size() * 4); rp.vl = take(hd.vl.size() * 4); rp.cpm = take(hd.cpm.size() * 4);
+    rp.rm = take(hd.rm.size() * 4); rp.vm = take(hd.vm.size() * 4); rp.cmp = take(hd.colmap.size() * 4); rp.al = take(hd.al.size() * 4);
+    rp.am = take(hd.am.size() * 4); rp.il = take(P.inst_l.size() * 4); rp.im = take(P.inst_m.size() * 4); rp.part = take(P.parts.size() * 4);
+    std::vector<uint8_t> host(off, 0);
+    auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) std::memcpy(host.data() + o, src, bytes); };
+    put(rp.cpl, hd.cpl.data(), hd.cpl.size() * 4); put(rp.rl, hd.rl.data(), hd.rl.size() * 4); put(rp.vl, hd.vl.data(), hd.vl.size() * 4);
+    put(rp.cpm, hd.cpm.data(), hd.cpm.size() * 4); put(rp.rm, hd.rm.data(), hd.rm.size() * 4); put(rp.vm, hd.vm.data(), hd.vm.size() * 4);
+    put(rp.cmp, hd.colmap.data(), hd.colmap.size() * 4); put(rp.al, hd.al.data(), hd.al.size() * 4); put(rp.am, hd.am.data(), hd.am.size() * 4);
+    put(rp.il, P.inst_l.data(), P.inst_l.size() * 4); put(rp.im, P.inst_m.data(), P.inst_m.size() * 4);
+    put(rp.part, P.parts.data(), P.parts.size() * 4);
+    HIP_TRY(ctx_malloc(c, (void**)&rp.d, off));
+    const hipError_t e = hipMemcpy(rp.d, host.data(), off, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(rp.d); HIP_TRY(e); }
+    c->recip_patterns.push_back(rp);
+    out = rp;
+    return BPPP_OK;
+}
+
+// The forms of the prover FROM INTEGERS (bppp_reciprocal_prove_values_batch*): digits, multiplicities and the value commitment are
+// made on the device from x and s (recip_witness_core.h; recip_prove_core.h: RecipCommitWs), and the commitments go back to the caller.
+// device: x, s, rnd, proofs, commitments_out and status are DEVICE memory, read and written in place, and the call is asynchronous on
+// the context's stream.
+struct RecipValues { bool device; uint8_t* commitments_out; };
+
+// ReciprocalRangeProofProtocol::prove (reciprocal.rs:110-146) for runtime dim_nd / dim_np: the inputs placed in the call's blob (uploaded;
+// in the device-resident forms used where they are), then the launch chain, then the proofs back.
 static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, const HostTranscripts* tx, size_t n, size_t dim_nd, size_t dim_np,
                             const uint8_t* commitments, const uint8_t* x, const uint8_t* sblind, const uint8_t* digits, const uint8_t* m,
                             const uint8_t* rnd, uint8_t* proofs, int32_t* status, bool sec1 = false,
-                            const uint8_t* seed = nullptr, uint64_t stream_base = 0) {
+                            const uint8_t* seed = nullptr, uint64_t stream_base = 0, const RecipValues* values = nullptr) {
     // sec1 (bppp_reciprocal_prove_batch_sec1): commitments n x 33 in, proofs in the 33-byte form out (converted on the device)
-    if (!c || !label_ok(label, label_len) || !commitments || !x || !sblind || !digits || !m || (!rnd && !seed) || !proofs) return BPPP_ERR_INVALID_ARG;
+    if (!c || !label_ok(label, label_len) || !x || !sblind || (!rnd && !seed) || !proofs) return BPPP_ERR_INVALID_ARG;
+    if (values ? !values->commitments_out : (!commitments || !digits || !m)) return BPPP_ERR_INVALID_ARG;
     if (dim_nd == 0 || dim_np == 0 || dim_nd > (size_t)c->ng || dim_nd + 10 > (size_t)c->nh || dim_np > dim_nd + 1 || dim_nd > 4096)
         return BPPP_ERR_INVALID_ARG;
+    // from integers: only the shapes whose digits x determines, dim_np^dim_nd <= n
+    if (values && !recip_values_shape_ok(dim_nd, dim_np)) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    RecipPattern P;
-    recip_pattern_build(P, dim_nd, dim_np);
+    const bool device_io = values && values->device;
     const size_t NG = (size_t)c->ng, NH = (size_t)c->nh, nd = dim_nd, np = dim_np, nm = nd, nv = nd + 1, nl = nv, n_rnd = 20 + 2 * nd;
     // seeded (bppp_*_prove_batch_seeded): the draws are made on the device below instead of uploaded
     if (seed && !draw_args_ok(seed, stream_base, n, n_rnd)) return BPPP_ERR_INVALID_ARG;
+    RecipPatternDev pat;
+    { const int rc_p = recip_pattern_get(c, nd, np, pat); if (rc_p != BPPP_OK) return rc_p; }
     WnlaProveShape sh = {n, NH, NG, 0, 0, 0};
     wnla_proof_shape(NH, NG, sh.rounds, sh.nl_f, sh.nn_f);
+    const size_t proof_bytes = 64 * (5 + 2 * sh.rounds) + 32 * (sh.nl_f + sh.nn_f);
     size_t off = 0;
     auto take = [&](size_t bytes) { return take_bytes(off, bytes + 16); };
-    const CircuitHostData& hd = P.hd;
-    // circuit pattern
-    const size_t o_cpl = take(hd.cpl.size() * 4), o_rl = take(hd.rl.size() * 4), o_vl = take(hd.vl.size() * 4), o_cpm = take(hd.cpm.size() * 4),
-                 o_rm = take(hd.rm.size() * 4), o_vm = take(hd.vm.size() * 4), o_cmp = take(hd.colmap.size() * 4), o_al = take(hd.al.size() * 4),
-                 o_am = take(hd.am.size() * 4), o_il = take(P.inst_l.size() * 4), o_im = take(P.inst_m.size() * 4), o_part = take(P.parts.size() * 4);
-    // inputs
+    // inputs (from integers: digits, m and the commitments are written here by the witness and commitment kernels)
     const size_t o_com = take(n * 64), o_x = take(n * 32), o_s = take(n * 32), o_dig = take(n * nd * 32), o_m = take(n * np * 32),
                  o_rnd = take(n * n_rnd * 32);
     // reciprocal stage
@@ -1399,29 +1438,27 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     WnlaProveBufs o_w;
     wnla_prove_take_proof(o_w, off, sh, 16);
     wnla_prove_take_state(o_w, off, c, sh, 16);
+    // from integers: the witness kernel's status, and (host buffers) the proofs as they go back
+    const size_t o_wst = values ? take(n * 4) : 0, o_pout = (values && !device_io) ? take(n * proof_bytes) : 0;
     WnlaBlob blob;
-    { const int rc_b = blob.take(c, off); if (rc_b != BPPP_OK) return rc_b; }
-    uint8_t* d = blob.d;
+    if (device_io) { const int rc_b = ensure_blob(c, off); if (rc_b != BPPP_OK) return rc_b; }      // (no sync when the call returns)
+    else { const int rc_b = blob.take(c, off); if (rc_b != BPPP_OK) return rc_b; }
+    uint8_t* d = c->d_blob;
     hipStream_t s = c->stream;
     auto up = [&](size_t o, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(d + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess; };
-    HIP_TRY(up(o_cpl, hd.cpl.data(), hd.cpl.size() * 4)); HIP_TRY(up(o_rl, hd.rl.data(), hd.rl.size() * 4)); HIP_TRY(up(o_vl, hd.vl.data(), hd.vl.size() * 4));
-    HIP_TRY(up(o_cpm, hd.cpm.data(), hd.cpm.size() * 4)); HIP_TRY(up(o_rm, hd.rm.data(), hd.rm.size() * 4)); HIP_TRY(up(o_vm, hd.vm.data(), hd.vm.size() * 4));
-    HIP_TRY(up(o_cmp, hd.colmap.data(), hd.colmap.size() * 4)); HIP_TRY(up(o_al, hd.al.data(), hd.al.size() * 4)); HIP_TRY(up(o_am, hd.am.data(), hd.am.size() * 4));
-    HIP_TRY(up(o_il, P.inst_l.data(), P.inst_l.size() * 4)); HIP_TRY(up(o_im, P.inst_m.data(), P.inst_m.size() * 4));
-    HIP_TRY(up(o_part, P.parts.data(), P.parts.size() * 4));
     const size_t o_wout = align16(n * 33);
     const size_t wire_bytes = o_wout + n * wire_proof_bytes(5 + 2 * sh.rounds, sh.nl_f + sh.nn_f) + 16;
-    { const int rc_i = prover_points_in(c, sec1, commitments, d + o_com, n, 1, wire_bytes, s); if (rc_i != BPPP_OK) return rc_i; }
-    HIP_TRY(up(o_x, x, n * 32)); HIP_TRY(up(o_s, sblind, n * 32));
-    HIP_TRY(up(o_dig, digits, n * nd * 32)); HIP_TRY(up(o_m, m, n * np * 32));
+    if (!values) { const int rc_i = prover_points_in(c, sec1, commitments, d + o_com, n, 1, wire_bytes, s); if (rc_i != BPPP_OK) return rc_i; }
+    if (!device_io) { HIP_TRY(up(o_x, x, n * 32)); HIP_TRY(up(o_s, sblind, n * 32)); }
+    if (!values) { HIP_TRY(up(o_dig, digits, n * nd * 32)); HIP_TRY(up(o_m, m, n * np * 32)); }
     DrawWipe wipe = {seed ? d + o_rnd : nullptr, n * n_rnd * 32, s};
     if (seed) { const int rc_d = draw_enqueue(s, seed, stream_base, n, n_rnd, d + o_rnd); if (rc_d != BPPP_OK) return rc_d; }
-    else HIP_TRY(up(o_rnd, rnd, n * n_rnd * 32));
-    HIP_TRY(hipStreamSynchronize(s));                      // the pattern vectors live on this stack frame
+    else if (!device_io) HIP_TRY(up(o_rnd, rnd, n * n_rnd * 32));
     RecipProveWs r;
     std::memset(&r, 0, sizeof r);
     r.N = n; r.nd = (int)nd; r.np = (int)np; r.NG = c->ng; r.NH = c->nh; r.n_rnd = (int)n_rnd;
-    r.commitments = d + o_com; r.x = d + o_x; r.s = d + o_s; r.digits = d + o_dig; r.m = d + o_m; r.rnd = d + o_rnd;
+    r.commitments = d + o_com; r.x = device_io ? x : d + o_x; r.s = device_io ? sblind : d + o_s; r.digits = d + o_dig; r.m = d + o_m;
+    r.rnd = (device_io && !seed) ? rnd : d + o_rnd;
     r.status = (int32_t*)(d + o_st); r.tstate = (u32*)(d + o_ts); r.inst_vals = (u32*)(d + o_inst); r.scr = (u32*)(d + o_scr);
     r.msc = (u32*)(d + o_c.msc); r.pbuf = (u32*)(d + o_c.pb);      // (the circuit stage's: the two stages run one after the other)
     r.cp_v = d + o_cpv; r.cp_sv = d + o_cpsv; r.cp_wr = d + o_cpwr; r.cp_vpts = d + o_cpvp; r.proof_r = d + o_prr;
@@ -1435,12 +1472,12 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     std::memset(&p, 0, sizeof p);
     p.base = r.base; p.tio = r.tio; p.divergent_positions = r.divergent_positions;
     CircuitDev& cd = p.cd;
-    cd.nm = (int)nm; cd.no = (int)np; cd.k = 1; cd.nl = (int)nl; cd.nv = (int)nv; cd.nw = (int)P.dims[5]; cd.f_l = 1; cd.f_m = 0;
-    cd.colptr_l = (const int*)(d + o_cpl); cd.rows_l = (const int*)(d + o_rl); cd.vals_l = (const u32*)(d + o_vl);
-    cd.colptr_m = (const int*)(d + o_cpm); cd.rows_m = (const int*)(d + o_rm); cd.vals_m = (const u32*)(d + o_vm);
-    cd.colmap = (const int*)(d + o_cmp); cd.a_l = (const u32*)(d + o_al); cd.a_m = (const u32*)(d + o_am);
-    cd.inst_l = (const int*)(d + o_il); cd.inst_m = (const int*)(d + o_im); cd.inst_vals = r.inst_vals;
-    p.N = n; p.NG = c->ng; p.NH = c->nh; p.n_rnd = (int)(18 + nv + nm); p.rnd_stride = n_rnd * 32; p.part = (const int*)(d + o_part);
+    cd.nm = (int)nm; cd.no = (int)np; cd.k = 1; cd.nl = (int)nl; cd.nv = (int)nv; cd.nw = (int)pat.nw; cd.f_l = 1; cd.f_m = 0;
+    cd.colptr_l = (const int*)(pat.d + pat.cpl); cd.rows_l = (const int*)(pat.d + pat.rl); cd.vals_l = (const u32*)(pat.d + pat.vl);
+    cd.colptr_m = (const int*)(pat.d + pat.cpm); cd.rows_m = (const int*)(pat.d + pat.rm); cd.vals_m = (const u32*)(pat.d + pat.vm);
+    cd.colmap = (const int*)(pat.d + pat.cmp); cd.a_l = (const u32*)(pat.d + pat.al); cd.a_m = (const u32*)(pat.d + pat.am);
+    cd.inst_l = (const int*)(pat.d + pat.il); cd.inst_m = (const int*)(pat.d + pat.im); cd.inst_vals = r.inst_vals;
+    p.N = n; p.NG = c->ng; p.NH = c->nh; p.n_rnd = (int)(18 + nv + nm); p.rnd_stride = n_rnd * 32; p.part = (const int*)(pat.d + pat.part);
     p.transcript_preloaded = 1;
     p.v_pts = r.cp_vpts; p.v = r.cp_v; p.s_v = r.cp_sv; p.w_l = r.digits; p.w_r = r.cp_wr; p.w_o = r.m; p.rnd = r.rnd + 32;
     p.proof_head = d + o_head; p.status = r.status; p.tstate = r.tstate;
@@ -1450,14 +1487,57 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     rc = wnla_prove_fill_behind(c, w, sh, d, o_w, p);
     if (rc != BPPP_OK) return rc;
     const unsigned blocks = blocks_of(n);
+    if (values) {
+        // the witness and the value commitment: x alone in, what stage r1 reads out (x and s are secrets: the "ct_prover" table as below)
+        RecipWitnessWs ww;
+        std::memset(&ww, 0, sizeof ww);
+        recip_witness_shape(ww, nd, np);
+        ww.N = n; ww.x = r.x; ww.digits = d + o_dig; ww.m = d + o_m; ww.status = (int32_t*)(d + o_wst);
+        RecipCommitWs cw;
+        std::memset(&cw, 0, sizeof cw);
+        cw.N = n; cw.NG = c->ng; cw.x = r.x; cw.s = r.s; cw.status = ww.status; cw.msc = r.msc; cw.pbuf = r.pbuf; cw.out = d + o_com;
+        cw.fb = r.fb; cw.fb_ct = r.fb_ct; cw.ct = r.ct;
+        GLAUNCH(s, K_RPROVE_WITNESS, k_rprove_witness<<<blocks, BPPP_BLOCK, 0, s>>>(ww, cw));
+        GLAUNCH(s, K_RPROVE_COMMIT, {
+            k_rprove_commit<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(cw);
+            k_rprove_commit_store<<<blocks, BPPP_BLOCK, 0, s>>>(cw);
+        });
+        r.witness_status = ww.status;
+    }
     HIP_TRY(hipMemsetAsync(r.msc, 0, 3 * (size_t)c->nbases * 8 * n * 4, s));
-    k_rprove_stage_r1<<<blocks, BPPP_BLOCK, 0, s>>>(r);
-    k_rprove_msm<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r);
-    k_rprove_stage_r2<<<blocks, BPPP_BLOCK, 0, s>>>(r);
-    rc = circuit_prove_launch(c, p, s);
-    if (rc != BPPP_OK) return rc;
-    wnla_prove_launch(w, s);
+    int rc_l = BPPP_OK;
+    GLAUNCH(s, K_RPROVE_CHAIN, {
+        k_rprove_stage_r1<<<blocks, BPPP_BLOCK, 0, s>>>(r);
+        k_rprove_msm<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r);
+        k_rprove_stage_r2<<<blocks, BPPP_BLOCK, 0, s>>>(r);
+        rc_l = circuit_prove_launch(c, p, s);
+        if (rc_l == BPPP_OK) wnla_prove_launch(w, s);
+    });
+    if (rc_l != BPPP_OK) return rc_l;
     HIP_TRY(hipGetLastError());
+    if (values) {
+        // the proofs put together on the device (a flagged instance as zero bytes): into the caller's buffer, or the blob and one copy back
+        ProofAssembleWs a;
+        std::memset(&a, 0, sizeof a);
+        a.N = n; a.proof_bytes = proof_bytes; a.nseg = 6; a.status = p.status; a.out = device_io ? proofs : d + o_pout;
+        a.src[0] = p.proof_head; a.bytes[0] = 256;
+        a.src[1] = w.proof_r; a.bytes[1] = (u32)(sh.rounds * 64);
+        a.src[2] = w.proof_x; a.bytes[2] = (u32)(sh.rounds * 64);
+        a.src[3] = r.proof_r; a.bytes[3] = 64;
+        a.src[4] = w.proof_l; a.bytes[4] = (u32)(sh.nl_f * 32);
+        a.src[5] = w.proof_n; a.bytes[5] = (u32)(sh.nn_f * 32);
+        const size_t words = n * (proof_bytes / 4);
+        if ((words + 255) / 256 > 0xFFFFFFFFu) return BPPP_ERR_INVALID_ARG;
+        k_gprove_assemble<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(a);
+        HIP_TRY(hipGetLastError());
+        const hipMemcpyKind back = device_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (!device_io) HIP_TRY(hipMemcpyAsync(proofs, d + o_pout, n * proof_bytes, back, s));
+        HIP_TRY(hipMemcpyAsync(values->commitments_out, d + o_com, n * 64, back, s));
+        if (status) HIP_TRY(hipMemcpyAsync(status, p.status, n * 4, back, s));
+        HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
+        if (!device_io) HIP_TRY(hipStreamSynchronize(s));
+        return BPPP_OK;
+    }
     const ProveReturn ret = {proofs, status, tx, &txd, &wipe};
     return sec1 ? prove_return_sec1(p, w, r.proof_r, c->d_wire + o_wout, ret, s) : prove_return_64(p, w, r.proof_r, ret, s);
 }
@@ -1850,6 +1930,44 @@ int bppp_circuit_prove_batch_seeded(bppp_ctx* c, const bppp_circuit* q, const ui
     if (!seed) return BPPP_ERR_INVALID_ARG;
     return circuit_prove_impl(c, q, label, label_len, nullptr, n, v_commitments, v, s_v, w_l, w_r, w_o, nullptr, proofs, status, false,
                               seed, stream_base);
+}
+
+// ---- the reciprocal prover from integers: x and s in, commitments and proofs out (include/bppp.h: "Range proofs from integers")
+int bppp_reciprocal_prove_values_batch(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                       const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd, uint8_t* proofs, uint8_t* commitments,
+                                       int32_t* status) {
+    CtxLock lock_(c);
+    if (!rnd) return BPPP_ERR_INVALID_ARG;
+    const RecipValues v = {false, commitments};
+    return recip_prove_impl(c, label, label_len, nullptr, n, dim_nd, dim_np, nullptr, x, sblind, nullptr, nullptr, rnd, proofs, status, false,
+                            nullptr, 0, &v);
+}
+int bppp_reciprocal_prove_values_batch_seeded(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                              const uint8_t* x, const uint8_t* sblind, const uint8_t seed[32], uint64_t stream_base,
+                                              uint8_t* proofs, uint8_t* commitments, int32_t* status) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    const RecipValues v = {false, commitments};
+    return recip_prove_impl(c, label, label_len, nullptr, n, dim_nd, dim_np, nullptr, x, sblind, nullptr, nullptr, nullptr, proofs, status, false,
+                            seed, stream_base, &v);
+}
+int bppp_reciprocal_prove_values_batch_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
+                                              const void* d_x, const void* d_s, const void* d_rnd, void* d_proofs, void* d_commitments,
+                                              void* d_status) {
+    CtxLock lock_(c);
+    if (!d_rnd) return BPPP_ERR_INVALID_ARG;
+    const RecipValues v = {true, (uint8_t*)d_commitments};
+    return recip_prove_impl(c, label, label_len, nullptr, n, dim_nd, dim_np, nullptr, (const uint8_t*)d_x, (const uint8_t*)d_s, nullptr, nullptr,
+                            (const uint8_t*)d_rnd, (uint8_t*)d_proofs, (int32_t*)d_status, false, nullptr, 0, &v);
+}
+int bppp_reciprocal_prove_values_batch_seeded_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
+                                                     size_t dim_np, const void* d_x, const void* d_s, const uint8_t seed[32],
+                                                     uint64_t stream_base, void* d_proofs, void* d_commitments, void* d_status) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    const RecipValues v = {true, (uint8_t*)d_commitments};
+    return recip_prove_impl(c, label, label_len, nullptr, n, dim_nd, dim_np, nullptr, (const uint8_t*)d_x, (const uint8_t*)d_s, nullptr, nullptr,
+                            nullptr, (uint8_t*)d_proofs, (int32_t*)d_status, false, seed, stream_base, &v);
 }
 
 }  // extern "C"

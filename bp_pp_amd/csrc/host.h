@@ -40,6 +40,8 @@ enum KernelId {
     K_WNLA_RLC_LHS, K_WNLA_RLC_CHUNK, K_WNLA_RLC_CHECK, K_WNLA_TABLES,
     K_CIRCUIT_PHASE1, K_CIRCUIT_C0_FIXED, K_CIRCUIT_C0_VAR, K_CIRCUIT_C0_FINISH,      // generic ArithmeticCircuit verifier (then the K_WNLA_* stage)
     K_SHARED_INV,      // u64 verifier from 2^18 proofs: the launches that invert once for 8 / 16 proofs (and the join of C0's halves ahead of round 1)
+    // reciprocal prover from integers (bppp_reciprocal_prove_values_batch*): the witness kernel | the value commitment | everything behind them
+    K_RPROVE_WITNESS, K_RPROVE_COMMIT, K_RPROVE_CHAIN,
     K_COUNT
 };
 static const char* const kKernelNames[K_COUNT] = {
@@ -48,7 +50,8 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_prove_stage_*", "k_prove_msm", "k_prove_round_scalars", "k_prove_round_fold", "k_prove_round_next",
     "k_recip_phase1", "k_recip_c0_fixed", "k_recip_c0_var", "k_recip_c0_finish", "k_wnla_begin", "k_wnla_round", "k_wnla_final_scalars",
     "k_wnla_msm", "k_wnla_accept", "k_wnla_rlc_lhs", "k_wnla_rlc_chunk", "k_wnla_rlc_check", "k_wnla_tables",
-    "k_circuit_phase1", "k_circuit_c0_fixed", "k_circuit_c0_var", "k_circuit_c0_finish", "k_verify_shared_inv"};
+    "k_circuit_phase1", "k_circuit_c0_fixed", "k_circuit_c0_var", "k_circuit_c0_finish", "k_verify_shared_inv",
+    "k_rprove_witness", "k_rprove_commit", "k_rprove_chain"};
 
 static inline size_t align16(size_t x) { return (x + 15) / 16 * 16; }
 // a transcript label as the ABI takes it: a null pointer only with length 0, and no longer than merlin can frame (its length prefix is a
@@ -56,6 +59,14 @@ static inline size_t align16(size_t x) { return (x + 15) / 16 * 16; }
 static inline bool label_ok(const uint8_t* label, size_t label_len) { return (label || !label_len) && label_len <= 0xFFFFFFFFu; }
 
 struct TimedLaunch { int id; hipEvent_t a, b; };
+
+// The reciprocal prover's circuit pattern (recip_prove_core.h: RecipPattern) for one (dim_nd, dim_np) in device memory: built and uploaded
+// at the first prove call of the shape, kept until the context goes (bppp_generic.hip: recip_pattern_get).  Offsets into d.
+struct RecipPatternDev {
+    size_t nd, np, nw;
+    uint8_t* d;
+    size_t cpl, rl, vl, cpm, rm, vm, cmp, al, am, il, im, part;
+};
 
 struct bppp_ctx {
     std::recursive_mutex mu;   // every exported call on a context holds it: overlapping calls from several host threads are serialized
@@ -126,6 +137,7 @@ struct bppp_ctx {
     size_t blob_bytes = 0;
     uint8_t* d_txio = nullptr;   // transcripts in / out of a generic prover call
     size_t txio_bytes = 0;
+    std::vector<RecipPatternDev> recip_patterns;      // the reciprocal prover's circuit patterns, one per shape proved on this context
     int inject_alloc_fault = 0;  // testing aid ("inject_alloc_fault"): the k-th device allocation from now on fails
     uint8_t* d_gws = nullptr;    // workspace of bppp_reciprocal_verify_batch_device
     size_t gws_bytes = 0;

@@ -100,3 +100,32 @@ __global__ __launch_bounds__(BPPP_BLOCK) void k_rprove_stage_r2(RecipProveWs w) 
     size_t t = (size_t)blockIdx.x * BPPP_BLOCK + threadIdx.x;
     if (t < w.N) recip_prove_stage_r2(w, t);
 }
+// ---- the reciprocal prover from integers (recip_witness_core.h; recip_prove_core.h: RecipCommitWs, ProofAssembleWs)
+static_assert(RW_BAD_ENCODING == ST_BAD_ENCODING && RW_OUT_OF_RANGE == ST_OUT_OF_RANGE, "recip_witness_core.h names the status flags by value");
+// digits, multiplicities and status of every instance from its x, then the scalars of its value commitment: a lane per instance
+__global__ __launch_bounds__(BPPP_BLOCK) void k_rprove_witness(RecipWitnessWs w, RecipCommitWs cw) {
+    size_t t = (size_t)blockIdx.x * BPPP_BLOCK + threadIdx.x;
+    if (t >= w.N) return;
+    recip_witness(w, t);
+    recip_commit_scalars(cw, t);
+}
+__global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_rprove_commit(RecipCommitWs w) {
+    size_t g = (size_t)blockIdx.x * BPPP_FB_BLOCK + threadIdx.x;
+    size_t t = g / BPPP_FB_LANES;
+    int lane = (int)(g % BPPP_FB_LANES);
+    if (t >= w.N) return;
+    pt part;
+    FbRanges rg;
+    recip_commit_ranges(rg, w);
+    if (w.ct) fb_group_sum_ct<BPPP_FB_LANES>(part, w.fb_ct, t, lane, w.msc, rg);
+    else fb_group_sum(part, w.fb, t, lane, w.msc, rg);
+    if (lane == 0) ws_st_pt(w.pbuf, w.N, t, part);
+}
+__global__ __launch_bounds__(BPPP_BLOCK) void k_rprove_commit_store(RecipCommitWs w) {
+    size_t t = (size_t)blockIdx.x * BPPP_BLOCK + threadIdx.x;
+    if (t < w.N) recip_commit_store(w, t);
+}
+__global__ __launch_bounds__(256) void k_gprove_assemble(ProofAssembleWs w) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x, words = w.proof_bytes / 4;
+    if (g < w.N * words) proof_assemble_word(w, g / words, (u32)(g % words));
+}

@@ -220,6 +220,10 @@ __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_cprove_msm
 __global__ __launch_bounds__(BPPP_BLOCK) void k_rprove_stage_r1(bppp::RecipProveWs w);
 __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_rprove_msm(bppp::RecipProveWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_rprove_stage_r2(bppp::RecipProveWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_rprove_witness(bppp::RecipWitnessWs w, bppp::RecipCommitWs cw);
+__global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_rprove_commit(bppp::RecipCommitWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_rprove_commit_store(bppp::RecipCommitWs w);
+__global__ __launch_bounds__(256) void k_gprove_assemble(bppp::ProofAssembleWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_msm_scalars(bppp::MsmWs w);
 __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_msm(bppp::MsmWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_msm_store(bppp::MsmWs w);

@@ -9,6 +9,7 @@
 // 18 + (dim_nd + 1) + dim_nd.   Proof layout (the generic verifier's): c_l, c_r, c_o, c_s | r | x | reciprocal r | l | n.
 #pragma once
 #include "circuit_prove_core.h"
+#include "recip_witness_core.h"
 
 namespace bppp {
 
@@ -17,6 +18,7 @@ struct RecipProveWs {
     int nd, np, NG, NH, n_rnd;
     const uint8_t *commitments, *x, *s, *digits, *m, *rnd;   // C-ABI layouts (device): n x 64, n x 32, n x 32, n x nd x 32, n x np x 32, n x n_rnd x 32
     int32_t* status;
+    const int32_t* witness_status;   // null, or what the witness kernel (recip_witness_core.h) said of each instance: the status starts from it
     u32* tstate;
     u32* inst_vals;      // [(1 + np) * 8][N]: -e, -1/(e + j)
     u32* scr;            // [(nd + np) * 8][N] prefix products of the batched inversion
@@ -37,7 +39,7 @@ HD void recip_prove_ranges(FbRanges& rg, const RecipProveWs& w) { fb_ranges_one(
 HD void recip_prove_stage_r1(const RecipProveWs& w, size_t t) {
     const size_t N = w.N;
     const int nd = w.nd, np = w.np;
-    int32_t status = ST_OK;
+    int32_t status = w.witness_status ? w.witness_status[t] : ST_OK;
     apt V;
     bool ok = apt_from_xy64(V, w.commitments + 64 * t);
     if (!ok) { fe_set_u32(V.x, 0); fe_set_u32(V.y, 0); }
@@ -111,6 +113,74 @@ HD void recip_prove_stage_r2(const RecipProveWs& w, size_t t) {
     batch_to_affine<2>(A, P);
     apt_to_xy64(w.proof_r + 64 * t, A[0]);
     apt_to_xy64(w.cp_vpts + 64 * t, A[1]);
+}
+
+// ---- the prover from integers (bppp_reciprocal_prove_values_batch*): the witness kernel's second half and the value commitment.
+// commit_value(x, s) = x g + s h_vec[0] (reciprocal.rs:88-90) through the fixed-base tables: scalar slots 0 = x, 1 = s of msc, the sum
+// in pbuf, the affine point in out.  status holds what recip_witness wrote; a non-canonical s adds ST_BAD_ENCODING.  A flagged
+// instance commits to zero scalars and gets the identity (64 zero bytes).
+struct RecipCommitWs {
+    size_t N;
+    int NG;
+    const uint8_t *x, *s;      // n x 32 each
+    int32_t* status;
+    u32* msc;                  // [2 * 8][N]
+    u32* pbuf;                 // [30][N]
+    uint8_t* out;              // n x 64
+    FbTable fb;
+    FbTable fb_ct;             // "ct_prover": x and s are the caller's secrets
+    int ct;
+};
+HD void recip_commit_ranges(FbRanges& rg, const RecipCommitWs& w) {
+    rg.n = 2;
+    rg.slot[0] = 0; rg.base[0] = 0; rg.count[0] = 1;
+    rg.slot[1] = 1; rg.base[1] = 1 + w.NG; rg.count[1] = 1;
+}
+HD void recip_commit_scalars(const RecipCommitWs& w, size_t t) {
+    sc xs, ss;
+    bool ok = sc_from_be(xs, w.x + 32 * t);
+    ok &= sc_from_be(ss, w.s + 32 * t);
+    const int32_t status = w.status[t] | (ok ? ST_OK : ST_BAD_ENCODING);
+    const u32 keep = status == ST_OK ? ~0u : 0u;
+#pragma unroll
+    for (int i = 0; i < 8; i++) { xs.v[i] &= keep; ss.v[i] &= keep; }
+    ws_st8(w.msc, w.N, t, 0, xs.v);
+    ws_st8(w.msc, w.N, t, 1, ss.v);
+    w.status[t] = status;
+}
+HD void recip_commit_store(const RecipCommitWs& w, size_t t) {
+    pt total;
+    ws_ld_pt(total, w.pbuf, w.N, t);
+    apt a;
+    pt_to_affine(a, total);
+    if (w.status[t] != ST_OK) { fe_set_u32(a.x, 0); fe_set_u32(a.y, 0); }
+    apt_to_xy64(w.out + 64 * t, a);
+}
+// The proofs of a device-resident prove call, put together on the device: per instance up to 6 pieces (each n x bytes[i], 16-byte
+// aligned, a multiple of 4 bytes) one behind the other in out + t * proof_bytes; a flagged instance gets zero bytes.  One 4-byte word
+// per thread; `out` is the caller's and may have any alignment.
+struct ProofAssembleWs {
+    size_t N, proof_bytes;
+    int nseg;
+    const uint8_t* src[6];
+    u32 bytes[6];
+    const int32_t* status;
+    uint8_t* out;
+};
+HD void proof_assemble_word(const ProofAssembleWs& w, size_t t, u32 word) {
+    u32 off = 4 * word, v = 0;
+    bool found = false;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        if (i < w.nseg && !found) {
+            if (off < w.bytes[i]) { v = *(const u32*)(w.src[i] + t * (size_t)w.bytes[i] + off); found = true; }
+            else off -= w.bytes[i];
+        }
+    }
+    if (w.status[t] != ST_OK) v = 0;
+    uint8_t* o = w.out + t * w.proof_bytes + 4 * (size_t)word;
+    if ((((uintptr_t)o) & 3u) == 0) *(u32*)o = v;
+    else { o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)(v >> 16); o[3] = (uint8_t)(v >> 24); }
 }
 
 // Host side: the reciprocal circuit's sparsity pattern for (dim_nd, dim_np) as column-compressed data (make_circuit,

@@ -38,6 +38,7 @@ enum : int32_t {
     ST_OK = 0,
     ST_BAD_ENCODING = 1,     // coordinate >= p, point off curve, scalar >= n (k256 deserialisation would have failed)
     ST_DEGENERATE = 2,       // challenge >= n or a zero inverse: the reference panics on unwrap() here
+    ST_OUT_OF_RANGE = 4,     // the provers that build the witness from the integer: x >= dim_np^dim_nd (recip_witness_core.h)
 };
 
 #define BPPP_U64_PROOF_BYTES 928

@@ -289,6 +289,15 @@ class WeightNormLinearArgument:
         return pr, px, pl, pn, st
 
 
+GROUP_ORDER = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
+
+
+def values_shape_ok(dim_nd: int, dim_np: int) -> bool:
+    """The shapes the prove_values_* calls serve: an integer determines its dim_nd base-dim_np digits only while dim_np^dim_nd <= n,
+    the group order (recip_witness_core.h: recip_values_shape_ok is the library's copy of this rule)."""
+    return dim_nd >= 1 and dim_np >= 1 and dim_np ** dim_nd <= GROUP_ORDER
+
+
 class ReciprocalRangeProofProtocol:
     """Mirror of `range_proof::reciprocal::ReciprocalRangeProofProtocol` (reciprocal.rs:64-107) for runtime dim_nd / dim_np,
     verify only.  dim_nd = dim_np = 16 is what U64RangeProofProtocol specialises."""
@@ -354,6 +363,65 @@ class ReciprocalRangeProofProtocol:
                                                                    commitments.ctypes.data, x.ctypes.data, s.ctypes.data, digits.ctypes.data,
                                                                    m.ctypes.data, seed, stream_base, proofs.ctypes.data, st.ctypes.data))
         return proofs, st, (rounds.value, nl.value, nn.value)
+
+    # ---- from integers: the witness (digits, multiplicities) and the value commitment made on the device
+    def values_shape_ok(self) -> bool:
+        """Whether this shape's digits are determined by the integer, dim_np^dim_nd <= n: what the prove_values_* calls serve."""
+        return values_shape_ok(self.dim_nd, self.dim_np)
+
+    def _proof_shape(self):
+        import ctypes as C
+        rounds, nl, nn = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _capi.lib().bppp_wnla_proof_shape(self._w.nh, self._w.ng, C.byref(rounds), C.byref(nl), C.byref(nn))
+        return rounds.value, nl.value, nn.value
+
+    def proof_bytes(self) -> int:
+        rounds, nl, nn = self._proof_shape()
+        return 64 * (5 + 2 * rounds) + 32 * (nl + nn)
+
+    def prove_values_batch(self, label: bytes, x, s, rnd):
+        """`U64RangeProofProtocol::prove(x, s, ..)` at this protocol's width (include/bppp.h: bppp_reciprocal_prove_values_batch): x / s
+        [B, 32] big-endian integers and blindings, rnd [B, 20 + 2 dim_nd, 32] -> (proofs, commitments [B, 64], status,
+        (rounds, nl, nn)).  x >= dim_np^dim_nd gives ST_OUT_OF_RANGE, a zeroed proof and a zero commitment for that row."""
+        x, s = _u8(x, (-1, 32)), _u8(s, (-1, 32))
+        B = x.shape[0]
+        rnd = _u8(rnd, (B, 20 + 2 * self.dim_nd, 32))
+        shape = self._proof_shape()
+        proofs, com, st = np.zeros((B, self.proof_bytes()), np.uint8), np.zeros((B, 64), np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.symbol("bppp_reciprocal_prove_values_batch")(self._w._ctx, label, len(label), B, self.dim_nd, self.dim_np,
+                                                                       x.ctypes.data, s.ctypes.data, rnd.ctypes.data, proofs.ctypes.data,
+                                                                       com.ctypes.data, st.ctypes.data))
+        return proofs, com, st, shape
+
+    def prove_values_batch_seeded(self, label: bytes, x, s, seed: bytes, stream_base: int):
+        """prove_values_batch with instance i's draws taken from ChaCha20 stream stream_base + i of `seed` on the device, as
+        prove_batch_seeded takes them -> (proofs, commitments, status, (rounds, nl, nn))."""
+        from .range_proof import _seed_args
+        x, s = _u8(x, (-1, 32)), _u8(s, (-1, 32))
+        B = x.shape[0]
+        seed, stream_base = _seed_args(seed, stream_base, B)
+        shape = self._proof_shape()
+        proofs, com, st = np.zeros((B, self.proof_bytes()), np.uint8), np.zeros((B, 64), np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.symbol("bppp_reciprocal_prove_values_batch_seeded")(self._w._ctx, label, len(label), B, self.dim_nd, self.dim_np,
+                                                                              x.ctypes.data, s.ctypes.data, seed, stream_base,
+                                                                              proofs.ctypes.data, com.ctypes.data, st.ctypes.data))
+        return proofs, com, st, shape
+
+    def prove_values_batch_device(self, label: bytes, n: int, d_x: int, d_s: int, d_rnd: int, d_proofs: int, d_commitments: int,
+                                  d_status: int = 0) -> None:
+        """prove_values_batch over device buffers (raw device addresses, layouts as above; d_status 0 = none); asynchronous on the
+        context's stream."""
+        _capi.check(_capi.symbol("bppp_reciprocal_prove_values_batch_device")(self._w._ctx, label, len(label), n, self.dim_nd, self.dim_np,
+                                                                              d_x, d_s, d_rnd, d_proofs, d_commitments, d_status or None))
+
+    def prove_values_batch_seeded_device(self, label: bytes, n: int, d_x: int, d_s: int, seed: bytes, stream_base: int, d_proofs: int,
+                                         d_commitments: int, d_status: int = 0) -> None:
+        """prove_values_batch_seeded over device buffers (raw device addresses); asynchronous on the context's stream."""
+        from .range_proof import _seed_args
+        seed, stream_base = _seed_args(seed, stream_base, n)
+        _capi.check(_capi.symbol("bppp_reciprocal_prove_values_batch_seeded_device")(self._w._ctx, label, len(label), n, self.dim_nd,
+                                                                                     self.dim_np, d_x, d_s, seed, stream_base, d_proofs,
+                                                                                     d_commitments, d_status or None))
 
     def commit_value_batch(self, x, s):
         """reciprocal.rs:88-90 for a batch: x [B, 32], s [B, 32] (big-endian scalars) -> (points, status)."""

@@ -17,6 +17,8 @@ pub enum GpuError {
     /// the reference would have panicked on this proof (`unwrap()` of a challenge >= n or of a zero inverse:
     /// transcript.rs:13, circuit.rs:192,196, reciprocal.rs:181, util.rs:119)
     ReferenceWouldPanic { index: usize },
+    /// `prove_values`: the integer has more than dim_nd base-dim_np digits (BPPP_ST_OUT_OF_RANGE) -- no witness exists
+    ValueOutOfRange { index: usize },
 }
 
 fn check(rc: i32) -> Result<(), GpuError> {
@@ -251,6 +253,38 @@ impl U64RangeProofProtocolGpu {
             return Err(GpuError::ReferenceWouldPanic { index: i });
         }
         Ok((proofs.chunks(928).map(|b| get_u64_proof(b).expect("library emitted an invalid proof")).collect(),
+            coms.chunks(64).map(|b| get_point(b).expect("library emitted a point off the curve")).collect()))
+    }
+
+    /// The u64 protocol's `prove(x, s, ..)` at ANOTHER WIDTH over this object's generators (bppp_reciprocal_prove_values_batch):
+    /// n x `ReciprocalRangeProofProtocol::prove` (reciprocal.rs:110-146) with the witness of u64_proof.rs:84-102 generalised to
+    /// dim_nd base-dim_np digits and built on the device, and `commit_value(x, s)` (reciprocal.rs:88-90) from the same call.  The
+    /// integers are scalars (32 bytes, big-endian on the wire); dim_nd <= 16 and dim_np <= dim_nd + 1 fit these generators, and
+    /// dim_np^dim_nd must not exceed the group order (any such shape here does).  The 20 + 2 dim_nd draws per proof are made HERE in
+    /// the reference's order, as in prove_batch.  Returns the proofs in the C ABI's layout (c_l, c_r, c_o, c_s | r | x | r | l | n:
+    /// 928 bytes on these generators) and the commitments.
+    pub fn prove_values<R: RngCore + CryptoRng>(&self, dim_nd: usize, dim_np: usize, label: &'static [u8], xs: &[Scalar], ss: &[Scalar], rng: &mut R) -> Result<(Vec<Vec<u8>>, Vec<ProjectivePoint>), GpuError> {
+        assert_eq!(xs.len(), ss.len());
+        let n = xs.len();
+        let k = 20 + 2 * dim_nd;
+        let mut rnd = Vec::with_capacity(n * k * 32);
+        for _ in 0..n * k {
+            put_scalar(&mut rnd, &Scalar::generate_biased(&mut *rng));
+        }
+        let (mut xb, mut sb) = (Vec::with_capacity(n * 32), Vec::with_capacity(n * 32));
+        xs.iter().for_each(|x| put_scalar(&mut xb, x));
+        ss.iter().for_each(|s| put_scalar(&mut sb, s));
+        let (mut proofs, mut coms, mut st) = (vec![0u8; 928 * n], vec![0u8; 64 * n], vec![0i32; n]);
+        check(unsafe {
+            bppp_reciprocal_prove_values_batch(self.ctx, label.as_ptr(), label.len(), n, dim_nd, dim_np, xb.as_ptr(), sb.as_ptr(), rnd.as_ptr(), proofs.as_mut_ptr(), coms.as_mut_ptr(), st.as_mut_ptr())
+        })?;
+        if let Some(i) = st.iter().position(|s| *s & BPPP_ST_OUT_OF_RANGE != 0) {
+            return Err(GpuError::ValueOutOfRange { index: i });
+        }
+        if let Some(i) = st.iter().position(|s| *s != 0) {
+            return Err(GpuError::ReferenceWouldPanic { index: i });
+        }
+        Ok((proofs.chunks(928).map(|b| b.to_vec()).collect(),
             coms.chunks(64).map(|b| get_point(b).expect("library emitted a point off the curve")).collect()))
     }
 }

@@ -52,6 +52,7 @@ extern "C" {
 #define BPPP_ST_BAD_ENCODING 1 /* off-curve point / coordinate >= p / scalar >= n: k256 deserialisation would fail */
 #define BPPP_ST_DEGENERATE 2   /* the reference would panic here: challenge >= n (transcript.rs:13) or zero inverse
                                   (circuit.rs:192,196, reciprocal.rs:181, util.rs:119) */
+#define BPPP_ST_OUT_OF_RANGE 4 /* bppp_reciprocal_prove_values_batch*: the value has more than dim_nd base-dim_np digits */
 
 #if defined(__GNUC__)
 #define BPPP_API __attribute__((visibility("default")))
@@ -790,6 +791,41 @@ BPPP_API int bppp_circuit_prove_batch_seeded(bppp_ctx* ctx, const bppp_circuit* 
                                              const uint8_t* v_commitments, const uint8_t* v, const uint8_t* s_v, const uint8_t* w_l,
                                              const uint8_t* w_r, const uint8_t* w_o, const uint8_t seed[32], uint64_t stream_base,
                                              uint8_t* proofs, int32_t* status /* n or NULL */);
+
+/* ---- Range proofs from integers at any width: the reciprocal prover that builds its own witness ----
+ * The counterpart of U64RangeProofProtocol::prove(x, s, t, rng) (u64_proof.rs:70-102) for runtime dim_nd / dim_np: per instance the
+ * integer x and the blinding s go in (32-byte big-endian scalars), the value commitment commit_value(x, s) = x g + s h_vec[0]
+ * (reciprocal.rs:88-90) and the proof of bppp_reciprocal_prove_batch come out.  The witness of u64_proof.rs:84-102, generalised, is
+ * made on the device: digits = the dim_nd base-dim_np digits of x, least significant first (u64_to_hex's order), m[v] = the number of
+ * digits equal to v; the commitment comes from the context's fixed-base tables (the "ct_prover" table when that option is on, as for
+ * the rest of the prover), in the same launch chain.  The bytes equal those of bppp_msm_batch + bppp_reciprocal_prove_batch fed with
+ * that witness; for dim_nd = dim_np = 16 on the u64 generators they equal bppp_u64_prove_batch's.
+ * Shapes: x determines its digits only while dim_np^dim_nd <= n, the group order; any other shape -- (64, 16), (256, 16), (256, 2) -- is
+ * refused with BPPP_ERR_INVALID_ARG before anything is launched (bppp_reciprocal_prove_batch keeps serving those, from a witness).  The
+ * other argument checks are bppp_reciprocal_prove_batch's.
+ * status: a non-canonical x or s (>= n) gives BPPP_ST_BAD_ENCODING, as for every input scalar; a canonical x >= dim_np^dim_nd gives
+ * BPPP_ST_OUT_OF_RANGE.  A flagged instance gets a zeroed proof and the identity (64 zero bytes) as its commitment; the other
+ * instances of the batch are not affected.
+ * rnd: the 20 + 2 dim_nd draws per instance of bppp_reciprocal_prove_batch; the seeded forms make them on the device with the stream
+ * layout of bppp_reciprocal_prove_batch_seeded and clear them behind the prover's last kernel.
+ * The _device forms take device pointers (d_status may be NULL), are asynchronous on the context's stream and wait for nothing; the
+ * FIRST prove call of a (dim_nd, dim_np) on a context, of any form, builds the shape's circuit pattern and uploads it with a blocking
+ * copy -- it stays on the context. */
+BPPP_API int bppp_reciprocal_prove_values_batch(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
+                                                size_t dim_np, const uint8_t* x /* n x 32 */, const uint8_t* s /* n x 32 */,
+                                                const uint8_t* rnd /* n x (20 + 2 dim_nd) x 32 */, uint8_t* proofs,
+                                                uint8_t* commitments /* n x 64 */, int32_t* status /* n or NULL */);
+BPPP_API int bppp_reciprocal_prove_values_batch_seeded(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
+                                                       size_t dim_np, const uint8_t* x, const uint8_t* s, const uint8_t seed[32],
+                                                       uint64_t stream_base, uint8_t* proofs, uint8_t* commitments,
+                                                       int32_t* status /* n or NULL */);
+BPPP_API int bppp_reciprocal_prove_values_batch_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
+                                                       size_t dim_np, const void* d_x, const void* d_s, const void* d_rnd,
+                                                       void* d_proofs, void* d_commitments, void* d_status);
+BPPP_API int bppp_reciprocal_prove_values_batch_seeded_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                                              size_t dim_nd, size_t dim_np, const void* d_x, const void* d_s,
+                                                              const uint8_t seed[32], uint64_t stream_base, void* d_proofs,
+                                                              void* d_commitments, void* d_status);
 
 /* Profiling aid for bench.py: when enabled, every kernel launch of the verify pipeline is bracketed by HIP events on
  * the context's stream; bppp_ctx_get_timings returns accumulated milliseconds and launch counts per kernel since the

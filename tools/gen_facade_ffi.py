@@ -34,6 +34,7 @@ pub const BPPP_ERR_NOMEM: c_int = -5;
 pub const BPPP_ERR_RCCL: c_int = -6;
 pub const BPPP_ST_BAD_ENCODING: i32 = 1;
 pub const BPPP_ST_DEGENERATE: i32 = 2;
+pub const BPPP_ST_OUT_OF_RANGE: i32 = 4;
 pub const POINT_BYTES: usize = 64;
 pub const SCALAR_BYTES: usize = 32;
 pub const U64_PROOF_BYTES: usize = 928;
