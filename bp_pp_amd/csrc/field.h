@@ -368,6 +368,33 @@ HD void fe_mul2_add(fe& r, const fe& a, const fe& b, const fe& c, const fe& d) {
     }
     fe_reduce_cols(r, col);
 }
+// r = a b + 2^LK c^2 with ONE reduction: the 100 products of a b and the 55 of the square share the 19 column sums.  The factor
+// costs nothing: a squaring shifts c's limbs for its cross terms anyway (by LK + 1 here, and by LK for the diagonal).  Bounds: the
+// column sums stay below 2^64, mag(a) mag(b) + 2^LK mag(c)^2 <= 64, and the shifted limbs stay 32-bit, 2^LK mag(c) <= 16.
+// Used for -y3 = e (x3 - d) + 8 b^2 in the Jacobian doubling (point.h), which drops the separate b^2 squaring's reduction.
+template <int LK>
+HD void fe_mul_add_sqr(fe& r, const fe& a, const fe& b, const fe& c) {
+#ifdef BPPP_FE_DEBUG
+    assert(a.mag * b.mag + (c.mag * c.mag << LK) <= 64);
+    assert((c.mag << LK) <= 16);
+#endif
+    u32 cx[10], cd[10];
+#pragma unroll
+    for (int i = 0; i < 10; i++) { cx[i] = c.v[i] << (LK + 1); cd[i] = c.v[i] << LK; }   // < 2^32: c.v[i] < mag(c) 2^27
+    u64 col[19];
+#pragma unroll
+    for (int k = 0; k < 19; k++) {
+        const int i0 = k < 10 ? 0 : k - 9, i1 = k < 10 ? k : 9;
+        u64 acc = (u64)a.v[i0] * b.v[k - i0];
+#pragma unroll
+        for (int i = i0 + 1; i <= i1; i++) acc += (u64)a.v[i] * b.v[k - i];
+#pragma unroll
+        for (int i = i0; 2 * i < k; i++) acc += (u64)cx[i] * c.v[k - i];
+        if ((k & 1) == 0) acc += (u64)cd[k / 2] * c.v[k / 2];
+        col[k] = acc;
+    }
+    fe_reduce_cols(r, col);
+}
 HD void fe_sqr(fe& r, const fe& a) {   // 55 limb products: cross terms use the doubled limb
     FE_CHECK(a, 8);
     u32 a2[10];

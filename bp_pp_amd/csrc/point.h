@@ -210,21 +210,22 @@ HD void ptz_to_pt(pt& r, const ptz& a, bool empty) {
     pt_cmov(r, empty, id);
 }
 // ---- Jacobian accumulator (x = X/Z^2, y = Y/Z^3) for the shared-doubling (Straus) loops over AFFINE per-proof tables:
-// doubling 2M + 5S, mixed addition 8M + 3S (the complete projective law costs 6M + 2S + m and 12M).  Incomplete in the same
+// doubling 3M + 4S in six reductions, mixed addition 8M + 3S in ten (the complete projective law costs 6M + 2S + m and 12M).  Incomplete in the same
 // way as the XYZZ law above and used with the same deferred detection: an exceptional addition has H = 0, so Z3 = Z1 H = 0,
 // and Z stays 0 through every later doubling (Z3 = 2 Y1 Z1) and addition.  Coordinate magnitudes stay <= (6, 3, 2).
 struct ptj { fe X, Y, Z; };
 HD void ptj_init(ptj& a) { fe_set_u32(a.X, 0); fe_set_u32(a.Y, 0); fe_set_u32(a.Z, 0); }
-HD void ptj_dbl(ptj& a) {   // dbl-2009-l (a = 0)
-    fe A, B, C, D, E, F, t;
+// dbl-2009-l (a = 0) with D = 4 X1 Y1^2 taken as ONE product, X1 (4 B), instead of 2 ((X1 + B)^2 - A - C), and C = B^2 never reduced on
+// its own: it is only needed in Y3 = E (D - X3) - 8 C, whose negative E (X3 - D) + 8 B^2 is one fused column sum (fe_mul_add_sqr:
+// the square's 55 products ride with the product's 100).  3S + 2M + the fused M + S: six reductions instead of seven, and neither
+// of the two fe_mul_small carry passes.  Result magnitudes (4, 2, 2).
+HD void ptj_dbl(ptj& a) {
+    fe A, B, D, E, F, t;
     fe_sqr(A, a.X);
     fe_sqr(B, a.Y);
-    fe_sqr(C, B);
-    fe_add(t, a.X, B);                 // <= 7
-    fe_sqr(t, t);
-    fe_sub_m<1>(t, t, A);              // 3
-    fe_sub_m<1>(t, t, C);              // 5
-    fe_mul_small(D, t, 2);             // 1
+    fe_add(t, B, B);
+    fe_add(t, t, t);                   // 4 B, magnitude 4
+    fe_mul(D, a.X, t);                 // D = 4 X1 Y1^2 (6 * 4 <= 64), magnitude 1
     fe_add(E, A, A);
     fe_add(E, E, A);                   // 3
     fe_sqr(F, E);
@@ -232,10 +233,9 @@ HD void ptj_dbl(ptj& a) {   // dbl-2009-l (a = 0)
     fe_add(a.Z, t, t);                 // Z3 = 2 Y1 Z1, magnitude 2
     fe_add(t, D, D);                   // 2
     fe_sub_m<2>(a.X, F, t);            // X3 = F - 2D, magnitude 4
-    fe_sub_m<4>(t, D, a.X);            // 6
-    fe_mul(t, E, t);
-    fe_mul_small(C, C, 8);
-    fe_sub_m<1>(a.Y, t, C);            // Y3 = E (D - X3) - 8C, magnitude 3
+    fe_sub_m<1>(t, a.X, D);            // X3 - D, magnitude 6
+    fe_mul_add_sqr<3>(t, E, t, B);     // -Y3 = E (X3 - D) + 8 B^2, one reduction (3 * 6 + 8 * 1 * 1 <= 64); magnitude 1
+    fe_neg_m<1>(a.Y, t);               // Y3, magnitude 2
 }
 HD void ptj_madd(ptj& a, bool& empty, const apt& q, bool skip) {
     fe Z2, U2, S2, H, R, HH, HHH, V, X3, Y3, Z3, t;
