@@ -416,7 +416,7 @@ int bppp_ctx_set_option(bppp_ctx* c, const char* name, long value) {
         c->inject_alloc_fault = (int)value;
         return BPPP_OK;
     }
-    // parts of a generic reciprocal verify call on device buffers (bppp_generic.hip: generic_parts_for): 0 = by size, 1 .. 4 = that many
+    // parts of a generic reciprocal verify call on device buffers (plan_core.h: plan_generic_parts): 0 = by size, 1 .. 4 = that many
     if (std::strcmp(name, "generic_parts") == 0) {
         if (value < 0 || value > 4) return BPPP_ERR_INVALID_ARG;
         c->generic_parts = (int)value;

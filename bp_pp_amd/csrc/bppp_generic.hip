@@ -2,6 +2,12 @@
 // generic fixed-base linear combination (the crate's commit functions).
 #include "host.h"
 
+// the launch choices of the three verifiers: one pure function of (protocol, instances, rounds, switches) in plan_core.h
+using bppp_host::GenericPlan;
+using bppp_host::plan_generic;
+using bppp_host::GENERIC_FORM_WNLA; using bppp_host::GENERIC_FORM_RECIPROCAL; using bppp_host::GENERIC_FORM_CIRCUIT;
+using bppp_host::GENERIC_FB_WAVEFRONT; using bppp_host::GENERIC_FB_ONE_LANE;
+
 // one launch (or a short run of launches) on stream `st`, timed under KernelId `id` when kernel timing is on; a failure leaves the
 // calling function with its code (an `int rc` and the context `c` are in scope wherever this is used)
 #define GLAUNCH(st, id, ...)                                   \
@@ -79,24 +85,17 @@ struct TxDev {
 // fast variable-base path of the generic verifiers' rounds: per instance 2 x rounds window tables (16 entries of 64 B per point), the
 // running products of their build (BPPP_TSCR_PER_POINT per point) and the decoded round points -- 1.2 KB + 0.55 KB + 64 B per point, grow-only
 // extra_points: tables of that many more points per instance behind the round points' (the reciprocal verifier's five C0 points)
-// Sets of round-point tables a call of n instances builds (WnlaWs::tab_parts): calls that leave the chip EMPTY -- at most four instances
-// per SIMD -- cut every 26-window stream in 2 (4: at most one instance per SIMD) parts over tables of P and 2^65 P (P, 2^35 P, 2^70 P,
-// 2^100 P), a lane per table, and walk a round's sum on 8 (16) lanes: what such a call takes is the length of ONE instance's chain
-// (round 6: one WNLA verify of the u64 size 4.1 -> ms).  The u64 verifier has done the same since round 3 (plan_core.h: split).
-static int wnla_table_parts(const bppp_ctx* c, size_t n, size_t rounds) {
-    if (rounds == 0 || c->generic_slow_rounds || c->no_lane_groups || c->no_split || c->generic_lane_group) return 1;
-    const size_t S = (size_t)(c->n_simds > 0 ? c->n_simds : 1);
-    return n <= S ? 4 : n <= 4 * S ? 2 : 1;
-}
 static size_t wnla_fast_bytes(size_t n, size_t rounds, size_t extra_points, size_t parts = 1) {
     const size_t np = 2 * rounds * parts + extra_points;
     return align16(np * 16 * sizeof(apt_packed) * n) + align16((size_t)BPPP_TSCR_PER_POINT * np * 10 * sizeof(u32) * n) + align16(np * 16 * sizeof(u32) * n);
 }
+// The buffers of that path for the WnlaWs of a call (or part) on plan p, none where the plan has no fast rounds.
 // base: where this call's (or this part's) share of the table buffer starts; null = the context's buffer, grown to what the call needs
-// parts: sets of round-point tables (wnla_table_parts); the extra points' tables follow them, at entry 2 x rounds x 16 x parts
-static int wnla_fast_setup(bppp_ctx* c, WnlaWs& w, size_t n, size_t rounds, size_t extra_points = 0, uint8_t* base = nullptr, size_t parts = 1) {
-    w.atab = nullptr; w.tscr = nullptr; w.rpts = nullptr; w.tab_parts = 1;
-    if (rounds == 0 || c->generic_slow_rounds) return BPPP_OK;
+// The extra points' tables (the outer protocol's C0 points) follow the p.tab_parts sets of round-point tables, at entry wnla_atab_first
+static int wnla_fast_setup(bppp_ctx* c, WnlaWs& w, const GenericPlan& p, size_t extra_points, uint8_t* base = nullptr) {
+    const size_t n = w.N, rounds = (size_t)w.rounds, parts = (size_t)p.tab_parts;
+    w.atab = nullptr; w.tscr = nullptr; w.rpts = nullptr; w.tab_parts = p.tab_parts;
+    if (!p.fast) return BPPP_OK;
     const size_t np = 2 * rounds * parts + extra_points;
     const size_t b_tab = align16(np * 16 * sizeof(apt_packed) * n), b_scr = align16((size_t)BPPP_TSCR_PER_POINT * np * 10 * sizeof(u32) * n);
     if (!base) {
@@ -107,89 +106,34 @@ static int wnla_fast_setup(bppp_ctx* c, WnlaWs& w, size_t n, size_t rounds, size
     w.atab = (apt_packed*)base;
     w.tscr = (u32*)(base + b_tab);
     w.rpts = (u32*)(base + b_tab + b_scr);
-    w.tab_parts = (int)parts;
     return BPPP_OK;
 }
-// lanes per instance for the generic rounds: 16 / 8 over tables in 4 / 2 parts (calls that leave the chip empty), else 4 or 2 while that
-// still leaves wavefront slots free (and the fast path's tables exist)
-static int wnla_round_group(const bppp_ctx* c, const WnlaWs& w, unsigned blocks) {
-    if (!w.atab || c->no_lane_groups) return 1;
-    if (w.tab_parts == 4) return 16;
-    if (w.tab_parts == 2) return 8;
-    if (c->generic_lane_group) return c->generic_lane_group;
-    if (4 * (size_t)blocks <= (size_t)c->n_simds) return 4;
-    if (2 * (size_t)blocks <= (size_t)c->n_simds) return 2;
-    return 1;
-}
-// the fixed-base sums of a generic verify call on a WAVEFRONT per instance instead of 8 lanes: calls of up to eight instances per SIMD, where
-// 8 lanes per instance are at most one wavefront per SIMD and the call waits for one lane's chain of (bases x windows) / 8 dependent
-// table additions -- one instance of configs[4]'s shape: k_wnla_msm 7.6 -> 0.86 ms, k_recip_c0_fixed 2.5 -> 0.32 ms; with phase 1 on lane groups the call
-// 16.7 -> 6.1 ms (round 6, profiles/r06/r06_p4_latency_recip256.txt).  By size, same shape on 16-bit tables: 2,048 instances 14.1 -> 8.4 ms,
-// 4,096 14.9 -> 11.2, 8,192 19.3 -> 18.6, 16,384 28.2 -> 28.7 (profiles/r06/r06_p5_fb_wide_sizes.txt): up to 8 S
-static bool generic_fb_wide(const bppp_ctx* c, size_t n) {
-    if (c->generic_fb_wide_max >= 0) return n <= (size_t)c->generic_fb_wide_max;
-    return !c->no_lane_groups && !c->no_split && n <= 8 * (size_t)c->n_simds;
-}
+static int wnla_atab_first(const GenericPlan& p, size_t rounds) { return (int)(2 * rounds * 16 * (size_t)p.tab_parts); }
 static unsigned fb64_blocks_of(size_t n) { return (unsigned)((n * 64 + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK); }
 static unsigned fb1_blocks_of(size_t n) { return (unsigned)((n + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK); }
 // the round points' window tables: a lane per instance, or a lane per (point, part) table in a call that leaves the chip empty
-static void launch_wnla_tables(const WnlaWs& w, size_t n, unsigned blocks, hipStream_t s) {
-    if (w.tab_parts > 1) {
+static void launch_wnla_tables(const WnlaWs& w, int tab_parts, size_t n, unsigned blocks, hipStream_t s) {
+    if (tab_parts > 1) {
         int lp = 2;
         while (lp < 2 * w.rounds) lp *= 2;
-        k_wnla_tables_split<<<(unsigned)(((size_t)lp * w.tab_parts * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, w.tab_parts, lp);
+        k_wnla_tables_split<<<(unsigned)(((size_t)lp * tab_parts * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, tab_parts, lp);
     }
     else k_wnla_tables<<<blocks, BPPP_BLOCK, 0, s>>>(w);
 }
-// lanes per instance for the final scalars (k_wnla_final_scalars_grp), as log2: up to 8 while the launch stays within four wavefronts
-// per SIMD.  The work is independent per generator, so unlike the rounds it divides by the full group size.
-static int wnla_final_scalars_group_lg(const bppp_ctx* c, unsigned rounds, unsigned blocks) {
-    if (c->no_lane_groups) return 0;
-    if (c->generic_lane_group) return wnla_final_scalars_lg((int)rounds, c->generic_lane_group == 2 ? 1 : 3);   // (tests: 2 or 8 parts)
-    int lg = 0;
-    while (lg < 3 && ((size_t)blocks << (lg + 1)) <= 4 * (size_t)c->n_simds) lg++;
-    return wnla_final_scalars_lg((int)rounds, lg);
-}
-// (lg: wnla_final_scalars_group_lg by the wavefronts of the whole call -- the caller has recorded it in the call's form)
+// the final scalars on 2^lg lanes per instance (GenericPlan::final_lg)
 static void launch_wnla_final_scalars(const WnlaWs& w, int lg, unsigned blocks, hipStream_t s) {
     if (lg > 0) {
         k_wnla_final_scalars_grp<<<blocks << lg, BPPP_BLOCK, 0, s>>>(w, lg);
         k_wnla_final_scalars_join<<<blocks, BPPP_BLOCK, 0, s>>>(w, lg);
     } else k_wnla_final_scalars<<<blocks, BPPP_BLOCK, 0, s>>>(w);
 }
-// "last_generic_form" of bppp_ctx_get_option (include/bppp.h has the bit layout): the launch choices of a generic verify call, each as
-// the value the launch below it is given -- written by the three verify bodies just before their first launch, read by the tests that
-// run every threshold of the predicates above at +- 1 (tests/test_gpu_generic_boundaries.py)
-enum { GENERIC_FORM_WNLA = 1, GENERIC_FORM_RECIPROCAL = 2, GENERIC_FORM_CIRCUIT = 3 };
-enum { GENERIC_FB_LANES8 = 0, GENERIC_FB_WAVEFRONT = 1, GENERIC_FB_ONE_LANE = 2 };
 // one part of a multi-part call (recip_verify_device_entry): its stream and its shares of the context's buffers
 // (started / stage: an event recorded behind the part's stage-th milestone -- 1 phase 1, 2 the C0 stage, 3 the rounds -- that the NEXT
 // part's chain waits for, so that the chains run out of step: one part's fixed-base sums under another's one-lane kernels)
-struct GenericPart { hipStream_t s; uint8_t* gtab; pt_slot* straus; unsigned call_blocks; hipEvent_t started; int stage; int n_parts; };
+struct GenericPart { hipStream_t s; uint8_t* gtab; pt_slot* straus; size_t call_n; hipEvent_t started; int stage; int n_parts; };
 static int part_milestone(const GenericPart* part, int stage, hipStream_t s) {
     if (part && part->started && part->stage == stage) HIP_TRY(hipEventRecord(part->started, s));
     return BPPP_OK;
-}
-// The launch choices of a call's WNLA stage (the table parts are in WnlaWs::tab_parts): made once per call by wnla_form_setup, recorded
-// by generic_form_code, carried out by wnla_verify_stage
-struct WnlaForm { int round_group, final_lg, fb; };      // lanes per instance in the rounds | log2 of those in the final scalars | GENERIC_FB_*
-// The stage's table buffer (room for extra_points tables behind the round points': the outer protocol's C0 points) and its form, by the
-// predicates above over the instances of this call (or part) and the wavefronts of the WHOLE call -- the parts of a multi-part call
-// share the chip, and they take neither table parts nor the wavefront sums.  fb_one_lane: the reciprocal verifier's own choice.
-static int wnla_form_setup(bppp_ctx* c, WnlaWs& w, WnlaForm& f, size_t extra_points, const GenericPart* part = nullptr, bool fb_one_lane = false) {
-    const size_t n = w.N, rounds = (size_t)w.rounds;
-    const unsigned call_blocks = part ? part->call_blocks : blocks_of(n);
-    const int rc = wnla_fast_setup(c, w, n, rounds, extra_points, part ? part->gtab : nullptr, part ? 1 : (size_t)wnla_table_parts(c, n, rounds));
-    if (rc != BPPP_OK) return rc;
-    f.round_group = wnla_round_group(c, w, call_blocks);
-    f.final_lg = wnla_final_scalars_group_lg(c, (unsigned)rounds, call_blocks);
-    f.fb = fb_one_lane ? GENERIC_FB_ONE_LANE : (!part && generic_fb_wide(c, n)) ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8;
-    return BPPP_OK;
-}
-static uint32_t generic_form_code(int protocol, const WnlaWs& w, const WnlaForm& f, int p1_group = 0, bool beside = false, int parts = 1,
-                                  bool per_point = false) {
-    return (uint32_t)protocol | (uint32_t)w.tab_parts << 2 | (uint32_t)f.round_group << 5 | (uint32_t)f.final_lg << 10 | (uint32_t)f.fb << 12 |
-           (uint32_t)p1_group << 14 | (uint32_t)(beside ? 1 : 0) << 18 | (uint32_t)parts << 19 | (uint32_t)(per_point ? 1 : 0) << 22;
 }
 // the wire form of the generic proofs (the *_sec1 entry points at the end of this file): conversion launches over a WireMap (wire_core.h)
 static int wire_launch(WireMap m, bool expand, hipStream_t s) {
@@ -312,33 +256,33 @@ static int wnla_call_prepare(bppp_ctx* c, size_t n, const uint8_t* rlc_seed, boo
     return rlc ? wnla_rlc_prepare(c, n) : BPPP_OK;
 }
 
-// THE WNLA VERIFY STAGE, the tail of all three generic verifiers: on stream s over a prepared WnlaWs, in the form wnla_form_setup chose --
+// THE WNLA VERIFY STAGE, the tail of all three generic verifiers: on stream s over a prepared WnlaWs, in the form of the call's plan --
 // the transcript's start, the round points' tables, the rounds, the final scalars, the final sum and the verdicts, the transcripts out.
 // tables_done: the caller has launched the tables already (the reciprocal verifier, on its helper stream beside phase 1)
 // rlc_seed: the final sum in RLC mode over the buffers d + o_rlc (wnla_rlc_final_sum); null = every instance's own sum
 // part: the part of a multi-part call this is (its stage-3 milestone lies behind the rounds); null = the whole call
-static int wnla_verify_stage(bppp_ctx* c, const WnlaWs& w, const WnlaForm& f, hipStream_t s, bool tables_done = false,
+static int wnla_verify_stage(bppp_ctx* c, const WnlaWs& w, const GenericPlan& plan, hipStream_t s, bool tables_done = false,
                              const uint8_t* rlc_seed = nullptr, uint8_t* d = nullptr, const WnlaRlcLayout& o_rlc = {0, 0, 0, 0},
                              const GenericPart* part = nullptr) {
     const size_t n = w.N;
     const unsigned blocks = blocks_of(n);
-    const int grp = f.round_group;
+    const int grp = plan.round_group;
     int rc;
     GLAUNCH(s, K_WNLA_BEGIN, k_wnla_begin<<<blocks, BPPP_BLOCK, 0, s>>>(w));
-    if (w.atab && !tables_done) GLAUNCH(s, K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, s));
+    if (plan.fast && !tables_done) GLAUNCH(s, K_WNLA_TABLES, launch_wnla_tables(w, plan.tab_parts, n, blocks, s));
     for (int k = 1; k <= w.rounds; k++) {
         if (grp > 1) GLAUNCH(s, K_WNLA_ROUND, k_wnla_round_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(w, k, grp));
         else GLAUNCH(s, K_WNLA_ROUND, k_wnla_round<<<blocks, BPPP_BLOCK, 0, s>>>(w, k));
     }
     rc = part_milestone(part, 3, s);
     if (rc != BPPP_OK) return rc;
-    GLAUNCH(s, K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, f.final_lg, blocks, s));
+    GLAUNCH(s, K_WNLA_FINAL_SCALARS, launch_wnla_final_scalars(w, plan.final_lg, blocks, s));
     if (rlc_seed) {
         rc = wnla_rlc_final_sum(c, w, rlc_seed, d, o_rlc, s);
         if (rc != BPPP_OK) return rc;
     } else {
-        if (f.fb == GENERIC_FB_ONE_LANE) GLAUNCH(s, K_WNLA_MSM, k_wnla_msm_l1<<<fb1_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
-        else if (f.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
+        if (plan.fb == GENERIC_FB_ONE_LANE) GLAUNCH(s, K_WNLA_MSM, k_wnla_msm_l1<<<fb1_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
+        else if (plan.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_WNLA_MSM, k_wnla_msm_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w));
         else GLAUNCH(s, K_WNLA_MSM, k_wnla_msm<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(w, 0));
         GLAUNCH(s, K_WNLA_ACCEPT, k_wnla_accept<<<blocks, BPPP_BLOCK, 0, s>>>(w));
     }
@@ -369,6 +313,7 @@ static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label
     // rlc_seed (bppp_wnla_verify_batch_rlc[_device]): the final sum in RLC mode (wnla_rlc_final_sum, and the rule above it)
     HIP_TRY(hipSetDevice(c->device));
     if (!wnla_shape_ok(rounds, nl, nn)) return BPPP_ERR_INVALID_ARG;
+    const GenericPlan plan = plan_generic(GENERIC_FORM_WNLA, n, rounds, generic_knobs_of(c), n, 1, 0);      // (of a verify call)
     int rc = check_host_transcripts(tx, n);
     if (rc != BPPP_OK) return rc;
     bool rlc;
@@ -428,11 +373,10 @@ static int wnla_run(bppp_ctx* c, bool commit, const uint8_t* label, size_t label
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(out_points, d + o_out, n * 64, hipMemcpyDeviceToHost, s));
     } else {
-        WnlaForm f;
-        rc = wnla_form_setup(c, w, f, 0);
+        rc = wnla_fast_setup(c, w, plan, 0);
         if (rc != BPPP_OK) return rc;
-        c->last_generic_form = generic_form_code(GENERIC_FORM_WNLA, w, f);
-        rc = wnla_verify_stage(c, w, f, s, false, rlc ? rlc_seed : nullptr, d, o_rlc);
+        c->last_generic_form = plan.code();
+        rc = wnla_verify_stage(c, w, plan, s, false, rlc ? rlc_seed : nullptr, d, o_rlc);
         if (rc != BPPP_OK) return rc;
         if (device_io) return BPPP_OK;
         HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
@@ -538,6 +482,8 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
                                     const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
                                     int32_t* d_st, uint8_t* d_ws, const TranscriptIo* dtio = nullptr, const uint8_t* rlc_seed = nullptr,
                                     const GenericPart* part = nullptr) {
+    // which kernels the call (or part) runs, on how many lanes per instance and on which stream: plan_core.h
+    const GenericPlan plan = plan_generic(GENERIC_FORM_RECIPROCAL, n, rounds, generic_knobs_of(c), part ? part->call_n : n, part ? part->n_parts : 1, 0);
     const RecipVerifyLayout o = recip_verify_layout(c, n, dim_nd, dim_np, rounds, rlc_seed != nullptr);
     uint8_t* d = d_ws;
     hipStream_t s = part ? part->s : c->stream;
@@ -554,43 +500,20 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
     if (dtio) r.tio = *dtio;
     WnlaWs w = wnla_ws_continuing(c, r, 5, nl, nn, d_acc, (u32*)(d + o.ys), (u32*)(d + o.tab), (u32*)(d + o.msc));
     const unsigned blocks = blocks_of(n);
-    // (the lane-group choices below go by the wavefronts of the WHOLE call: the parts of a multi-part call share the chip)
-    const unsigned call_blocks = part ? part->call_blocks : blocks;
     int rc;
-    // the two fixed-base sums: 8 lanes per instance, or one from the size at which one lane per instance fills the SIMDs twice over
-    const bool fb_one_lane = c->fb_one_lane_mode >= 0 ? c->fb_one_lane_mode == 1 : n >= (size_t)128 * (size_t)c->n_simds;
     // the WNLA stage's table buffer with room for the five C0 points' tables behind the round points': the variable-base part of C0 on
     // affine window tables too (and on lane groups while one lane per instance leaves wavefront slots free)
-    WnlaForm f;
-    rc = wnla_form_setup(c, w, f, 5, part, fb_one_lane);
+    rc = wnla_fast_setup(c, w, plan, 5, part ? part->gtab : nullptr);
     if (rc != BPPP_OK) return rc;
-    r.atab = w.atab; r.tscr = w.tscr; r.atab_first = (int)(2 * rounds * 16 * (size_t)w.tab_parts);
-    // What needs nothing but the proof bytes -- the round points' window tables -- and what needs only phase 1 -- the C0 points' tables
-    // and C0's variable-base sum, one lane (or a lane group) per instance -- runs on the HELPER stream beside phase 1 and the fixed-base
-    // half of C0 (8 lanes per instance: the kernel that fills the chip); round 6: 2^15 instances of configs[4]'s shape, where the
-    // one-lane kernels are half a wavefront per SIMD, 46.6 -> 45.0 ms per batch.  With kernel timing on everything stays on one stream so
-    // that the per-kernel times add up; the parts of a multi-part call are chains of their own.
-    // (only while the one-lane kernels are at most half a wavefront per SIMD: beyond that the kernels fill the chip by themselves and side
-    // by side they take LONGER than one after the other, as in the u64 verifier -- 2^16 instances 79.6 ms on two streams against 79.2 on
-    // one, 2^17 154.2 / 153.0, 2^18 314.3 / 301.4: profiles/r06/r06_b1_recip_beside_sizes.txt)
-    const bool beside = w.atab && !c->timing && !part && (c->recip_beside >= 0 ? c->recip_beside == 1 : 2 * (size_t)call_blocks <= (size_t)c->n_simds);
+    r.atab = w.atab; r.tscr = w.tscr; r.atab_first = wnla_atab_first(plan, rounds);
+    const bool beside = plan.beside;      // the round points' tables, the C0 points' tables and C0's variable-base sum on the helper stream
     hipStream_t a = beside ? c->aux_stream : s;
-    // lanes per instance for phase 1's two loops over the digits: as many (up to 8) as keep the launch within ONE wavefront per SIMD --
-    // the kernel is an uncapped build (one wavefront per SIMD fits), and a group's lanes each repeat the head (transcript, inversions:
-    // a seventh of the one-lane kernel).  Round 6, configs[4]'s shape, the kernel alone: 2^15 instances 3.48 -> 2.10 ms on 2 lanes
-    // (2.65 on 4, 3.8 on 8: two and four generations of wavefronts); the call 45.71 -> 45.30 ms, because the round-point tables
-    // that ran beside the half-empty one-lane kernel now share its SIMDs (profiles/r06/r06_p2_recip_phase1_groups.txt)
-    int G = 1;
-    if (c->recip_p1_group) G = c->recip_p1_group;
-    else if (!c->no_lane_groups) {
-        if (c->generic_lane_group) G = c->generic_lane_group == 2 ? 2 : 8;      // (tests: the smallest and the largest split at any size)
-        else while (G < 8 && 2 * (size_t)G * call_blocks <= (size_t)c->n_simds) G *= 2;
-    }
-    c->last_generic_form = generic_form_code(GENERIC_FORM_RECIPROCAL, w, f, G, beside, part ? part->n_parts : 1);
+    const int G = plan.p1_group;
+    c->last_generic_form = plan.code();
     if (beside) {
         HIP_TRY(hipEventRecord(c->ev_tab, s));               // (the call's inputs are ready on s)
         HIP_TRY(hipStreamWaitEvent(a, c->ev_tab, 0));
-        GLAUNCH(a, K_WNLA_TABLES, launch_wnla_tables(w, n, blocks, a));
+        GLAUNCH(a, K_WNLA_TABLES, launch_wnla_tables(w, plan.tab_parts, n, blocks, a));
     }
     if (G > 1) GLAUNCH(s, K_RECIP_PHASE1, k_recip_phase1_grp<<<(unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, G));
     else GLAUNCH(s, K_RECIP_PHASE1, k_recip_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
@@ -600,11 +523,11 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
         HIP_TRY(hipEventRecord(c->ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(a, c->ev_fork, 0));
     }
-    if (f.fb == GENERIC_FB_ONE_LANE) GLAUNCH(s, K_RECIP_C0_FIXED, k_recip_c0_fixed_l1<<<fb1_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
-    else if (f.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_RECIP_C0_FIXED, k_recip_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    if (plan.fb == GENERIC_FB_ONE_LANE) GLAUNCH(s, K_RECIP_C0_FIXED, k_recip_c0_fixed_l1<<<fb1_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    else if (plan.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_RECIP_C0_FIXED, k_recip_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
     else GLAUNCH(s, K_RECIP_C0_FIXED, k_recip_c0_fixed<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
-    if (r.atab) {
-        const int grp = f.round_group > 4 ? 4 : f.round_group;      // (C0's sum: lane groups of 2 or 4)
+    if (plan.fast) {
+        const int grp = plan.c0var_group;
         GLAUNCH(a, K_RECIP_C0_VAR, {
             k_recip_c0_tables<<<blocks, BPPP_BLOCK, 0, a>>>(r);
             if (grp > 1) k_recip_c0_var_grp<<<(unsigned)(((size_t)grp * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, a>>>(r, grp);
@@ -618,14 +541,7 @@ static int recip_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t la
     GLAUNCH(s, K_RECIP_C0_FINISH, k_recip_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
     rc = part_milestone(part, 2, s);
     if (rc != BPPP_OK) return rc;
-    return wnla_verify_stage(c, w, f, s, beside, rlc_seed, d, o.rlc, part);      // (the final sum in RLC mode whenever a seed is given, at any n)
-}
-// parts of a reciprocal verify call (see recip_verify_device_entry): by how far one lane per instance under-fills the chip; one part
-// with kernel timing on (the per-kernel times must add up), in RLC mode (its stages work on the whole batch) and for small calls
-static int generic_parts_for(const bppp_ctx* c, size_t n, bool rlc) {
-    if (rlc || c->timing || n < 2 * BPPP_BLOCK) return 1;
-    if (c->generic_parts > 0) return c->generic_parts > 4 ? 4 : c->generic_parts;      // forced (A/B runs, tests at small sizes)
-    return 1;
+    return wnla_verify_stage(c, w, plan, s, beside, rlc_seed, d, o.rlc, part);      // (the final sum in RLC mode whenever a seed is given, at any n)
 }
 static int recip_verify_check_args(const bppp_ctx* c, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn) {
     if (dim_nd == 0 || dim_np == 0 || dim_nd > (size_t)c->ng || dim_nd + 10 > (size_t)c->nh || dim_np > dim_nd + 1 || rounds > 12 ||
@@ -658,7 +574,7 @@ int recip_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_le
     // third of the step waiting on lone wavefronts' dependent chains -- while the two fixed-base sums (8 lanes per instance: 769 and 263
     // bases) fill it.  Instances are independent, so the parts need no ordering among themselves: one part's fixed-base sums run under
     // another part's one-lane kernels, and the wavefront slots the chains leave idle do the sums' work.
-    const int K = generic_parts_for(c, n, rlc_seed != nullptr);
+    const int K = bppp_host::plan_generic_parts(n, rlc_seed != nullptr, c->timing, c->generic_parts);
     if (K > 1) {
         rc = bppp_ensure_twin_lanes(c);
         if (rc != BPPP_OK) return rc;
@@ -672,7 +588,7 @@ int recip_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_le
         }
         rc = ensure_buffer(c, c->d_gws, c->gws_bytes, ws_total);
         if (rc != BPPP_OK) return rc;
-        const bool fast = rounds != 0 && !c->generic_slow_rounds;
+        const bool fast = bppp_host::generic_fast(rounds, generic_knobs_of(c));
         if (fast) {
             rc = ensure_buffer(c, c->d_gtab, c->gtab_bytes, gt_total);
             if (rc != BPPP_OK) return rc;
@@ -682,12 +598,11 @@ int recip_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_le
         hipEvent_t started[4] = {c->ev_tab, c->ev_fork, c->ev_join, nullptr};      // (free here: a part's kernels are one chain on one stream)
         const int stage = c->generic_stagger;
         const size_t proof_bytes = 64 * (5 + 2 * rounds) + 32 * (nl + nn);
-        const unsigned call_blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
         HIP_TRY(hipEventRecord(c->ev_twin_fork, c->stream));
         for (int i = 1; i < parts; i++) HIP_TRY(hipStreamWaitEvent(streams[i], c->ev_twin_fork, 0));
         int rc_parts = BPPP_OK;
         for (int i = 0; i < parts && rc_parts == BPPP_OK; i++) {
-            const GenericPart gp = {streams[i], fast ? c->d_gtab + gt_off[i] : nullptr, c->d_straus + lo[i] * 5 * BPPP_STRAUS_ENTRIES, call_blocks,
+            const GenericPart gp = {streams[i], fast ? c->d_gtab + gt_off[i] : nullptr, c->d_straus + lo[i] * 5 * BPPP_STRAUS_ENTRIES, n,
                                     stage && i + 1 < parts ? started[i] : nullptr, stage, parts};
             if (stage && i > 0) HIP_TRY(hipStreamWaitEvent(streams[i], started[i - 1], 0));
             rc_parts = recip_verify_device_impl(c, label, label_len, m[i], dim_nd, dim_np, (const uint8_t*)d_commitments + 64 * lo[i],
@@ -914,6 +829,7 @@ static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const ui
     int rc = circuit_verify_check(c, q, label, label_len, commitments, proofs, accept, rounds, nl, nn);
     if (rc != BPPP_OK || n == 0) return rc;
     const CircuitDev& cd = q->cd;
+    const GenericPlan plan = plan_generic(GENERIC_FORM_CIRCUIT, n, rounds, generic_knobs_of(c), n, 1, 4 + (size_t)cd.k);
     rc = check_host_transcripts(tx, n);
     if (rc != BPPP_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -957,29 +873,23 @@ static int circuit_verify_host_impl(bppp_ctx* c, const bppp_circuit* q, const ui
     WnlaWs w = wnla_ws_continuing(c, r, 4, nl, nn, device_io ? accept : d + o_acc, (u32*)(d + o_ys), (u32*)(d + o_tab), (u32*)(d + o_msc));
     const unsigned blocks = blocks_of(n);
     // the WNLA stage's table buffer with room for the 4 + k points of C0's variable-base part behind the round points' tables
-    WnlaForm f;
-    rc = wnla_form_setup(c, w, f, 4 + k);
+    rc = wnla_fast_setup(c, w, plan, 4 + k);
     if (rc != BPPP_OK) return rc;
-    r.atab = w.atab; r.tscr = w.tscr; r.atab_first = (int)(2 * rounds * 16 * (size_t)w.tab_parts);
-    // C0's variable-base sum: a lane per point (L lanes per instance, tables and sum in one launch) while that stays within two
-    // wavefronts per SIMD, else the one-lane kernels (five points per shared-doubling pass).  Round 6, `mixed_k2` (6 points): one
-    // verify 4.74 -> 2.76 ms (this stage 3.0 -> 0.98), 8,192 instances 1.37 ms where 16,384 on the one-lane kernels take 2.64
-    int L = 8;
-    while (L < 4 + (int)k) L *= 2;
-    const bool per_point = r.atab && !c->no_lane_groups && !c->no_split && L <= 64 && (size_t)L * blocks <= 2 * (size_t)c->n_simds;
-    c->last_generic_form = generic_form_code(GENERIC_FORM_CIRCUIT, w, f, 0, false, 1, per_point);
+    r.atab = w.atab; r.tscr = w.tscr; r.atab_first = wnla_atab_first(plan, rounds);
+    c->last_generic_form = plan.code();
     GLAUNCH(s, K_CIRCUIT_PHASE1, k_circuit_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    if (f.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    if (plan.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
     else GLAUNCH(s, K_CIRCUIT_C0_FIXED, k_circuit_c0_fixed<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
     GLAUNCH(s, K_CIRCUIT_C0_VAR, {
-        if (per_point) k_circuit_c0_var_pts<<<(unsigned)(((size_t)L * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, L);
+        // (a lane per point: tables and sum in one launch)
+        if (plan.per_point) k_circuit_c0_var_pts<<<(unsigned)(((size_t)plan.c0_lanes * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, plan.c0_lanes);
         else {
-            if (r.atab) k_circuit_c0_tables<<<blocks, BPPP_BLOCK, 0, s>>>(r);
+            if (plan.fast) k_circuit_c0_tables<<<blocks, BPPP_BLOCK, 0, s>>>(r);
             k_circuit_c0_var<<<blocks, BPPP_BLOCK, 0, s>>>(r);
         }
     });
     GLAUNCH(s, K_CIRCUIT_C0_FINISH, k_circuit_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    rc = wnla_verify_stage(c, w, f, s, false, rlc ? rlc_seed : nullptr, d, o_rlc);
+    rc = wnla_verify_stage(c, w, plan, s, false, rlc ? rlc_seed : nullptr, d, o_rlc);
     if (rc != BPPP_OK) return rc;
     if (device_io) return BPPP_OK;
     HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));

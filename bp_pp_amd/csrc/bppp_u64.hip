@@ -10,7 +10,6 @@
 extern unsigned long long* g_bppp_stamps_dev;      // bppp_ctx.hip
 #endif
 static_assert(bppp_host::PLAN_BLOCK == BPPP_BLOCK, "plan_core.h counts workgroups of BPPP_BLOCK lanes");
-// the switches of a context that the plans depend on
 struct VerifyLanes { hipStream_t s, a; hipEvent_t ev_fork, ev_join, ev_tab; hipEvent_t ev_started; };      // a: null = no helper stream; ev_started: recorded after the first kernel (or null)
 // the second stream pair of a twin call (plan_core.h: twin), created at the first such call
 int bppp_ensure_twin_lanes(bppp_ctx* c) {
@@ -37,15 +36,6 @@ int bppp_ensure_twin_lanes(bppp_ctx* c) {
     }
     for (hipEvent_t* e : {&c->ev_twin_fork, &c->ev_twin_join, &c->ev2_fork, &c->ev2_join, &c->ev2_tab}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     return BPPP_OK;
-}
-static bppp_host::PlanKnobs knobs_of(const bppp_ctx* c) {
-    bppp_host::PlanKnobs k;
-    k.n_simds = c->n_simds;
-    k.no_small = c->no_small; k.no_lane_groups = c->no_lane_groups; k.no_split = c->no_split; k.timing = c->timing;
-    k.tables_beside = c->tables_beside; k.tail_beside = c->tail_beside; k.fb_one_lane_mode = c->fb_one_lane_mode; k.next_overlap = c->next_overlap;
-    k.shared_inv = c->shared_inv; k.twin = c->twin; k.pace = c->pace;
-    k.next_msm_max = c->next_msm_max; k.lane_forms_max = c->lane_forms_max; k.lane4_max = c->lane4_max; k.scal_parts_max = c->scal_parts_max;
-    return k;
 }
 
 // 1 / in[t] for all t < n, one inversion per G elements (k_verify_misc.hip)

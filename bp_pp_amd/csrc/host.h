@@ -16,6 +16,7 @@
 
 #include "../../include/bppp.h"
 #include "kernels.h"
+#include "plan_core.h"
 
 using namespace bppp;
 
@@ -166,7 +167,7 @@ struct bppp_ctx {
     int tail_beside = -1;     // diagnostic BPPP_TAIL_BESIDE: the last round's sum beside the final fixed-base sum always (1) / never (0)
     u32* d_zinv = nullptr;    // [10][n] of the current call inside d_ws (carve)
     int generic_stagger = 1;  // the parts' chains start out of step: part i + 1 behind part i's phase 1 (1), C0 stage (2), rounds (3); 0: together
-    int generic_parts = 0;    // diagnostic BPPP_GENERIC_PARTS: parts of a generic reciprocal verify call (bppp_generic.hip: generic_parts_for); 0 = by size
+    int generic_parts = 0;    // diagnostic BPPP_GENERIC_PARTS: parts of a generic reciprocal verify call (plan_core.h: plan_generic_parts); 0 = by size
     int twin_stream_kind = 1; // diagnostic BPPP_TWIN_STREAMS: the second chain's stream at 0 normal priority | 1 high priority (default) | 2 with a CU mask of all CUs
     int twin = -1, pace = -1; // diagnostics BPPP_TWIN / BPPP_PACE (plan_core.h: VerifyPlan::twin, ::pace); unset = by batch size
     hipStream_t twin_stream = nullptr, twin_aux = nullptr;      // the second half's stream pair of a twin verify call (bppp_u64.hip: ensure_twin_lanes)
@@ -179,7 +180,7 @@ struct bppp_ctx {
     int fb_one_lane_mode = -1;   // diagnostic BPPP_FB_ONE_LANE: 1 = one lane per proof in the u64 verifier's fixed-base kernels at every size, 0 = never, unset = by size   // diagnostics, read from the environment once at context creation
     // single-proof front end (bppp_coalesce.hip): created at the first *_one call; options "coalesce_max" / "coalesce_us" / "coalesce_lanes"
     uint32_t last_verify_plan = 0, last_prove_plan = 0;      // plan_core.h: the kernels the context's last u64 verify / prove call (or part) ran
-    uint32_t last_generic_form = 0;                          // bppp_generic.hip: generic_form_code of the context's last generic verify call (or part); include/bppp.h has the bits
+    uint32_t last_generic_form = 0;                          // plan_core.h: GenericPlan::code of the context's last generic verify call (or part); include/bppp.h has the bits
     struct bppp_fronts* fronts = nullptr;      // lives until the context itself is deleted (closure is sticky: never re-created once closed)
     std::atomic<bool> fronts_closed{false};    // set by bppp_ctx_destroy before it drains: *_one callers return BPPP_ERR_CLOSED instead of retrying
     std::atomic<int> one_callers{0};           // threads inside a *_one entry point (counted before they touch anything else of the context);
@@ -191,6 +192,25 @@ struct bppp_ctx {
     double total_ms[K_COUNT] = {0};
     int64_t launches[K_COUNT] = {0};
 };
+
+// the switches of a context that the plans depend on (plan_core.h): the u64 verifier's and prover's, the generic verifiers'
+static inline bppp_host::PlanKnobs knobs_of(const bppp_ctx* c) {
+    bppp_host::PlanKnobs k;
+    k.n_simds = c->n_simds;
+    k.no_small = c->no_small; k.no_lane_groups = c->no_lane_groups; k.no_split = c->no_split; k.timing = c->timing;
+    k.tables_beside = c->tables_beside; k.tail_beside = c->tail_beside; k.fb_one_lane_mode = c->fb_one_lane_mode; k.next_overlap = c->next_overlap;
+    k.shared_inv = c->shared_inv; k.twin = c->twin; k.pace = c->pace;
+    k.next_msm_max = c->next_msm_max; k.lane_forms_max = c->lane_forms_max; k.lane4_max = c->lane4_max; k.scal_parts_max = c->scal_parts_max;
+    return k;
+}
+static inline bppp_host::GenericKnobs generic_knobs_of(const bppp_ctx* c) {
+    bppp_host::GenericKnobs k;
+    k.n_simds = c->n_simds;
+    k.no_lane_groups = c->no_lane_groups; k.no_split = c->no_split; k.timing = c->timing; k.slow_rounds = c->generic_slow_rounds;
+    k.lane_group = c->generic_lane_group; k.fb_wide_max = c->generic_fb_wide_max; k.fb_one_lane_mode = c->fb_one_lane_mode;
+    k.recip_beside = c->recip_beside; k.recip_p1_group = c->recip_p1_group;
+    return k;
+}
 
 struct CtxLock {
     bppp_ctx* c;

@@ -83,7 +83,7 @@ __device__ __forceinline__ void wnla_msm_lanes(const WnlaWs& w) {
 __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_wnla_msm(WnlaWs w, int commit_mode) { wnla_msm_lanes<BPPP_FB_LANES>(w); (void)commit_mode; }
 __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_wnla_msm_l1(WnlaWs w) { wnla_msm_lanes<1>(w); }
 // a wavefront per instance: calls so small that 8 lanes per instance leave the chip empty and the call waits for one lane's chain of
-// (1 + |g_vec| + |h_vec|) x windows / 8 dependent table additions (bppp_generic.hip: generic_fb_wide)
+// (1 + |g_vec| + |h_vec|) x windows / 8 dependent table additions (plan_core.h: plan_generic, GENERIC_FB_WAVEFRONT)
 __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_wnla_msm_l64(WnlaWs w) { wnla_msm_lanes<64>(w); }
 __global__ __launch_bounds__(BPPP_BLOCK) void k_wnla_commit_store(WnlaWs w) {
     size_t t = (size_t)blockIdx.x * BPPP_BLOCK + threadIdx.x;

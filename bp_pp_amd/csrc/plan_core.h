@@ -19,6 +19,18 @@
 //   prove   n <= S: a wavefront per sum, wide round scalars | n <= 4 S: 16-lane stages and folds | n <= 16 S: 4-lane stages and folds |
 //           n <= 32 S: next commitment from fixed-base sums | n <= 128 S: round scalars in four parts | n >= 128 S: one lane per sum;
 //           the 256-register builds from more than 64 S values (one wavefront per SIMD) on
+//
+// The generic verifiers (WNLA, reciprocal, circuit: bppp_generic.hip) take theirs from plan_generic below in the same way; its code is
+// "last_generic_form" of bppp_ctx_get_option (include/bppp.h has the bits).  n instances, blocks = ceil(n / 64):
+//   all         n <= S           4 sets of round-point tables per instance, rounds on 16 lanes    | n <= 4 S: 2 sets, 8 lanes
+//               n <= 8 S         a wavefront per fixed-base sum, 8 lanes beyond
+//               n <= 16 S        rounds on 4 lanes per instance (4 blocks <= S)                    | n <= 32 S: 2 lanes | 1
+//               n <= 32 S        final scalars on 8 lanes per instance (8 blocks <= 4 S)           | n <= 64 S: 4 | n <= 128 S: 2 | 1,
+//                                and never more than 2^(rounds - 1)
+//   reciprocal  n <= 8 S         phase 1 on 8 lanes per instance (2 G blocks <= S)                 | n <= 16 S: 4 | n <= 32 S: 2 | 1
+//               n <= 32 S        round-point tables and C0's variable-base sum on the helper stream beside phase 1 (2 blocks <= S)
+//               n >= 128 S       one lane per fixed-base sum
+//   circuit     n <= 16 S        C0's variable-base sum on a lane per point (L blocks <= 2 S; L = 8 for up to 8 points)
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -231,6 +243,124 @@ inline int plan_describe(uint32_t code, bool prove, char* buf, size_t cap) {
     return std::snprintf(buf, cap, "fb=%s fb4_from_jobs=%u stage=%s fold=%s scalars=%s next_by_msm=%u w2=%u overlap_next=%u next_g4=%u ct=%u",
                          pick(FB, 4, code & 15), (code >> 4) & 15, pick(ST, 6, (code >> 8) & 15), pick(ST, 6, (code >> 12) & 15), pick(SC, 3, (code >> 16) & 15),
                          (code >> 20) & 1, (code >> 21) & 1, (code >> 22) & 1, (code >> 23) & 1, (code >> 24) & 1);
+}
+
+// ---- The generic verifiers: WeightNormLinearArgument, ReciprocalRangeProofProtocol and ArithmeticCircuit for any generator-vector sizes
+// (bppp_generic.hip).  All three end in the WNLA stage (tables of the round points, rounds, final scalars, final fixed-base sum); the
+// reciprocal and the circuit verifier run a phase 1 and a C0 stage of their own in front of it.
+struct GenericKnobs {
+    int n_simds = 1024;
+    bool no_lane_groups = false, no_split = false, timing = false;
+    bool slow_rounds = false;          // BPPP_GENERIC_SLOW_ROUNDS: projective tables + complete additions in the rounds
+    int lane_group = 0;                // BPPP_GENERIC_LANE_GROUP = 2 | 4: that many lanes per instance in the grouped kernels at any size (tests); 0 = by size
+    long fb_wide_max = -1;             // diagnostic: the largest call (instances) whose fixed-base sums run a wavefront per instance; -1 = by size
+    int fb_one_lane_mode = -1;         // diagnostic: the reciprocal verifier's fixed-base sums on one lane always (1) / never (0); -1 = by size
+    int recip_beside = -1;             // diagnostic: the reciprocal verifier's one-lane kernels beside its fixed-base ones always (1) / never (0); -1 = by size
+    int recip_p1_group = 0;            // diagnostic: 1 | 2 | 4 | 8 lanes per instance in the reciprocal verifier's phase 1; 0 = by size
+};
+enum { GENERIC_FORM_WNLA = 1, GENERIC_FORM_RECIPROCAL = 2, GENERIC_FORM_CIRCUIT = 3 };
+enum { GENERIC_FB_LANES8 = 0, GENERIC_FB_WAVEFRONT = 1, GENERIC_FB_ONE_LANE = 2 };
+
+struct GenericPlan {
+    int protocol = GENERIC_FORM_WNLA;
+    bool fast = false;           // the rounds walk affine window tables of the round points (else: projective tables, complete additions)
+    int tab_parts = 1;           // sets of round-point tables per instance: 1, or 2 / 4 with every 26-window stream cut in as many parts
+    int round_group = 1;         // lanes per instance in the rounds
+    int final_lg = 0;            // log2 of the lanes per instance in the final scalars
+    int fb = GENERIC_FB_LANES8;  // lanes per fixed-base sum: GENERIC_FB_*
+    int c0var_group = 0;         // reciprocal: lanes per instance in C0's variable-base sum
+    int p1_group = 0;            // reciprocal: lanes per instance in phase 1
+    bool beside = false;         // reciprocal: the round-point tables and C0's variable-base sum on the helper stream, beside phase 1
+    int parts = 1;               // parts the call runs in (this is the plan of one of them)
+    int c0_lanes = 0;            // circuit: lanes per instance of C0's variable-base sum on a lane per point (a power of two >= the points)
+    bool per_point = false;      // circuit: C0's variable-base sum runs in that form
+    // "last_generic_form" (include/bppp.h has the bit layout): each choice as the value its launch is given
+    uint32_t code() const {
+        return (uint32_t)protocol | (uint32_t)tab_parts << 2 | (uint32_t)round_group << 5 | (uint32_t)final_lg << 10 | (uint32_t)fb << 12 |
+               (uint32_t)p1_group << 14 | (uint32_t)(beside ? 1 : 0) << 18 | (uint32_t)parts << 19 | (uint32_t)(per_point ? 1 : 0) << 22;
+    }
+};
+
+// the lanes one instance's final scalars are dealt to, as log2: what is wanted, cut to what the table of 2^rounds entries has room for
+constexpr int final_scalars_lg_clip(int rounds, int want_lg) { return want_lg < rounds ? want_lg : (rounds > 0 ? rounds - 1 : 0); }
+// the fast variable-base path of the rounds (window tables of the round points in the context's table buffer)
+inline bool generic_fast(size_t rounds, const GenericKnobs& k) { return rounds != 0 && !k.slow_rounds; }
+
+// Parts of a reciprocal verify call on device buffers (K chains on K streams, so that one part's fixed-base sums run under another
+// part's one-lane kernels): one part with kernel timing on (the per-kernel times must add up), in RLC mode (its stages work on the
+// whole batch) and for small calls; otherwise what the caller forces ("generic_parts": A/B runs, tests at small sizes), at most 4
+inline int plan_generic_parts(size_t n, bool rlc, bool timing, int forced) {
+    if (rlc || timing || n < 2 * PLAN_BLOCK) return 1;
+    return forced > 4 ? 4 : forced > 0 ? forced : 1;
+}
+
+// n: instances of this call, or of this part of it; call_n: instances of the whole call (= n unless n_parts > 1) -- the lane-group
+// choices go by the wavefronts of the WHOLE call, because the parts of a multi-part call share the chip; a part takes neither table
+// parts nor the wavefront sums nor the helper stream (it is a chain on one stream).  c0_points: the circuit's 4 + k points of C0.
+inline GenericPlan plan_generic(int protocol, size_t n, size_t rounds, const GenericKnobs& k, size_t call_n, int n_parts, size_t c0_points) {
+    GenericPlan p;
+    p.protocol = protocol;
+    p.parts = n_parts;
+    const bool part = n_parts > 1;
+    const size_t S = (size_t)(k.n_simds > 0 ? k.n_simds : 1);
+    const size_t blocks = (call_n + PLAN_BLOCK - 1) / PLAN_BLOCK;
+    const bool groups = !k.no_lane_groups, split_ok = groups && !k.no_split;
+    p.fast = generic_fast(rounds, k);
+    // Sets of round-point tables: calls that leave the chip EMPTY -- at most four instances per SIMD -- cut every 26-window stream in 2
+    // (4: at most one instance per SIMD) parts over tables of P and 2^65 P (P, 2^35 P, 2^70 P, 2^100 P), a lane per table, and walk a
+    // round's sum on 8 (16) lanes: what such a call takes is the length of ONE instance's chain (round 6: one WNLA verify of the u64
+    // size 4.1 -> ms).  The u64 verifier has done the same since round 3 (split, above).
+    p.tab_parts = (part || !p.fast || !split_ok || k.lane_group) ? 1 : n <= S ? 4 : n <= 4 * S ? 2 : 1;
+    // lanes per instance in the rounds: 16 / 8 over tables in 4 / 2 parts, else 4 or 2 while that still leaves wavefront slots free
+    p.round_group = (!p.fast || !groups) ? 1 : p.tab_parts == 4 ? 16 : p.tab_parts == 2 ? 8 : k.lane_group ? k.lane_group :
+                    4 * blocks <= S ? 4 : 2 * blocks <= S ? 2 : 1;
+    // ... in the final scalars: up to 8 while the launch stays within four wavefronts per SIMD.  The work is independent per generator,
+    // so unlike the rounds it divides by the full group size.  (lane_group, tests: 2 or 8 parts)
+    int lg = 0;
+    if (groups && k.lane_group) lg = k.lane_group == 2 ? 1 : 3;
+    else if (groups) while (lg < 3 && (blocks << (lg + 1)) <= 4 * S) lg++;
+    p.final_lg = final_scalars_lg_clip((int)rounds, lg);
+    // The fixed-base sums.  One lane per instance from the size at which that fills the SIMDs twice over (the reciprocal verifier only).
+    // A WAVEFRONT per instance instead of 8 lanes in calls of up to eight instances per SIMD, where 8 lanes per instance are at most one
+    // wavefront per SIMD and the call waits for one lane's chain of (bases x windows) / 8 dependent table additions -- one instance of
+    // configs[4]'s shape: k_wnla_msm 7.6 -> 0.86 ms, k_recip_c0_fixed 2.5 -> 0.32 ms; with phase 1 on lane groups the call 16.7 -> 6.1 ms
+    // (round 6, profiles/r06/r06_p4_latency_recip256.txt).  By size, same shape on 16-bit tables: 2,048 instances 14.1 -> 8.4 ms, 4,096
+    // 14.9 -> 11.2, 8,192 19.3 -> 18.6, 16,384 28.2 -> 28.7 (profiles/r06/r06_p5_fb_wide_sizes.txt): up to 8 S
+    const bool fb_one_lane = protocol == GENERIC_FORM_RECIPROCAL && (k.fb_one_lane_mode >= 0 ? k.fb_one_lane_mode == 1 : n >= 128 * S);
+    const bool fb_wide = !part && (k.fb_wide_max >= 0 ? n <= (size_t)k.fb_wide_max : split_ok && n <= 8 * S);
+    p.fb = fb_one_lane ? GENERIC_FB_ONE_LANE : fb_wide ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8;
+    if (protocol == GENERIC_FORM_RECIPROCAL) {
+        p.c0var_group = p.round_group > 4 ? 4 : p.round_group;      // (C0's sum: lane groups of 2 or 4)
+        // What needs nothing but the proof bytes -- the round points' window tables -- and what needs only phase 1 -- the C0 points' tables
+        // and C0's variable-base sum, one lane (or a lane group) per instance -- runs on the HELPER stream beside phase 1 and the fixed-base
+        // half of C0 (8 lanes per instance: the kernel that fills the chip); round 6: 2^15 instances of configs[4]'s shape, where the
+        // one-lane kernels are half a wavefront per SIMD, 46.6 -> 45.0 ms per batch.  With kernel timing on everything stays on one stream
+        // so that the per-kernel times add up; the parts of a multi-part call are chains of their own.
+        // (only while the one-lane kernels are at most half a wavefront per SIMD: beyond that the kernels fill the chip by themselves and
+        // side by side they take LONGER than one after the other, as in the u64 verifier -- 2^16 instances 79.6 ms on two streams against
+        // 79.2 on one, 2^17 154.2 / 153.0, 2^18 314.3 / 301.4: profiles/r06/r06_b1_recip_beside_sizes.txt)
+        p.beside = p.fast && !k.timing && !part && (k.recip_beside >= 0 ? k.recip_beside == 1 : 2 * blocks <= S);
+        // lanes per instance for phase 1's two loops over the digits: as many (up to 8) as keep the launch within ONE wavefront per SIMD --
+        // the kernel is an uncapped build (one wavefront per SIMD fits), and a group's lanes each repeat the head (transcript, inversions:
+        // a seventh of the one-lane kernel).  Round 6, configs[4]'s shape, the kernel alone: 2^15 instances 3.48 -> 2.10 ms on 2 lanes
+        // (2.65 on 4, 3.8 on 8: two and four generations of wavefronts); the call 45.71 -> 45.30 ms, because the round-point tables
+        // that ran beside the half-empty one-lane kernel now share its SIMDs (profiles/r06/r06_p2_recip_phase1_groups.txt)
+        int G = 1;
+        if (k.recip_p1_group) G = k.recip_p1_group;
+        else if (groups && k.lane_group) G = k.lane_group == 2 ? 2 : 8;      // (tests: the smallest and the largest split at any size)
+        else if (groups) while (G < 8 && 2 * (size_t)G * blocks <= S) G *= 2;
+        p.p1_group = G;
+    }
+    if (protocol == GENERIC_FORM_CIRCUIT) {
+        // C0's variable-base sum: a lane per point (c0_lanes per instance, tables and sum in one launch) while that stays within two
+        // wavefronts per SIMD, else the one-lane kernels (five points per shared-doubling pass).  Round 6, `mixed_k2` (6 points): one
+        // verify 4.74 -> 2.76 ms (this stage 3.0 -> 0.98), 8,192 instances 1.37 ms where 16,384 on the one-lane kernels take 2.64
+        int L = 8;
+        while ((size_t)L < c0_points && L < (1 << 30)) L *= 2;
+        p.c0_lanes = L;
+        p.per_point = p.fast && split_ok && L <= 64 && (size_t)L * ((n + PLAN_BLOCK - 1) / PLAN_BLOCK) <= 2 * S;
+    }
+    return p;
 }
 
 }  // namespace bppp_host

@@ -12,6 +12,7 @@
 // (1 + ng + nh)-term fixed-base MSM.  Length quirks are reproduced: extra entries of proof.l / proof.n beyond the folded
 // generator vectors multiply identities (util.rs:24-26) but extra n entries still enter |n|^2_mu (wnla.rs:67).
 #pragma once
+#include "plan_core.h"      // (first: field.h pulls <stdio.h> in inside its namespace in the host build)
 #include "verify_core.h"
 
 namespace bppp {
@@ -328,7 +329,7 @@ HD void wnla_verify_final_scalars(const WnlaWs& w, size_t t) {
     wnla_final_scalars_join(w, t, 0);
 }
 // the lanes one instance's final scalars are dealt to (a power of two <= 8 that the table has room for; 1 = the whole instance)
-HD int wnla_final_scalars_lg(int rounds, int want_lg) { return want_lg < rounds ? want_lg : (rounds > 0 ? rounds - 1 : 0); }
+HD int wnla_final_scalars_lg(int rounds, int want_lg) { return bppp_host::final_scalars_lg_clip(rounds, want_lg); }
 HD void wnla_msm_ranges(FbRanges& rg, const WnlaWs& w) { fb_ranges_one(rg, 0, 0, 1 + w.ng + w.nh); }
 HD void wnla_verify_store(const WnlaWs& w, size_t t, const pt& rhs) { ws_st_pt(w.pfix, w.N, t, rhs); }
 HD void wnla_verify_accept(const WnlaWs& w, size_t t) {

@@ -57,9 +57,9 @@ def test_circuit_verify_vs_oracle(name, B):
 
 @pytest.mark.parametrize("name,B", [("mixed_k2", 9), ("ac_works", 5)])
 def test_circuit_verify_one_lane_kernels_vs_oracle(name, B, monkeypatch):
-    """Small calls take the per-point form of C0's variable-base sum and the wavefront-per-instance fixed-base sums (bppp_generic.hip:
-    per_point, generic_fb_wide); BPPP_NO_LANE_GROUPS=1 keeps the kernels large batches run -- one lane per instance, five points per
-    shared-doubling pass, 8 lanes per fixed-base sum -- so that they are compared with the oracle at a size the oracle finishes too."""
+    """Small calls take the per-point form of C0's variable-base sum and the wavefront-per-instance fixed-base sums (plan_core.h:
+    plan_generic -- per_point, GENERIC_FB_WAVEFRONT); BPPP_NO_LANE_GROUPS=1 keeps the kernels large batches run -- one lane per instance, five
+    points per shared-doubling pass, 8 lanes per fixed-base sum -- so that they are compared with the oracle at a size the oracle finishes too."""
     import torch
     if torch.cuda.device_count() == 0:
         pytest.fail("needs a GPU")
