@@ -27,6 +27,7 @@ namespace bppp {
 
 #define BPPP_BKT_WINDOWS 8       // 8-bit digits of a 64-bit half-weight
 #define BPPP_BKT_MAX_M 8192      // items are numbered in 16 bits (2 M <= 65536) and LDS holds 4 waves x (2 KB + 2 M x 2 B) <= 160 KB
+#define BPPP_BKT_SCALAR_GROUP 16 // bases per workgroup of k_bkt_scalars
 
 struct c4_packed { u32 x[8], y[8], z[8]; };   // C4 in canonical packed words, 96 B (projective: no inversion spent on it)
 
@@ -46,6 +47,12 @@ struct BucketWs {
     uint8_t* accept;
     FbTable fb;             // N = nsuper
 };
+
+// launch geometry of the stage, one expression for the host side (host.h: launch_bucket_stage) and the tests' launcher (tests/prims):
+// dynamic LDS of k_bkt_accumulate (per wave 512 words of bucket bookkeeping + M words of sorted item numbers, then the 8 window sums)
+// and the base groups of k_bkt_scalars (its grid's y)
+HD size_t bkt_lds_bytes(u32 M) { return ((size_t)4 * (512 + M) + 8 * 30) * sizeof(u32); }
+HD unsigned bkt_scalar_groups(int nb) { return (unsigned)((nb + BPPP_BKT_SCALAR_GROUP - 1) / BPPP_BKT_SCALAR_GROUP); }
 
 // per proof: half-weights and the packed commitment
 HD void bkt_prepare(const BucketWs& w, size_t t) {
@@ -127,6 +134,7 @@ HD bool bkt_superchunk_serial(const BucketWs& w, size_t chunk) {
         pt_add(total, total, sum);
     }
     const size_t ns = w.fb.N;
+    ws_st_pt(w.lhs, ns, chunk, total);      // as k_bkt_accumulate leaves it
     for (int i = 0; i < w.nb; i++) {
         u32 aa[12], ab[12];
         for (int k = 0; k < 12; k++) aa[k] = ab[k] = 0;

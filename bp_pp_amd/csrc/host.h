@@ -482,10 +482,10 @@ static inline int launch_bucket_stage(bppp_ctx* c, BucketWs& bw, size_t n, unsig
     bw.asc = (u32*)p; p += align16(nsuper * (size_t)nb * 32);
     bw.sflag = p;
     bw.fb = fb_table_of(c, nsuper);
-    const size_t lds_bytes = ((size_t)4 * (512 + SM) + 8 * 30) * sizeof(u32);
+    const size_t lds_bytes = bkt_lds_bytes(SM);
     (void)hipFuncSetAttribute((const void*)k_bkt_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     const unsigned blocks = (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK);
-    const dim3 sgrid((unsigned)nsuper, (unsigned)((nb + BPPP_BKT_SCALAR_GROUP - 1) / BPPP_BKT_SCALAR_GROUP));
+    const dim3 sgrid((unsigned)nsuper, bkt_scalar_groups(nb));
     rc = timed_launch(K_BKT_PREPARE, [&]() { k_bkt_prepare<<<blocks, BPPP_BLOCK, 0, s>>>(bw); });
     if (rc == BPPP_OK) rc = timed_launch(K_BKT_ACCUMULATE, [&]() { k_bkt_accumulate<<<(unsigned)nsuper, 256, lds_bytes, s>>>(bw); });
     if (rc == BPPP_OK) rc = timed_launch(K_BKT_SCALARS, [&]() { k_bkt_scalars<<<sgrid, 256, 0, s>>>(bw); });

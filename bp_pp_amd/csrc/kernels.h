@@ -241,6 +241,5 @@ __global__ __launch_bounds__(BPPP_BLOCK) void k_recip_c0_var_grp(bppp::RecipWs w
 __global__ __launch_bounds__(BPPP_BLOCK) void k_recip_c0_finish(bppp::RecipWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_bkt_prepare(bppp::BucketWs w);
 __global__ __launch_bounds__(256) void k_bkt_accumulate(bppp::BucketWs w);
-#define BPPP_BKT_SCALAR_GROUP 16
 __global__ __launch_bounds__(256) void k_bkt_scalars(bppp::BucketWs w);
 __global__ __launch_bounds__(64) void k_bkt_check(bppp::BucketWs w);

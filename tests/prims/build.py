@@ -1,12 +1,15 @@
-"""Builds the TEST-ONLY primitive libraries of tests/test_prims.py from one dispatcher (prims_core.h):
+"""Builds the TEST-ONLY primitive libraries of tests/test_prims*.py from one dispatcher (prims_core.h):
 
   libbppp_prims_gcc.so    g++ host build (prims_host.cpp): the code path of the tests/emul emulation
   libbppp_prims_clang.so  ROCm's clang++ host build (prims_host.cpp): field.h's __builtin_addc / __builtin_subc carry chains
-  libbppp_prims_hip.so    hipcc gfx950 build (prims_device.hip) with the product's BASE_FLAGS: the code the GPU runs
+  libbppp_prims_hip.so    hipcc gfx950 build (prims_device.hip, bucket_device.hip) with the product's BASE_FLAGS: the code the GPU runs
 
 Each library exports the dispatcher (prims_run_host / prims_run_device) and the variable-base sums (prims_run_sums_host: the one-lane
 forms; prims_run_sums_device: those and the lane-group forms) and the transcript primitives (prims_run_transcript_host: the register
-sponge; prims_run_transcript_device: that and the LDS sponge, in the uniform and the grouped launch layout).  A library is rebuilt when it is missing or older than any bp_pp_amd/csrc/*.h or tests/prims/* source."""
+sponge; prims_run_transcript_device: that and the LDS sponge, in the uniform and the grouped launch layout) and the bucket stage of the
+RLC batch mode (tests/test_prims_bucket.py, arguments in bucket_prims.h; prims_run_bucket_host: the single-thread form of bucket_core.h;
+prims_run_bucket_device: the product's own k_bkt_* kernels, whose translation unit bucket_device.hip includes as it is).  A library is
+rebuilt when it is missing or older than any bp_pp_amd/csrc/*.h, an included kernel unit or any tests/prims/* source."""
 import ctypes as C
 import glob
 import os
@@ -26,6 +29,8 @@ SO = {
     "gfx950": os.path.join(HERE, "libbppp_prims_hip.so"),
 }
 HOST_FLAGS = ["-O2", "-shared", "-fPIC", "-std=c++17"]
+DEVICE_UNITS = ("prims_device.hip", "bucket_device.hip")
+INCLUDED_KERNEL_UNITS = ("k_verify_bucket.hip",)      # bp_pp_amd/csrc units that bucket_device.hip includes
 
 
 def _hipcc():
@@ -42,7 +47,8 @@ def clangxx():
 
 
 def _stale(so):
-    deps = glob.glob(os.path.join(ROOT, "bp_pp_amd", "csrc", "*.h")) + [
+    csrc = os.path.join(ROOT, "bp_pp_amd", "csrc")
+    deps = glob.glob(os.path.join(csrc, "*.h")) + [os.path.join(csrc, u) for u in INCLUDED_KERNEL_UNITS] + [
         p for p in glob.glob(os.path.join(HERE, "*")) if os.path.isfile(p) and not p.endswith(".so") and "__pycache__" not in p]
     return not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps)
 
@@ -65,7 +71,8 @@ def build(backend, force=False):
         raise RuntimeError(why)
     if backend == "gfx950":
         from bp_pp_amd._build import BASE_FLAGS
-        cmd = [_hipcc(), *BASE_FLAGS, "-shared", "-Wl,-rpath,/opt/rocm/lib", "-o", so + ".tmp", os.path.join(HERE, "prims_device.hip")]
+        cmd = [_hipcc(), *BASE_FLAGS, "-shared", "-Wl,-rpath,/opt/rocm/lib", "-o", so + ".tmp",
+               *[os.path.join(HERE, u) for u in DEVICE_UNITS]]
     else:
         cxx = "g++" if backend == "gcc" else clangxx()
         cmd = [cxx, *HOST_FLAGS, "-o", so + ".tmp", os.path.join(HERE, "prims_host.cpp")]
@@ -102,6 +109,17 @@ def load(backend):
     run_tr.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz]
     run_tr.restype = C.c_int
     L.run_transcript = run_tr
+    u64p = C.POINTER(C.c_uint64)
+    L.prims_bucket_fb_entries.argtypes = [C.c_int, C.c_int]
+    L.prims_bucket_fb_entries.restype = sz
+    L.prims_bucket_fb_build.argtypes = [C.c_char_p, C.c_int, C.c_int, vp]
+    L.prims_bucket_fb_build.restype = C.c_int
+    L.prims_bucket_geometry.argtypes = [C.c_uint32, C.c_int, u64p]
+    L.prims_bucket_geometry.restype = None
+    run_bkt = L.prims_run_bucket_device if backend == "gfx950" else L.prims_run_bucket_host
+    run_bkt.argtypes = [sz, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    run_bkt.restype = C.c_int
+    L.run_bucket = run_bkt
     if backend != "gfx950":
         L.prims_is_clang.restype = C.c_int
     return L

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "prims_core.h"
+#include "bucket_prims.h"
 
 #define PRIMS_API extern "C" __attribute__((visibility("default")))
 
@@ -75,6 +76,35 @@ PRIMS_API int prims_run_transcript_host(const uint32_t* prog, uint32_t form, uin
         uint32_t* o = out + r * TR_OUT_WORDS;
         if (!ok) { o[51] = prims::ST_BAD_PARAM; continue; }
         prims::tr_eval_regs(prog, states + r * BPPP_TRANSCRIPT_STATE_BYTES, in + r * TR_IN_WORDS, o);
+    }
+    return 0;
+}
+
+// The bucket stage of the RLC batch mode (bucket_prims.h has the arguments) in the single-thread form of bucket_core.h: bkt_prepare per
+// proof, then bkt_superchunk_serial per superchunk (plain bucket sums, bkt_mac / bkt_finish_scalar, fb_sum_serial), and k_bkt_check's
+// verdict bytes.  Returns 0, or -1 for arguments out of range.
+PRIMS_API size_t prims_bucket_fb_entries(int nb, int W) { return bktp::fb_entries(nb, W); }
+PRIMS_API int prims_bucket_fb_build(const uint8_t* gens, int nb, int W, uint8_t* table_out) {
+    if (nb < 1 || nb > BKT_MAX_NB || W != 4) return -1;
+    return bktp::fb_build(gens, nb, W, table_out);
+}
+// {dynamic LDS bytes of k_bkt_accumulate, base groups of k_bkt_scalars}: the launch geometry the product and the launcher share
+PRIMS_API void prims_bucket_geometry(uint32_t M, int nb, uint64_t out[2]) { out[0] = bppp::bkt_lds_bytes(M); out[1] = bppp::bkt_scalar_groups(nb); }
+PRIMS_API int prims_run_bucket_host(size_t N, uint32_t M, int nb, const uint64_t* seed, const int32_t* status, const uint32_t* acc,
+                                    const uint32_t* fsc, const uint8_t* table, int W, int given, uint64_t* wab, uint32_t* c4, uint32_t* lhs,
+                                    uint32_t* asc, uint8_t* sflag, uint8_t* accept) {
+    if (!bktp::args_ok(N, M, nb, W)) return -1;
+    const size_t ns = bktp::nsuper_of(N, M);
+    for (size_t c = 0; c < ns; c++) sflag[c] = BKT_SENTINEL;
+    for (size_t j = 0; j < N; j++) accept[j] = BKT_SENTINEL;
+    const bppp::BucketWs w = bktp::workspace(N, M, nb, seed, status, acc, fsc, table, W, wab, c4, lhs, asc, sflag, accept);
+    if (!given)
+        for (size_t t = 0; t < N; t++) bppp::bkt_prepare(w, t);
+    for (size_t c = 0; c < ns; c++) {
+        const bool ok = bppp::bkt_superchunk_serial(w, c);
+        sflag[c] = ok ? 0 : 1;
+        if (ok)
+            for (size_t j = c * M; j < c * M + M && j < N; j++) accept[j] = status[j] == bppp::ST_OK ? 1 : 0;
     }
     return 0;
 }
