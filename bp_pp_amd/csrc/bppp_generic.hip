@@ -6,6 +6,7 @@
 using bppp_host::GenericPlan;
 using bppp_host::plan_generic;
 using bppp_host::GENERIC_FORM_WNLA; using bppp_host::GENERIC_FORM_RECIPROCAL; using bppp_host::GENERIC_FORM_CIRCUIT;
+using bppp_host::GENERIC_FORM_AGGREGATE;
 using bppp_host::GENERIC_FB_WAVEFRONT; using bppp_host::GENERIC_FB_ONE_LANE;
 
 // one launch (or a short run of launches) on stream `st`, timed under KernelId `id` when kernel timing is on; a failure leaves the
@@ -702,6 +703,158 @@ static int recip_verify_host_impl(bppp_ctx* c, const uint8_t* label, size_t labe
                                   d + o_ws, tx ? &dtio : nullptr, rlc_seed);
     if (rc != BPPP_OK) return rc;
     if (dtio.states_out) HIP_TRY(hipMemcpyAsync(tx->states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPPP_OK;
+}
+
+// ---------------------------------------------------------------- aggregated reciprocal range proof: k values under one proof
+// (agg_core.h has the protocol; tests/agg_cases.py states it on the oracle).  Verifier only, exact mode, 64-byte points: phase 1 and the
+// C0 stage of its own, then the WNLA stage.  k = 1 IS ReciprocalRangeProofProtocol and goes to that verifier's entry points.
+struct AggVerifyLayout { size_t ts, sc0, pts, a, pf, inv, vs, wc, wcv, rho, mu, ys, tab, msc, total; };
+static AggVerifyLayout agg_verify_layout(const bppp_ctx* c, size_t n, size_t k, size_t dim_nd, size_t dim_np, size_t rounds) {
+    const size_t NB = (size_t)c->nbases, T = (size_t)1 << rounds, NH = (size_t)c->nh, nm = k * dim_nd;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes); };
+    AggVerifyLayout o;
+    o.ts = take(52 * n * 4); o.sc0 = take((nm + 5 + k) * 8 * n * 4); o.pts = take((4 + k) * 16 * n * 4); o.a = take(30 * n * 4);
+    o.pf = take(30 * n * 4); o.inv = take(dim_np * 8 * n * 4); o.vs = take(k * 40 * n * 4); o.wc = take(n * 64); o.wcv = take(n * NH * 32);
+    o.rho = take(n * 32); o.mu = take(n * 32); o.ys = take((rounds ? rounds : 1) * 8 * n * 4); o.tab = take(2 * T * 8 * n * 4);
+    o.msc = take(NB * 8 * n * 4);
+    o.total = off;
+    return o;
+}
+static size_t agg_proof_bytes(size_t k, size_t rounds, size_t nl, size_t nn) { return 64 * (4 + 2 * rounds + k) + 32 * (nl + nn); }
+// 1 <= k <= 64, k dim_nd generators of g_vec and dim_nd + 10 of h_vec in the context, dim_np <= dim_nd + 1, the WNLA stage's bounds
+static int agg_verify_check_args(const bppp_ctx* c, size_t k, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn) {
+    if (k == 0 || k > 64 || dim_nd == 0 || dim_np == 0 || dim_nd > (size_t)c->ng || k * dim_nd > (size_t)c->ng || dim_nd + 10 > (size_t)c->nh ||
+        dim_np > dim_nd + 1 || rounds > 12 || nl > 4096 || nn > 4096)
+        return BPPP_ERR_INVALID_ARG;
+    return BPPP_OK;
+}
+// the launch sequence of one call (or of one max_batch part of it), every buffer in device memory; d_ws holds agg_verify_layout().total
+static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                                  const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
+                                  int32_t* d_st, uint8_t* d_ws) {
+    const GenericPlan plan = plan_generic(GENERIC_FORM_AGGREGATE, n, rounds, generic_knobs_of(c), n, 1, 4 + k);
+    const AggVerifyLayout o = agg_verify_layout(c, n, k, dim_nd, dim_np, rounds);
+    uint8_t* d = d_ws;
+    hipStream_t s = c->stream;
+    AggWs r;
+    std::memset(&r, 0, sizeof r);
+    r.N = n; r.k = (int)k; r.nd = (int)dim_nd; r.np = (int)dim_np; r.rounds = (int)rounds; r.nl = (int)nl; r.nn = (int)nn;
+    r.NG = c->ng; r.NH = c->nh; r.proof_bytes = agg_proof_bytes(k, rounds, nl, nn);
+    r.commitments = d_com; r.proofs = d_proofs; r.status = d_st; r.tstate = (u32*)(d + o.ts);
+    r.sc0 = (u32*)(d + o.sc0); r.pts = (u32*)(d + o.pts); r.acc = (u32*)(d + o.a); r.pfix = (u32*)(d + o.pf); r.inv = (u32*)(d + o.inv);
+    r.vsum = (u32*)(d + o.vs);
+    r.straus = c->d_straus;
+    r.wn_commit = d + o.wc; r.wn_c = d + o.wcv; r.wn_rho = d + o.rho; r.wn_mu = d + o.mu;
+    r.fb = fb_table_of(c, n);
+    t_new(r.base, label, (u32)label_len);
+    WnlaWs w = wnla_ws_continuing(c, r, 4 + k, nl, nn, d_acc, (u32*)(d + o.ys), (u32*)(d + o.tab), (u32*)(d + o.msc));
+    const unsigned blocks = blocks_of(n);
+    int rc;
+    // the WNLA stage's table buffer with room for the 4 + k points of C0's variable-base part behind the round points' tables
+    rc = wnla_fast_setup(c, w, plan, 4 + k);
+    if (rc != BPPP_OK) return rc;
+    r.atab = w.atab; r.tscr = w.tscr; r.atab_first = wnla_atab_first(plan, rounds);
+    // as the reciprocal verifier: what needs only the proof bytes (the round points' tables) and what needs only phase 1 (the C0
+    // points' tables and sum) on the helper stream, beside phase 1 and the fixed-base half of C0
+    const bool beside = plan.beside;
+    hipStream_t a = beside ? c->aux_stream : s;
+    const int G = plan.p1_group;
+    c->last_generic_form = plan.code();
+    if (beside) {
+        HIP_TRY(hipEventRecord(c->ev_tab, s));               // (the call's inputs are ready on s)
+        HIP_TRY(hipStreamWaitEvent(a, c->ev_tab, 0));
+        GLAUNCH(a, K_WNLA_TABLES, launch_wnla_tables(w, plan.tab_parts, n, blocks, a));
+    }
+    if (G > 1) GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1_grp<<<(unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, G));
+    else GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
+    if (beside) {
+        HIP_TRY(hipEventRecord(c->ev_fork, s));
+        HIP_TRY(hipStreamWaitEvent(a, c->ev_fork, 0));
+    }
+    if (plan.fb == GENERIC_FB_ONE_LANE) GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed_l1<<<fb1_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    else if (plan.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    else GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    GLAUNCH(a, K_AGG_C0_VAR, {
+        if (plan.fast) k_agg_c0_tables<<<blocks, BPPP_BLOCK, 0, a>>>(r);
+        k_agg_c0_var<<<blocks, BPPP_BLOCK, 0, a>>>(r);
+    });
+    if (beside) {
+        HIP_TRY(hipEventRecord(c->ev_join, a));
+        HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
+    }
+    GLAUNCH(s, K_AGG_C0_FINISH, k_agg_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
+    return wnla_verify_stage(c, w, plan, s, beside);
+}
+// a call of more than max_batch instances runs as consecutive parts on the context's stream over one workspace, as the u64 verifier's
+// (instances are independent); d_ws: agg_verify_layout(min(n, max_batch)).total
+static size_t agg_part_size(const bppp_ctx* c, size_t n) { return n < c->max_batch ? n : c->max_batch; }
+static int agg_verify_parts(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                            const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
+                            int32_t* d_st, uint8_t* d_ws) {
+    const size_t per = agg_part_size(c, n), pb = agg_proof_bytes(k, rounds, nl, nn);
+    for (size_t lo = 0; lo < n; lo += per) {
+        const size_t m = n - lo < per ? n - lo : per;
+        const int rc = agg_verify_device_impl(c, label, label_len, m, k, dim_nd, dim_np, d_com + 64 * k * lo, d_proofs + pb * lo, rounds, nl, nn,
+                                              d_acc + lo, d_st + lo, d_ws);
+        if (rc != BPPP_OK) return rc;
+    }
+    return BPPP_OK;
+}
+size_t bppp_reciprocal_agg_proof_bytes(size_t k, size_t rounds, size_t nl, size_t nn) { return agg_proof_bytes(k, rounds, nl, nn); }
+int bppp_reciprocal_agg_verify_batch_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                            size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
+                                            size_t nn, void* d_accept, void* d_status, void* d_reject_count) {
+    CtxLock lock_(c);
+    if (!c || !label_ok(label, label_len) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
+    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (k == 1)
+        return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
+                                         nullptr, d_reject_count);
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
+    if (n == 0) return BPPP_OK;
+    const size_t per = agg_part_size(c, n);
+    rc = ensure_straus_capacity(c, per);
+    if (rc != BPPP_OK) return rc;
+    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_verify_layout(c, per, k, dim_nd, dim_np, rounds).total);
+    if (rc != BPPP_OK) return rc;
+    rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, rounds, nl, nn,
+                          (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws);
+    if (rc != BPPP_OK || !d_reject_count) return rc;
+    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
+    HIP_TRY(hipGetLastError());
+    return BPPP_OK;
+}
+int bppp_reciprocal_agg_verify_batch(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                                     const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                     int32_t* status) {
+    CtxLock lock_(c);
+    if (!c || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
+    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (k == 1) return recip_verify_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr);
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t per = agg_part_size(c, n);
+    rc = ensure_straus_capacity(c, per);
+    if (rc != BPPP_OK) return rc;
+    const size_t pb = agg_proof_bytes(k, rounds, nl, nn);
+    const size_t o_com = 0, o_pr = align16(n * k * 64), o_acc = align16(o_pr + n * pb), o_st = align16(o_acc + n), o_ws = align16(o_st + n * 4),
+                 total = o_ws + agg_verify_layout(c, per, k, dim_nd, dim_np, rounds).total;
+    WnlaBlob blob;
+    { const int rc_b = blob.take(c, total); if (rc_b != BPPP_OK) return rc_b; }
+    uint8_t* d = blob.d;
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * k * 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_pr, proofs, n * pb, hipMemcpyHostToDevice, s));
+    rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, d + o_com, d + o_pr, rounds, nl, nn, d + o_acc, (int32_t*)(d + o_st), d + o_ws);
+    if (rc != BPPP_OK) return rc;
     HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

@@ -43,6 +43,7 @@ enum KernelId {
     K_SHARED_INV,      // u64 verifier from 2^18 proofs: the launches that invert once for 8 / 16 proofs (and the join of C0's halves ahead of round 1)
     // reciprocal prover from integers (bppp_reciprocal_prove_values_batch*): the witness kernel | the value commitment | everything behind them
     K_RPROVE_WITNESS, K_RPROVE_COMMIT, K_RPROVE_CHAIN,
+    K_AGG_PHASE1, K_AGG_C0_FIXED, K_AGG_C0_VAR, K_AGG_C0_FINISH,      // aggregated reciprocal verifier (then the K_WNLA_* stage)
     K_COUNT
 };
 static const char* const kKernelNames[K_COUNT] = {
@@ -52,7 +53,8 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_recip_phase1", "k_recip_c0_fixed", "k_recip_c0_var", "k_recip_c0_finish", "k_wnla_begin", "k_wnla_round", "k_wnla_final_scalars",
     "k_wnla_msm", "k_wnla_accept", "k_wnla_rlc_lhs", "k_wnla_rlc_chunk", "k_wnla_rlc_check", "k_wnla_tables",
     "k_circuit_phase1", "k_circuit_c0_fixed", "k_circuit_c0_var", "k_circuit_c0_finish", "k_verify_shared_inv",
-    "k_rprove_witness", "k_rprove_commit", "k_rprove_chain"};
+    "k_rprove_witness", "k_rprove_commit", "k_rprove_chain",
+    "k_agg_phase1", "k_agg_c0_fixed", "k_agg_c0_var", "k_agg_c0_finish"};
 
 static inline size_t align16(size_t x) { return (x + 15) / 16 * 16; }
 // a transcript label as the ABI takes it: a null pointer only with length 0, and no longer than merlin can frame (its length prefix is a

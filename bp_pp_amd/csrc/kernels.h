@@ -7,6 +7,7 @@
 #include "circuit_prove_core.h"
 #include "prove_core.h"
 #include "recip_core.h"
+#include "agg_core.h"
 #include "recip_prove_core.h"
 #include "bucket_core.h"
 #include "rlc_core.h"
@@ -239,6 +240,15 @@ __global__ __launch_bounds__(BPPP_BLOCK) void k_recip_c0_var(bppp::RecipWs w);
 __global__ __launch_bounds__(BPPP_BLOCK, BPPP_TABLES_MIN_WAVES) void k_recip_c0_tables(bppp::RecipWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_recip_c0_var_grp(bppp::RecipWs w, int group);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_recip_c0_finish(bppp::RecipWs w);
+// aggregated reciprocal range proof verifier (k_agg.hip, agg_core.h)
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_phase1(bppp::AggWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_phase1_grp(bppp::AggWs w, int G);
+__global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_agg_c0_fixed(bppp::AggWs w);
+__global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_agg_c0_fixed_l1(bppp::AggWs w);
+__global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_agg_c0_fixed_l64(bppp::AggWs w);
+__global__ __launch_bounds__(BPPP_BLOCK, BPPP_TABLES_MIN_WAVES) void k_agg_c0_tables(bppp::AggWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_c0_var(bppp::AggWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_c0_finish(bppp::AggWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_bkt_prepare(bppp::BucketWs w);
 __global__ __launch_bounds__(256) void k_bkt_accumulate(bppp::BucketWs w);
 __global__ __launch_bounds__(256) void k_bkt_scalars(bppp::BucketWs w);

@@ -31,6 +31,8 @@
 //               n <= 32 S        round-point tables and C0's variable-base sum on the helper stream beside phase 1 (2 blocks <= S)
 //               n >= 128 S       one lane per fixed-base sum
 //   circuit     n <= 16 S        C0's variable-base sum on a lane per point (L blocks <= 2 S; L = 8 for up to 8 points)
+//   aggregate   (the aggregated reciprocal range proof, agg_core.h) phase 1's lanes, `beside` and the one-lane fixed-base sums as for the
+//               reciprocal verifier; C0's variable-base sum over its 4 + k points on one lane per instance, five points per pass
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -258,7 +260,7 @@ struct GenericKnobs {
     int recip_beside = -1;             // diagnostic: the reciprocal verifier's one-lane kernels beside its fixed-base ones always (1) / never (0); -1 = by size
     int recip_p1_group = 0;            // diagnostic: 1 | 2 | 4 | 8 lanes per instance in the reciprocal verifier's phase 1; 0 = by size
 };
-enum { GENERIC_FORM_WNLA = 1, GENERIC_FORM_RECIPROCAL = 2, GENERIC_FORM_CIRCUIT = 3 };
+enum { GENERIC_FORM_WNLA = 1, GENERIC_FORM_RECIPROCAL = 2, GENERIC_FORM_CIRCUIT = 3, GENERIC_FORM_AGGREGATE = 4 };
 enum { GENERIC_FB_LANES8 = 0, GENERIC_FB_WAVEFRONT = 1, GENERIC_FB_ONE_LANE = 2 };
 
 struct GenericPlan {
@@ -268,15 +270,17 @@ struct GenericPlan {
     int round_group = 1;         // lanes per instance in the rounds
     int final_lg = 0;            // log2 of the lanes per instance in the final scalars
     int fb = GENERIC_FB_LANES8;  // lanes per fixed-base sum: GENERIC_FB_*
-    int c0var_group = 0;         // reciprocal: lanes per instance in C0's variable-base sum
-    int p1_group = 0;            // reciprocal: lanes per instance in phase 1
-    bool beside = false;         // reciprocal: the round-point tables and C0's variable-base sum on the helper stream, beside phase 1
+    int c0var_group = 0;         // reciprocal: lanes per instance in C0's variable-base sum (aggregate: always 1)
+    int p1_group = 0;            // reciprocal, aggregate: lanes per instance in phase 1
+    bool beside = false;         // reciprocal, aggregate: the round-point tables and C0's variable-base sum on the helper stream, beside phase 1
     int parts = 1;               // parts the call runs in (this is the plan of one of them)
     int c0_lanes = 0;            // circuit: lanes per instance of C0's variable-base sum on a lane per point (a power of two >= the points)
     bool per_point = false;      // circuit: C0's variable-base sum runs in that form
+    int c0_chunks = 0;           // aggregate: shared-doubling passes of C0's variable-base sum, ceil((4 + k) / 5)
     // "last_generic_form" (include/bppp.h has the bit layout): each choice as the value its launch is given
+    // (the protocol field has two bits: the aggregate verifier reads 0 there and sets bit 23)
     uint32_t code() const {
-        return (uint32_t)protocol | (uint32_t)tab_parts << 2 | (uint32_t)round_group << 5 | (uint32_t)final_lg << 10 | (uint32_t)fb << 12 |
+        return ((uint32_t)protocol & 3u) | (uint32_t)(protocol == GENERIC_FORM_AGGREGATE ? 1 : 0) << 23 | (uint32_t)tab_parts << 2 | (uint32_t)round_group << 5 | (uint32_t)final_lg << 10 | (uint32_t)fb << 12 |
                (uint32_t)p1_group << 14 | (uint32_t)(beside ? 1 : 0) << 18 | (uint32_t)parts << 19 | (uint32_t)(per_point ? 1 : 0) << 22;
     }
 };
@@ -296,7 +300,7 @@ inline int plan_generic_parts(size_t n, bool rlc, bool timing, int forced) {
 
 // n: instances of this call, or of this part of it; call_n: instances of the whole call (= n unless n_parts > 1) -- the lane-group
 // choices go by the wavefronts of the WHOLE call, because the parts of a multi-part call share the chip; a part takes neither table
-// parts nor the wavefront sums nor the helper stream (it is a chain on one stream).  c0_points: the circuit's 4 + k points of C0.
+// parts nor the wavefront sums nor the helper stream (it is a chain on one stream).  c0_points: the 4 + k points of C0 (circuit, aggregate).
 inline GenericPlan plan_generic(int protocol, size_t n, size_t rounds, const GenericKnobs& k, size_t call_n, int n_parts, size_t c0_points) {
     GenericPlan p;
     p.protocol = protocol;
@@ -326,11 +330,14 @@ inline GenericPlan plan_generic(int protocol, size_t n, size_t rounds, const Gen
     // configs[4]'s shape: k_wnla_msm 7.6 -> 0.86 ms, k_recip_c0_fixed 2.5 -> 0.32 ms; with phase 1 on lane groups the call 16.7 -> 6.1 ms
     // (round 6, profiles/r06/r06_p4_latency_recip256.txt).  By size, same shape on 16-bit tables: 2,048 instances 14.1 -> 8.4 ms, 4,096
     // 14.9 -> 11.2, 8,192 19.3 -> 18.6, 16,384 28.2 -> 28.7 (profiles/r06/r06_p5_fb_wide_sizes.txt): up to 8 S
-    const bool fb_one_lane = protocol == GENERIC_FORM_RECIPROCAL && (k.fb_one_lane_mode >= 0 ? k.fb_one_lane_mode == 1 : n >= 128 * S);
+    const bool recip_like = protocol == GENERIC_FORM_RECIPROCAL || protocol == GENERIC_FORM_AGGREGATE;
+    const bool fb_one_lane = recip_like && (k.fb_one_lane_mode >= 0 ? k.fb_one_lane_mode == 1 : n >= 128 * S);
     const bool fb_wide = !part && (k.fb_wide_max >= 0 ? n <= (size_t)k.fb_wide_max : split_ok && n <= 8 * S);
     p.fb = fb_one_lane ? GENERIC_FB_ONE_LANE : fb_wide ? GENERIC_FB_WAVEFRONT : GENERIC_FB_LANES8;
-    if (protocol == GENERIC_FORM_RECIPROCAL) {
-        p.c0var_group = p.round_group > 4 ? 4 : p.round_group;      // (C0's sum: lane groups of 2 or 4)
+    if (recip_like) {
+        // (C0's sum: lane groups of 2 or 4; the aggregate verifier's 4 + k points go five per pass on one lane)
+        p.c0var_group = protocol == GENERIC_FORM_AGGREGATE ? 1 : p.round_group > 4 ? 4 : p.round_group;
+        if (protocol == GENERIC_FORM_AGGREGATE) p.c0_chunks = (int)((c0_points + 4) / 5);
         // What needs nothing but the proof bytes -- the round points' window tables -- and what needs only phase 1 -- the C0 points' tables
         // and C0's variable-base sum, one lane (or a lane group) per instance -- runs on the HELPER stream beside phase 1 and the fixed-base
         // half of C0 (8 lanes per instance: the kernel that fills the chip); round 6: 2^15 instances of configs[4]'s shape, where the

@@ -15,6 +15,7 @@
 #include "../k_prove.hip"
 #include "../k_prove_w2.hip"
 #include "../k_generic.hip"
+#include "../k_agg.hip"
 #include "../k_gprove.hip"
 #include "../k_wire.hip"
 #include "../k_draw.hip"

@@ -175,7 +175,7 @@ class WeightNormLinearArgument:
         v = self.get_option("last_generic_form")
         if v == 0:
             return {}
-        return {"protocol": (None, "wnla", "reciprocal", "circuit")[v & 3], "tab_parts": v >> 2 & 7, "round_group": v >> 5 & 31,
+        return {"protocol": "aggregate" if v >> 23 & 1 else (None, "wnla", "reciprocal", "circuit")[v & 3], "tab_parts": v >> 2 & 7, "round_group": v >> 5 & 31,
                 "final_scalars_lg": v >> 10 & 3, "fixed_base": ("lanes8", "wavefront", "one_lane", None)[v >> 12 & 3],
                 "phase1_group": v >> 14 & 15, "beside": v >> 18 & 1, "parts": v >> 19 & 7, "per_point": v >> 22 & 1}
 
@@ -600,6 +600,63 @@ class ReciprocalRangeProofProtocol:
 
     def device_bytes(self) -> int:
         return int(_capi.lib().bppp_ctx_device_bytes(self._w._ctx))
+
+
+class AggregatedReciprocalRangeProofProtocol:
+    """k values of dim_nd base-dim_np digits under ONE reciprocal range proof (include/bppp.h: "AGGREGATED reciprocal range proofs";
+    bp_pp_amd/csrc/agg_core.h).  VERIFY ONLY, exact mode, 64-byte points: proofs come from elsewhere (the tests make them with the
+    oracle's circuit prover, tests/agg_cases.py).  k = 1 is ReciprocalRangeProofProtocol."""
+
+    def __init__(self, k: int, dim_nd: int, dim_np: int, g: bytes, g_vec, h_vec, g_vec_, h_vec_, device: int = 0, fb_window_bits: int = 0):
+        if len(g_vec) != k * dim_nd or len(h_vec) != dim_nd + 10:
+            raise ValueError("g_vec must hold k * dim_nd points and h_vec dim_nd + 10 (dim_nv + 9)")
+        self.k, self.dim_nd, self.dim_np = k, dim_nd, dim_np
+        self._w = WeightNormLinearArgument(g, list(g_vec) + list(g_vec_), list(h_vec) + list(h_vec_), device, fb_window_bits)
+
+    def close(self):
+        self._w.close()
+
+    def proof_shape(self):
+        """(rounds, nl, nn) of a proof over this context's generators."""
+        rounds, nl_f, nn_f = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _capi.lib().bppp_wnla_proof_shape(self._w.nh, self._w.ng, C.byref(rounds), C.byref(nl_f), C.byref(nn_f))
+        return rounds.value, nl_f.value, nn_f.value
+
+    def proof_bytes(self, rounds: int, nl: int, nn: int) -> int:
+        return int(_capi.symbol("bppp_reciprocal_agg_proof_bytes")(self.k, rounds, nl, nn))
+
+    def verify_batch(self, label: bytes, commitments, proofs, rounds: int, nl: int, nn: int):
+        """commitments [B, k, 64] (value-major), proofs [B, proof_bytes] -> (accept [B], status [B])."""
+        commitments = _u8(commitments, (-1, self.k, 64))
+        B = commitments.shape[0]
+        proofs = _u8(proofs, (B, self.proof_bytes(rounds, nl, nn)))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_verify_batch")(self._w._ctx, label, len(label), B, self.k, self.dim_nd, self.dim_np,
+                                                                     commitments.ctypes.data, proofs.ctypes.data, rounds, nl, nn,
+                                                                     acc.ctypes.data, st.ctypes.data))
+        return acc, st
+
+    def verify_batch_device(self, label: bytes, n: int, d_commitments: int, d_proofs: int, rounds: int, nl: int, nn: int, d_accept: int,
+                            d_status: int, d_reject_count: int = 0) -> None:
+        """The same over device buffers (raw device pointers; d_reject_count 0 = none), asynchronous on the context's stream."""
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_verify_batch_device")(self._w._ctx, label, len(label), n, self.k, self.dim_nd,
+                                                                            self.dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept,
+                                                                            d_status, d_reject_count or None))
+
+    def synchronize(self) -> None:
+        self._w.synchronize()
+
+    def set_option(self, name: str, value: int) -> None:
+        self._w.set_option(name, value)
+
+    def get_option(self, name: str) -> int:
+        return self._w.get_option(name)
+
+    def enable_timing(self, on: bool = True) -> None:
+        self._w.enable_timing(on)
+
+    def timings(self, reset: bool = True) -> dict:
+        return self._w.timings(reset)
 
 
 class ArithmeticCircuit:

@@ -145,7 +145,7 @@ BPPP_API int bppp_ctx_set_option(bppp_ctx* ctx, const char* name, long value);
  * bppp_reciprocal_verify_batch* (a reciprocal call of the u64 shape runs the u64 kernels, leaves this alone and sets "last_verify_plan")
  * -- written before the call's first launch, each field the value the launch was given; of a call that ran in parts, the last part's
  * form.  0 before the first such call.  Bits, from the low end:
- *    0 ..  1   protocol: 1 = WNLA, 2 = reciprocal, 3 = circuit
+ *    0 ..  1   protocol: 1 = WNLA, 2 = reciprocal, 3 = circuit, 0 with bit 23 set = the aggregated reciprocal verifier
  *    2 ..  4   sets of round-point tables: 4 | 2 (calls of up to n_simds | 4 n_simds instances) | 1
  *    5 ..  9   lanes per instance in the rounds: 16 | 8 (over 4 | 2 sets of tables) | 4 | 2 (up to 16 | 32 n_simds instances) | 1
  *   10 .. 11   log2 of the lanes per instance of the final scalars: 3 | 2 | 1 (up to 32 | 64 | 128 n_simds instances) | 0, and at
@@ -157,6 +157,8 @@ BPPP_API int bppp_ctx_set_option(bppp_ctx* ctx, const char* name, long value);
  *              one part, kernel timing off)
  *   19 .. 21   parts the call ran in ("generic_parts"; 1 unless reciprocal)
  *   22         circuit: 1 = C0's variable-base sum on a lane per point (up to 16 n_simds instances for up to 8 points)
+ *   23         1 = bppp_reciprocal_agg_verify_batch* (k > 1): bits 12 .. 18 read as for the reciprocal verifier; C0's variable-base sum
+ *              walks its 4 + k points five per pass on one lane per instance
  * The sizes are those of a default context: the diagnostic environment switches override them, and the field shows what was taken. */
 BPPP_API long bppp_ctx_get_option(bppp_ctx* ctx, const char* name);
 /* Which kernels a u64 verify (prove = 0) or prove (prove = 1) call of n proofs runs on a device of n_simds SIMDs (CUs x 4; MI355X: 1024):
@@ -674,6 +676,27 @@ BPPP_API int bppp_reciprocal_verify_batch_rlc_sharded_device(bppp_group* grp, co
 BPPP_API int bppp_reciprocal_verify_batch_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd,
                                                  size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
                                                  size_t nn, void* d_accept, void* d_status);
+/* AGGREGATED reciprocal range proofs: k values (1 <= k <= 64), each of dim_nd base-dim_np digits, under ONE proof -- the reciprocal
+ * circuit written for k values that share one multiplicity vector, verified by ArithmeticCircuit::verify over the k commitments
+ * V_i + R_i (tests/agg_cases.py states the circuit and the transcript on the oracle; bp_pp_amd/csrc/agg_core.h the closed forms).
+ * The context (bppp_wnla_ctx_create) holds at least k dim_nd generators in g_vec || g_vec_ and dim_nd + 10 in h_vec || h_vec_.
+ *   commitments  n x k x 64, value-major: V_i = x_i g + s_i h_vec[0]
+ *   proofs       n x bppp_reciprocal_agg_proof_bytes(k, rounds, nl, nn) = 64 (4 + 2 rounds + k) + 32 (nl + nn):
+ *                c_l c_r c_o c_s | r[rounds] | x[rounds] | R_0 .. R_{k-1} | l[nl] | n[nn]        (k = 1: the reciprocal proof's layout)
+ * accept / status as bppp_reciprocal_verify_batch; BPPP_ERR_INVALID_ARG, before anything touches the GPU, unless 1 <= k <= 64,
+ * k dim_nd <= |g_vec|, dim_nd + 10 <= |h_vec|, dim_np <= dim_nd + 1, rounds <= 12, nl, nn <= 4096.  k = 1 IS
+ * bppp_reciprocal_verify_batch[_device] (and so the u64 kernels for the u64 shape).  The device form takes device buffers (d_status
+ * required; d_reject_count: optional device int32, the number of rejected instances), is asynchronous on the context's stream and
+ * runs a call of more than "max_batch" instances as consecutive parts.  Verifier only, exact mode, 64-byte points: there is no
+ * aggregated prover, SEC1 form, RLC mode, caller-transcript form, sharded form or single-proof front end yet. */
+BPPP_API size_t bppp_reciprocal_agg_proof_bytes(size_t k, size_t rounds, size_t nl, size_t nn);
+BPPP_API int bppp_reciprocal_agg_verify_batch(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                              size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl,
+                                              size_t nn, uint8_t* accept, int32_t* status);
+BPPP_API int bppp_reciprocal_agg_verify_batch_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                     size_t dim_nd, size_t dim_np, const void* d_commitments, const void* d_proofs,
+                                                     size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status,
+                                                     void* d_reject_count);
 /* The optional random-linear-combination mode (as bppp_u64_verify_batch_rlc above) for the reciprocal verifier at any dimensions:
  * the final MSM over all 1 + |g_vec| + |h_vec| generators -- 769 bases for BASELINE configs[4]'s shape, about half of that
  * verifier's time -- is done once per chunk of 8 instances on secretly weighted sums; chunks that do not pass are re-checked
