@@ -56,6 +56,10 @@ EXPORTS += VALUES_EXPORTS
 # the aggregated reciprocal range proof verifier (include/bppp.h: "AGGREGATED reciprocal range proofs")
 AGG_EXPORTS = ["bppp_reciprocal_agg_proof_bytes", "bppp_reciprocal_agg_verify_batch", "bppp_reciprocal_agg_verify_batch_device"]
 EXPORTS += AGG_EXPORTS
+# the aggregated reciprocal range proof prover from integers (include/bppp.h: "AGGREGATED range proofs from integers")
+AGG_PROVE_EXPORTS = ["bppp_reciprocal_agg_prove_draws", "bppp_reciprocal_agg_prove_values_batch", "bppp_reciprocal_agg_prove_values_batch_seeded",
+                     "bppp_reciprocal_agg_prove_values_batch_device", "bppp_reciprocal_agg_prove_values_batch_seeded_device"]
+EXPORTS += AGG_PROVE_EXPORTS
 
 # the entry points of the wire form's RLC mode and single-proof front end (a subset of EXPORTS)
 RLC_SEC1_EXPORTS = [name for name in EXPORTS if name.endswith(("_rlc_sec1", "_rlc_sec1_device")) or "_one_sec1" in name]
@@ -273,6 +277,15 @@ def lib():
         L.bppp_reciprocal_agg_verify_batch.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp]
         L.bppp_reciprocal_agg_verify_batch_device.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, vp]
         L.bppp_reciprocal_agg_verify_batch.restype = L.bppp_reciprocal_agg_verify_batch_device.restype = i32
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_reciprocal_agg_prove_values_batch"):
+        L.bppp_reciprocal_agg_prove_draws.argtypes = [sz, sz]
+        L.bppp_reciprocal_agg_prove_draws.restype = sz
+        L.bppp_reciprocal_agg_prove_values_batch.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_seeded.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_device.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_seeded_device.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        for name in AGG_PROVE_EXPORTS[1:]:
+            getattr(L, name).restype = i32
     L.bppp_strerror.argtypes = [i32]
     L.bppp_strerror.restype = C.c_char_p
     L.bppp_last_error.restype = C.c_char_p

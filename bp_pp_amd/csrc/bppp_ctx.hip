@@ -328,6 +328,7 @@ void bppp_ctx_destroy(bppp_ctx* c) {
     if (c->d_blob) (void)hipFree(c->d_blob);
     if (c->d_txio) (void)hipFree(c->d_txio);
     for (auto& rp : c->recip_patterns) if (rp.d) (void)hipFree(rp.d);
+    for (auto& ap : c->agg_prove_shapes) if (ap.d) (void)hipFree(ap.d);
     if (c->d_gws) (void)hipFree(c->d_gws);
     if (c->d_gtab) (void)hipFree(c->d_gtab);
     if (c->d_expand) (void)hipFree(c->d_expand);

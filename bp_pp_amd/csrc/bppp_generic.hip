@@ -2033,5 +2033,238 @@ int bppp_reciprocal_prove_values_batch_seeded_device(bppp_ctx* c, const uint8_t*
                             nullptr, (uint8_t*)d_proofs, (int32_t*)d_status, false, seed, stream_base, &v);
 }
 
+// ---------------------------------------------------------------- aggregated reciprocal range proof: the prover from integers
+// (agg_prove_core.h has the stages; tests/agg_cases.py::prove states the protocol on the oracle).  k = 1 IS the reciprocal prover from
+// integers and goes to its entry points.
+static int agg_prove_shape_get(bppp_ctx* c, size_t k, size_t nd, size_t np, AggProveShapeDev& out) {
+    for (const AggProveShapeDev& ap : c->agg_prove_shapes)
+        if (ap.k == k && ap.nd == nd && ap.np == np) { out = ap; return BPPP_OK; }
+    AggProveShape P;
+    agg_prove_shape_build(P, k, nd, np);
+    AggProveShapeDev ap;
+    std::memset(&ap, 0, sizeof ap);
+    ap.k = k; ap.nd = nd; ap.np = np;
+    size_t off = 0;
+    ap.part = take_bytes(off, P.parts.size() * 4 + 16); ap.al = take_bytes(off, P.al.size() * 4 + 16); ap.am = take_bytes(off, P.am.size() * 4 + 16);
+    std::vector<uint8_t> host(off, 0);
+    std::memcpy(host.data() + ap.part, P.parts.data(), P.parts.size() * 4);
+    std::memcpy(host.data() + ap.al, P.al.data(), P.al.size() * 4);
+    std::memcpy(host.data() + ap.am, P.am.data(), P.am.size() * 4);
+    HIP_TRY(ctx_malloc(c, (void**)&ap.d, off));
+    const hipError_t e = hipMemcpy(ap.d, host.data(), off, hipMemcpyHostToDevice);      // (synchronous: the host vector lives on this frame)
+    if (e != hipSuccess) { (void)hipFree(ap.d); HIP_TRY(e); }
+    c->agg_prove_shapes.push_back(ap);
+    out = ap;
+    return BPPP_OK;
+}
+// where one part's buffers sit in the context's blob
+struct AggProveLayout {
+    size_t x, s, rnd, com, dig, m, st, rst, vsc, vpb, ts, inst, scr, rsc, rpb, vsum, cpv, cpsv, cpwr, cpvp, prR, head, pout, cout;
+    CircuitProveBufs c;
+    WnlaProveBufs w;
+    size_t total;
+};
+static AggProveLayout agg_prove_layout(const bppp_ctx* c, size_t n, size_t k, size_t nd, size_t np, const WnlaProveShape& sh, size_t proof_bytes) {
+    const size_t nm = k * nd, nv = nd + 1, rows = n * k, n_rnd = agg_prove_draws(k, nd);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { return take_bytes(off, bytes + 16); };
+    AggProveLayout o;
+    o.x = take(rows * 32); o.s = take(rows * 32); o.rnd = take(n * n_rnd * 32); o.com = take(rows * 64); o.dig = take(n * nm * 32);
+    o.m = take(n * np * 32); o.st = take(n * 4); o.rst = take(rows * 4); o.vsc = take(2 * 8 * rows * 4); o.vpb = take(30 * rows * 4);
+    o.ts = take(52 * n * 4); o.inst = take((2 + np) * 8 * n * 4); o.scr = take((nm + np) * 8 * n * 4); o.rsc = take(nv * 8 * rows * 4);
+    o.rpb = take(30 * rows * 4); o.vsum = take(k * 50 * n * 4); o.cpv = take(rows * nv * 32); o.cpsv = take(rows * 32);
+    o.cpwr = take(n * nm * 32); o.cpvp = take(rows * 64); o.prR = take(rows * 64); o.head = take(n * 256);
+    o.c = circuit_prove_take(off, c, n, nm, nv, k * nv);
+    WnlaProveShape shn = sh;
+    shn.n = n;
+    wnla_prove_take_proof(o.w, off, shn, 16);
+    wnla_prove_take_state(o.w, off, c, shn, 16);
+    o.pout = take(n * proof_bytes); o.cout = take(rows * 64);
+    o.total = off;
+    return o;
+}
+// Instances per part: "max_batch" bounds the multiplication gates (k dim_nd per instance) whose vectors a part holds -- the circuit
+// prover keeps about two dozen scalar vectors of that length, three scalar sets over all generators and the WNLA prover's state,
+// roughly 150-200 KB per instance at (16, 16, 16) -- so the default 2^21 gives 2^13 instances of that shape, about 1.6 GB.
+static size_t agg_prove_part_size(const bppp_ctx* c, size_t n, size_t k, size_t nd) {
+    size_t per = c->max_batch / (k * nd);
+    if (per < 1) per = 1;
+    return n < per ? n : per;
+}
+// one part of m instances: the launch chain on the context's stream.  Host forms: inputs uploaded into the blob, outputs copied back
+// (queued; the caller waits).  Device forms: x, s, rnd, proofs, commitments, status used where they are.
+static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t m, size_t k, size_t nd, size_t np, const AggProveShapeDev& shp,
+                          const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd, const uint8_t* seed, uint64_t stream, uint8_t* proofs,
+                          uint8_t* commitments, int32_t* status, bool device_io, const WnlaProveShape& sh0, size_t proof_bytes) {
+    const size_t n = m, nm = k * nd, nv = nd + 1, rows = n * k, n_rnd = agg_prove_draws(k, nd);
+    WnlaProveShape sh = sh0;
+    sh.n = n;
+    const AggProveLayout o = agg_prove_layout(c, n, k, nd, np, sh, proof_bytes);
+    uint8_t* d = c->d_blob;
+    hipStream_t s = c->stream;
+    int rc = BPPP_OK;
+    if (!device_io) {
+        HIP_TRY(hipMemcpyAsync(d + o.x, x, rows * 32, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d + o.s, sblind, rows * 32, hipMemcpyHostToDevice, s));
+    }
+    DrawWipe wipe = {seed ? d + o.rnd : nullptr, n * n_rnd * 32, s};
+    if (seed) { const int rc_d = draw_enqueue(s, seed, stream, n, n_rnd, d + o.rnd); if (rc_d != BPPP_OK) return rc_d; }
+    else if (!device_io) HIP_TRY(hipMemcpyAsync(d + o.rnd, rnd, n * n_rnd * 32, hipMemcpyHostToDevice, s));
+    AggProveWs a;
+    std::memset(&a, 0, sizeof a);
+    a.N = n; a.k = (int)k; a.nd = (int)nd; a.np = (int)np; a.NG = c->ng; a.NH = c->nh; a.n_rnd = (int)n_rnd;
+    recip_witness_shape(a.rw, nd, np);
+    a.x = device_io ? x : d + o.x; a.s = device_io ? sblind : d + o.s; a.rnd = (device_io && !seed) ? rnd : d + o.rnd;
+    a.digits = d + o.dig; a.m = d + o.m; a.status = (int32_t*)(d + o.st); a.row_status = (int32_t*)(d + o.rst); a.vsc = (u32*)(d + o.vsc);
+    a.commitments = d + o.com; a.tstate = (u32*)(d + o.ts); a.inst_vals = (u32*)(d + o.inst); a.scr = (u32*)(d + o.scr);
+    a.rsc = (u32*)(d + o.rsc); a.rpb = (u32*)(d + o.rpb); a.vsum = (u32*)(d + o.vsum);
+    a.cp_v = d + o.cpv; a.cp_sv = d + o.cpsv; a.cp_wr = d + o.cpwr; a.cp_vpts = d + o.cpvp; a.proof_R = d + o.prR;
+    a.fb = fb_table_of(c, rows);
+    { const int rc_ct = ct_setup(c, a.fb_ct, a.ct, rows); if (rc_ct != BPPP_OK) return rc_ct; }      // x_i, s_i, rb_i and the reciprocals are secret
+    t_new(a.base, label, (u32)label_len);
+    // the value commitments: the reciprocal prover's commitment kernels over N k rows
+    RecipCommitWs cw;
+    std::memset(&cw, 0, sizeof cw);
+    cw.N = rows; cw.NG = c->ng; cw.x = a.x; cw.s = a.s; cw.status = a.row_status; cw.msc = a.vsc; cw.pbuf = (u32*)(d + o.vpb); cw.out = d + o.com;
+    cw.fb = a.fb; cw.fb_ct = a.fb_ct; cw.ct = a.ct;
+    // the circuit prover on the aggregate's circuit: closed-form collect, so no pattern
+    CircuitProveWs p;
+    std::memset(&p, 0, sizeof p);
+    p.base = a.base;
+    CircuitDev& cd = p.cd;
+    cd.nm = (int)nm; cd.no = (int)np; cd.k = (int)k; cd.nl = (int)(k * nv); cd.nv = (int)nv; cd.nw = (int)(2 * nm + np); cd.f_l = 1; cd.f_m = 0;
+    cd.a_l = (const u32*)(shp.d + shp.al); cd.a_m = (const u32*)(shp.d + shp.am); cd.inst_vals = a.inst_vals;
+    p.N = n; p.NG = c->ng; p.NH = c->nh; p.n_rnd = (int)(18 + nv + nm); p.rnd_stride = n_rnd * 32; p.part = (const int*)(shp.d + shp.part);
+    p.transcript_preloaded = 1;
+    p.v_pts = a.cp_vpts; p.v = a.cp_v; p.s_v = a.cp_sv; p.w_l = a.digits; p.w_r = a.cp_wr; p.w_o = a.m; p.rnd = a.rnd + 32 * k;
+    p.proof_head = d + o.head; p.status = a.status; p.tstate = a.tstate;
+    circuit_prove_carve(p, d, o.c);
+    p.fb = fb_table_of(c, n);
+    { const int rc_ct = ct_setup(c, p.fb_ct, p.ct, n); if (rc_ct != BPPP_OK) return rc_ct; }
+    WnlaProveWs w;
+    rc = wnla_prove_fill_behind(c, w, sh, d, o.w, p);
+    if (rc != BPPP_OK) return rc;
+    const unsigned blocks = blocks_of(n), fb_blocks = fb_blocks_of(n), row_blocks = blocks_of(rows), row_fb_blocks = fb_blocks_of(rows);
+    GLAUNCH(s, K_APROVE_WITNESS, k_aprove_witness<<<blocks, BPPP_BLOCK, 0, s>>>(a));
+    GLAUNCH(s, K_APROVE_COMMIT, {
+        k_rprove_commit<<<row_fb_blocks, BPPP_FB_BLOCK, 0, s>>>(cw);
+        k_rprove_commit_store<<<row_blocks, BPPP_BLOCK, 0, s>>>(cw);
+    });
+    GLAUNCH(s, K_APROVE_POLES, {
+        k_aprove_stage_r1<<<blocks, BPPP_BLOCK, 0, s>>>(a);
+        k_aprove_msm<<<row_fb_blocks, BPPP_FB_BLOCK, 0, s>>>(a);
+        k_aprove_stage_r2<<<blocks, BPPP_BLOCK, 0, s>>>(a);
+    });
+    HIP_TRY(hipMemsetAsync(p.msc, 0, 3 * (size_t)c->nbases * 8 * n * 4, s));     // the sets are written sparsely (slot = base index)
+    GLAUNCH(s, K_APROVE_STAGE_A, {
+        k_cprove_stage_a<<<blocks, BPPP_BLOCK, 0, s>>>(p);
+        for (int set = 0; set < 3; set++) k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, set, 0);
+    });
+    GLAUNCH(s, K_APROVE_STAGE_B, k_aprove_stage_b<<<blocks, BPPP_BLOCK, 0, s>>>(p));
+    if (c->timing) GLAUNCH(s, K_APROVE_COLLECT, k_aprove_collect<<<blocks, BPPP_BLOCK, 0, s>>>(p));      // (same values again: its time alone)
+    GLAUNCH(s, K_APROVE_TAIL, {
+        k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 0);
+        k_cprove_stage_c<<<blocks, BPPP_BLOCK, 0, s>>>(p);
+        k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 1);
+        k_cprove_stage_d<<<blocks, BPPP_BLOCK, 0, s>>>(p);
+        wnla_prove_launch(w, s);
+    });
+    HIP_TRY(hipGetLastError());
+    // the proofs put together on the device (a flagged instance as zero bytes); a flagged instance's commitments zeroed by the same kernel
+    ProofAssembleWs as;
+    std::memset(&as, 0, sizeof as);
+    as.N = n; as.proof_bytes = proof_bytes; as.nseg = 6; as.status = p.status; as.out = device_io ? proofs : d + o.pout;
+    as.src[0] = p.proof_head; as.bytes[0] = 256;
+    as.src[1] = w.proof_r; as.bytes[1] = (u32)(sh.rounds * 64);
+    as.src[2] = w.proof_x; as.bytes[2] = (u32)(sh.rounds * 64);
+    as.src[3] = a.proof_R; as.bytes[3] = (u32)(k * 64);
+    as.src[4] = w.proof_l; as.bytes[4] = (u32)(sh.nl_f * 32);
+    as.src[5] = w.proof_n; as.bytes[5] = (u32)(sh.nn_f * 32);
+    size_t words = n * (proof_bytes / 4);
+    if ((words + 255) / 256 > 0xFFFFFFFFu) return BPPP_ERR_INVALID_ARG;
+    k_gprove_assemble<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(as);
+    // the commitments through the same kernel: one segment of k x 64 bytes, so that a status raised behind the witness stage zeroes them too
+    ProofAssembleWs ac;
+    std::memset(&ac, 0, sizeof ac);
+    ac.N = n; ac.proof_bytes = k * 64; ac.nseg = 1; ac.status = p.status; ac.out = device_io ? commitments : d + o.cout;
+    ac.src[0] = d + o.com; ac.bytes[0] = (u32)(k * 64);
+    words = n * (k * 16);
+    k_gprove_assemble<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(ac);
+    HIP_TRY(hipGetLastError());
+    if (!device_io) {
+        HIP_TRY(hipMemcpyAsync(proofs, d + o.pout, n * proof_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(commitments, d + o.cout, rows * 64, hipMemcpyDeviceToHost, s));
+    }
+    if (status) HIP_TRY(hipMemcpyAsync(status, p.status, n * 4, device_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
+    return BPPP_OK;
+}
+static int agg_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t nd, size_t np, const uint8_t* x,
+                          const uint8_t* sblind, const uint8_t* rnd, const uint8_t* seed, uint64_t stream_base, uint8_t* proofs,
+                          uint8_t* commitments, int32_t* status, bool device_io) {
+    if (!c || !label_ok(label, label_len) || !x || !sblind || (!rnd && !seed) || !proofs || !commitments) return BPPP_ERR_INVALID_ARG;
+    if (!agg_prove_shape_ok(k, nd, np, (size_t)c->ng, (size_t)c->nh)) return BPPP_ERR_INVALID_ARG;
+    const size_t n_rnd = agg_prove_draws(k, nd);
+    if (seed && !draw_args_ok(seed, stream_base, n, n_rnd)) return BPPP_ERR_INVALID_ARG;
+    if (k == 1) {
+        const RecipValues v = {device_io, commitments};
+        return recip_prove_impl(c, label, label_len, nullptr, n, nd, np, nullptr, x, sblind, nullptr, nullptr, rnd, proofs, status, false, seed,
+                                stream_base, &v);
+    }
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    AggProveShapeDev shp;
+    { const int rc_s = agg_prove_shape_get(c, k, nd, np, shp); if (rc_s != BPPP_OK) return rc_s; }
+    WnlaProveShape sh = {0, (size_t)c->nh, (size_t)c->ng, 0, 0, 0};
+    wnla_proof_shape(sh.nl, sh.nn, sh.rounds, sh.nl_f, sh.nn_f);
+    const size_t proof_bytes = agg_proof_bytes(k, sh.rounds, sh.nl_f, sh.nn_f);
+    const size_t per = agg_prove_part_size(c, n, k, nd);
+    sh.n = per;
+    WnlaBlob blob;      // host forms: nothing of the call still runs when it returns, whichever way it leaves
+    const size_t blob_bytes = agg_prove_layout(c, per, k, nd, np, sh, proof_bytes).total;
+    if (device_io) { const int rc_b = ensure_blob(c, blob_bytes); if (rc_b != BPPP_OK) return rc_b; }
+    else { const int rc_b = blob.take(c, blob_bytes); if (rc_b != BPPP_OK) return rc_b; }
+    for (size_t lo = 0; lo < n; lo += per) {
+        const size_t m = n - lo < per ? n - lo : per;
+        const int rc = agg_prove_part(c, label, label_len, m, k, nd, np, shp, x + lo * k * 32, sblind + lo * k * 32,
+                                      rnd ? rnd + lo * n_rnd * 32 : nullptr, seed, stream_base + lo, proofs + lo * proof_bytes,
+                                      commitments + lo * k * 64, status ? status + lo : nullptr, device_io, sh, proof_bytes);
+        if (rc != BPPP_OK) return rc;
+    }
+    if (!device_io) HIP_TRY(hipStreamSynchronize(c->stream));
+    return BPPP_OK;
+}
+size_t bppp_reciprocal_agg_prove_draws(size_t k, size_t dim_nd) { return agg_prove_draws(k, dim_nd); }
+int bppp_reciprocal_agg_prove_values_batch(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                                           const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd, uint8_t* proofs, uint8_t* commitments,
+                                           int32_t* status) {
+    CtxLock lock_(c);
+    if (!rnd) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_impl(c, label, label_len, n, k, dim_nd, dim_np, x, sblind, rnd, nullptr, 0, proofs, commitments, status, false);
+}
+int bppp_reciprocal_agg_prove_values_batch_seeded(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                  size_t dim_np, const uint8_t* x, const uint8_t* sblind, const uint8_t seed[32],
+                                                  uint64_t stream_base, uint8_t* proofs, uint8_t* commitments, int32_t* status) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_impl(c, label, label_len, n, k, dim_nd, dim_np, x, sblind, nullptr, seed, stream_base, proofs, commitments, status, false);
+}
+int bppp_reciprocal_agg_prove_values_batch_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                  size_t dim_np, const void* d_x, const void* d_s, const void* d_rnd, void* d_proofs,
+                                                  void* d_commitments, void* d_status) {
+    CtxLock lock_(c);
+    if (!d_rnd) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_impl(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_x, (const uint8_t*)d_s, (const uint8_t*)d_rnd, nullptr, 0,
+                          (uint8_t*)d_proofs, (uint8_t*)d_commitments, (int32_t*)d_status, true);
+}
+int bppp_reciprocal_agg_prove_values_batch_seeded_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                         size_t dim_np, const void* d_x, const void* d_s, const uint8_t seed[32],
+                                                         uint64_t stream_base, void* d_proofs, void* d_commitments, void* d_status) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_impl(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_x, (const uint8_t*)d_s, nullptr, seed, stream_base,
+                          (uint8_t*)d_proofs, (uint8_t*)d_commitments, (int32_t*)d_status, true);
+}
+
 }  // extern "C"
 #undef GLAUNCH

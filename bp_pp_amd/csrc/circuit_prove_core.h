@@ -118,7 +118,16 @@ HD void circuit_prove_stage_a(const CircuitProveWs& w, size_t t) {
     w.status[t] = w.transcript_preloaded ? (w.status[t] | st) : st;
 }
 // ---- stage B: c_o, c_l, c_r -> affine + transcript, challenges, coefficient vectors, f polynomial, r_s, scalar set of c_s (set 0)
-HD void circuit_prove_stage_b(const CircuitProveWs& w, size_t t) {
+// collect: what fills lamv, muv and coef -- circuit_collect's walk over the circuit's pattern, or a protocol's closed forms
+// (agg_prove_core.h).  A functor type with an HD operator(), so that it stays inlined into the stage.
+struct CircuitCollectWalk {
+    HD void operator()(const CircuitDev& cd, u32* lamv, u32* muv, u32* coef, size_t N, size_t t, const sc& lambda, const sc& mu, const sc& mu_inv,
+                       sc& lam_nv, sc& mu_nv) const {
+        circuit_collect(cd, lamv, muv, coef, N, t, lambda, mu, mu_inv, lam_nv, mu_nv);
+    }
+};
+template <typename Collect>
+HD void circuit_prove_stage_b_with(const CircuitProveWs& w, size_t t, const Collect& collect) {
     const size_t N = w.N;
     const CircuitDev& cd = w.cd;
     const int nm = cd.nm, nv = cd.nv, k = cd.k;
@@ -174,7 +183,7 @@ HD void circuit_prove_stage_b(const CircuitProveWs& w, size_t t) {
     cp_st(w.misc, w, t, CM_RHO, rho); cp_st(w.misc, w, t, CM_LAMBDA, lambda); cp_st(w.misc, w, t, CM_BETA, beta);
     cp_st(w.misc, w, t, CM_DELTA, delta); cp_st(w.misc, w, t, CM_MU, mu); cp_st(w.misc, w, t, CM_DINV, delta_inv);
     sc lam_nv, mu_nv;
-    circuit_collect(cd, w.lamv, w.muv, w.coef, N, t, lambda, mu, mu_inv, lam_nv, mu_nv);
+    collect(cd, w.lamv, w.muv, w.coef, N, t, lambda, mu, mu_inv, lam_nv, mu_nv);
     // v_0, r_v[0], v_1 = 2 sum_i coef_i (v_i[0], s_v[i], v_i[1..])                               (circuit.rs:376-392)
     sc v0 = zero, rv0 = zero;
 #pragma nounroll
@@ -313,6 +322,7 @@ HD void circuit_prove_stage_b(const CircuitProveWs& w, size_t t) {
     for (int i = 0; i < 9; i++) cp_st(w.rs, w, t, i, rs[i]);
     cp_fill_hg(w, t, 0, w.rs, w.ls, w.ns);
 }
+HD void circuit_prove_stage_b(const CircuitProveWs& w, size_t t) { circuit_prove_stage_b_with(w, t, CircuitCollectWalk()); }
 // ---- stage C: c_s -> affine + transcript, tau, the WNLA witness (l, n), c, and the WNLA commitment's scalar set (set 0)
 HD void circuit_prove_stage_c(const CircuitProveWs& w, size_t t) {
     const size_t N = w.N;

@@ -44,6 +44,9 @@ enum KernelId {
     // reciprocal prover from integers (bppp_reciprocal_prove_values_batch*): the witness kernel | the value commitment | everything behind them
     K_RPROVE_WITNESS, K_RPROVE_COMMIT, K_RPROVE_CHAIN,
     K_AGG_PHASE1, K_AGG_C0_FIXED, K_AGG_C0_VAR, K_AGG_C0_FINISH,      // aggregated reciprocal verifier (then the K_WNLA_* stage)
+    // aggregated reciprocal prover (bppp_reciprocal_agg_prove_values_batch*): witness | value commitments | r1, pole commitments, r2 |
+    // stage A and its sums | stage B | the closed-form collect alone (a rerun, only when timing is on) | everything behind stage B
+    K_APROVE_WITNESS, K_APROVE_COMMIT, K_APROVE_POLES, K_APROVE_STAGE_A, K_APROVE_STAGE_B, K_APROVE_COLLECT, K_APROVE_TAIL,
     K_COUNT
 };
 static const char* const kKernelNames[K_COUNT] = {
@@ -54,7 +57,8 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_wnla_msm", "k_wnla_accept", "k_wnla_rlc_lhs", "k_wnla_rlc_chunk", "k_wnla_rlc_check", "k_wnla_tables",
     "k_circuit_phase1", "k_circuit_c0_fixed", "k_circuit_c0_var", "k_circuit_c0_finish", "k_verify_shared_inv",
     "k_rprove_witness", "k_rprove_commit", "k_rprove_chain",
-    "k_agg_phase1", "k_agg_c0_fixed", "k_agg_c0_var", "k_agg_c0_finish"};
+    "k_agg_phase1", "k_agg_c0_fixed", "k_agg_c0_var", "k_agg_c0_finish",
+    "k_aprove_witness", "k_aprove_commit", "k_aprove_poles", "k_aprove_stage_a", "k_aprove_stage_b", "k_aprove_collect", "k_aprove_tail"};
 
 static inline size_t align16(size_t x) { return (x + 15) / 16 * 16; }
 // a transcript label as the ABI takes it: a null pointer only with length 0, and no longer than merlin can frame (its length prefix is a
@@ -69,6 +73,14 @@ struct RecipPatternDev {
     size_t nd, np, nw;
     uint8_t* d;
     size_t cpl, rl, vl, cpm, rm, vm, cmp, al, am, il, im, part;
+};
+
+// What the aggregated reciprocal prover's generic stages read of its circuit besides the closed forms (agg_prove_core.h: AggProveShape)
+// for one (k, dim_nd, dim_np) in device memory: uploaded at the first prove call of the shape, kept until the context goes.
+struct AggProveShapeDev {
+    size_t k, nd, np;
+    uint8_t* d;
+    size_t part, al, am;
 };
 
 struct bppp_ctx {
@@ -140,6 +152,7 @@ struct bppp_ctx {
     size_t blob_bytes = 0;
     uint8_t* d_txio = nullptr;   // transcripts in / out of a generic prover call
     size_t txio_bytes = 0;
+    std::vector<AggProveShapeDev> agg_prove_shapes;   // the aggregated reciprocal prover's, one per shape proved on this context
     std::vector<RecipPatternDev> recip_patterns;      // the reciprocal prover's circuit patterns, one per shape proved on this context
     int inject_alloc_fault = 0;  // testing aid ("inject_alloc_fault"): the k-th device allocation from now on fails
     uint8_t* d_gws = nullptr;    // workspace of bppp_reciprocal_verify_batch_device

@@ -9,6 +9,7 @@
 #include "recip_core.h"
 #include "agg_core.h"
 #include "recip_prove_core.h"
+#include "agg_prove_core.h"
 #include "bucket_core.h"
 #include "rlc_core.h"
 #include "wnla_rlc_core.h"
@@ -249,6 +250,13 @@ __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_agg_c0_fix
 __global__ __launch_bounds__(BPPP_BLOCK, BPPP_TABLES_MIN_WAVES) void k_agg_c0_tables(bppp::AggWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_agg_c0_var(bppp::AggWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_agg_c0_finish(bppp::AggWs w);
+// aggregated reciprocal range proof prover (k_aggprove.hip, agg_prove_core.h)
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_witness(bppp::AggProveWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_r1(bppp::AggProveWs w);
+__global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_aprove_msm(bppp::AggProveWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_r2(bppp::AggProveWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_b(bppp::CircuitProveWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_collect(bppp::CircuitProveWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_bkt_prepare(bppp::BucketWs w);
 __global__ __launch_bounds__(256) void k_bkt_accumulate(bppp::BucketWs w);
 __global__ __launch_bounds__(256) void k_bkt_scalars(bppp::BucketWs w);

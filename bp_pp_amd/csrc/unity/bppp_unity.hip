@@ -17,5 +17,6 @@
 #include "../k_generic.hip"
 #include "../k_agg.hip"
 #include "../k_gprove.hip"
+#include "../k_aggprove.hip"
 #include "../k_wire.hip"
 #include "../k_draw.hip"

@@ -61,7 +61,7 @@ def derive_generators(seed: bytes, n: int = 49, first_index: int = 0) -> bytes:
 
 def ctx_timings(ctx, reset: bool = True) -> dict:
     """Per-kernel HIP-event times accumulated by a context since the last reset (bppp_ctx_enable_timing / _get_timings)."""
-    cap = 48
+    cap = 96
     names = (C.c_char_p * cap)()
     ms = (C.c_double * cap)()
     cnt = (C.c_int64 * cap)()

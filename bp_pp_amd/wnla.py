@@ -604,8 +604,10 @@ class ReciprocalRangeProofProtocol:
 
 class AggregatedReciprocalRangeProofProtocol:
     """k values of dim_nd base-dim_np digits under ONE reciprocal range proof (include/bppp.h: "AGGREGATED reciprocal range proofs";
-    bp_pp_amd/csrc/agg_core.h).  VERIFY ONLY, exact mode, 64-byte points: proofs come from elsewhere (the tests make them with the
-    oracle's circuit prover, tests/agg_cases.py).  k = 1 is ReciprocalRangeProofProtocol."""
+    bp_pp_amd/csrc/agg_core.h, agg_prove_core.h).  Exact mode, 64-byte points.  The verifier takes commitments [B, k, 64] and proofs; the
+    prover takes the integers: prove_values_batch* make the k value commitments and the proof on the device (include/bppp.h:
+    "AGGREGATED range proofs from integers"; tests/agg_cases.py states the protocol on the oracle).  k = 1 is
+    ReciprocalRangeProofProtocol."""
 
     def __init__(self, k: int, dim_nd: int, dim_np: int, g: bytes, g_vec, h_vec, g_vec_, h_vec_, device: int = 0, fb_window_bits: int = 0):
         if len(g_vec) != k * dim_nd or len(h_vec) != dim_nd + 10:
@@ -624,6 +626,54 @@ class AggregatedReciprocalRangeProofProtocol:
 
     def proof_bytes(self, rounds: int, nl: int, nn: int) -> int:
         return int(_capi.symbol("bppp_reciprocal_agg_proof_bytes")(self.k, rounds, nl, nn))
+
+    def prove_draws(self) -> int:
+        """Draws per instance: rb_0 .. rb_{k-1}, then the circuit prover's 18 + (dim_nd + 1) + k dim_nd."""
+        return int(_capi.symbol("bppp_reciprocal_agg_prove_draws")(self.k, self.dim_nd))
+
+    def prove_values_batch(self, label: bytes, x, s, rnd):
+        """x / s [B, k, 32] big-endian integers and blindings (value-major), rnd [B, prove_draws(), 32] -> (proofs [B, proof_bytes],
+        commitments [B, k, 64], status [B], (rounds, nl, nn)).  Any x_i >= dim_np^dim_nd gives ST_OUT_OF_RANGE for the instance: a
+        zeroed proof and k zeroed commitments."""
+        x, s = _u8(x, (-1, self.k, 32)), _u8(s, (-1, self.k, 32))
+        B = x.shape[0]
+        rnd = _u8(rnd, (B, self.prove_draws(), 32))
+        shape = self.proof_shape()
+        proofs, com, st = np.zeros((B, self.proof_bytes(*shape)), np.uint8), np.zeros((B, self.k, 64), np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch")(self._w._ctx, label, len(label), B, self.k, self.dim_nd, self.dim_np,
+                                                                           x.ctypes.data, s.ctypes.data, rnd.ctypes.data, proofs.ctypes.data,
+                                                                           com.ctypes.data, st.ctypes.data))
+        return proofs, com, st, shape
+
+    def prove_values_batch_seeded(self, label: bytes, x, s, seed: bytes, stream_base: int):
+        """prove_values_batch with instance i's draws taken from ChaCha20 stream stream_base + i of `seed` on the device."""
+        from .range_proof import _seed_args
+        x, s = _u8(x, (-1, self.k, 32)), _u8(s, (-1, self.k, 32))
+        B = x.shape[0]
+        seed, stream_base = _seed_args(seed, stream_base, B)
+        shape = self.proof_shape()
+        proofs, com, st = np.zeros((B, self.proof_bytes(*shape)), np.uint8), np.zeros((B, self.k, 64), np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_seeded")(self._w._ctx, label, len(label), B, self.k, self.dim_nd,
+                                                                                  self.dim_np, x.ctypes.data, s.ctypes.data, seed, stream_base,
+                                                                                  proofs.ctypes.data, com.ctypes.data, st.ctypes.data))
+        return proofs, com, st, shape
+
+    def prove_values_batch_device(self, label: bytes, n: int, d_x: int, d_s: int, d_rnd: int, d_proofs: int, d_commitments: int,
+                                  d_status: int = 0) -> None:
+        """prove_values_batch over device buffers (raw device addresses, layouts as above; d_status 0 = none); asynchronous on the
+        context's stream."""
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_device")(self._w._ctx, label, len(label), n, self.k, self.dim_nd,
+                                                                                  self.dim_np, d_x, d_s, d_rnd, d_proofs, d_commitments,
+                                                                                  d_status or None))
+
+    def prove_values_batch_seeded_device(self, label: bytes, n: int, d_x: int, d_s: int, seed: bytes, stream_base: int, d_proofs: int,
+                                         d_commitments: int, d_status: int = 0) -> None:
+        """prove_values_batch_seeded over device buffers (raw device addresses); asynchronous on the context's stream."""
+        from .range_proof import _seed_args
+        seed, stream_base = _seed_args(seed, stream_base, n)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_seeded_device")(self._w._ctx, label, len(label), n, self.k,
+                                                                                         self.dim_nd, self.dim_np, d_x, d_s, seed, stream_base,
+                                                                                         d_proofs, d_commitments, d_status or None))
 
     def verify_batch(self, label: bytes, commitments, proofs, rounds: int, nl: int, nn: int):
         """commitments [B, k, 64] (value-major), proofs [B, proof_bytes] -> (accept [B], status [B])."""

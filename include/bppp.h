@@ -687,8 +687,9 @@ BPPP_API int bppp_reciprocal_verify_batch_device(bppp_ctx* ctx, const uint8_t* l
  * k dim_nd <= |g_vec|, dim_nd + 10 <= |h_vec|, dim_np <= dim_nd + 1, rounds <= 12, nl, nn <= 4096.  k = 1 IS
  * bppp_reciprocal_verify_batch[_device] (and so the u64 kernels for the u64 shape).  The device form takes device buffers (d_status
  * required; d_reject_count: optional device int32, the number of rejected instances), is asynchronous on the context's stream and
- * runs a call of more than "max_batch" instances as consecutive parts.  Verifier only, exact mode, 64-byte points: there is no
- * aggregated prover, SEC1 form, RLC mode, caller-transcript form, sharded form or single-proof front end yet. */
+ * runs a call of more than "max_batch" instances as consecutive parts.  Exact mode, 64-byte points: there is no SEC1 form, RLC
+ * mode, caller-transcript form, sharded form or single-proof front end yet.  The prover from integers is below
+ * (bppp_reciprocal_agg_prove_values_batch*). */
 BPPP_API size_t bppp_reciprocal_agg_proof_bytes(size_t k, size_t rounds, size_t nl, size_t nn);
 BPPP_API int bppp_reciprocal_agg_verify_batch(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
                                               size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl,
@@ -849,6 +850,46 @@ BPPP_API int bppp_reciprocal_prove_values_batch_seeded_device(bppp_ctx* ctx, con
                                                               size_t dim_nd, size_t dim_np, const void* d_x, const void* d_s,
                                                               const uint8_t seed[32], uint64_t stream_base, void* d_proofs,
                                                               void* d_commitments, void* d_status);
+
+/* ---- AGGREGATED range proofs from integers: k values under one proof, the aggregate counterpart of the calls above ----
+ * Per instance k integers x_i and blindings s_i go in (32-byte big-endian scalars, value-major); the k value commitments
+ * V_i = x_i g + s_i h_vec[0] and ONE proof in the layout bppp_reciprocal_agg_verify_batch takes come out.  The protocol is what
+ * tests/agg_cases.py::prove states on the oracle: Transcript::new(label), app_point("reciprocal_commitment", V_i) for i < k,
+ * e = challenge("reciprocal_challenge"), r_{i,d} = (digit_{i,d} + e)^-1, R_i = rb_i h_vec[0] + sum_d r_{i,d} h_vec[9 + d], then
+ * ArithmeticCircuit::prove over the k commitments V_i + R_i with v_i = [x_i, r_i...], s_v[i] = s_i + rb_i, w_l = all digits
+ * (value-major), w_r = all reciprocals, w_o = the multiplicities over all k dim_nd digits.
+ *   x, s         n x k x 32
+ *   rnd          n x bppp_reciprocal_agg_prove_draws(k, dim_nd) x 32, per instance rb_0 .. rb_{k-1}, then the circuit prover's
+ *                18 + (dim_nd + 1) + k dim_nd draws in its own order; the same draws give the oracle's bytes.  The seeded forms make
+ *                them on the device (stream layout of bppp_reciprocal_prove_batch_seeded, instance i on stream stream_base + i) and
+ *                clear them behind the prover's last kernel.
+ *   proofs       n x bppp_reciprocal_agg_proof_bytes(k, rounds, nl, nn), (rounds, nl, nn) = bppp_wnla_proof_shape(|h_vec|, |g_vec|)
+ *   commitments  n x k x 64
+ * BPPP_ERR_INVALID_ARG, before anything touches the GPU: the verifier's conditions (1 <= k <= 64, k dim_nd <= |g_vec|,
+ * dim_nd + 10 <= |h_vec|, dim_np <= dim_nd + 1), dim_np^dim_nd <= n (x must determine its digits, as above), a NULL output, a stream
+ * range that overflows.  k = 1 IS bppp_reciprocal_prove_values_batch* (its kernels, its bytes).
+ * status, per INSTANCE: any non-canonical x_i or s_i gives BPPP_ST_BAD_ENCODING, any canonical x_i >= dim_np^dim_nd
+ * BPPP_ST_OUT_OF_RANGE, a degenerate challenge or a zero digit + e BPPP_ST_DEGENERATE.  A flagged instance gets a zeroed proof and k
+ * zeroed commitments; the other instances are not affected.
+ * The _device forms take device pointers (d_status may be NULL), are asynchronous on the context's stream and wait for nothing; the
+ * FIRST prove call of a (k, dim_nd, dim_np) on a context uploads the shape's circuit data with a blocking copy -- it stays on the
+ * context.  A call runs as consecutive parts of at most "max_batch" / (k dim_nd) instances (at least one): the option bounds the
+ * multiplication gates whose vectors a part holds (about 200 KB per instance at (16, 16, 16)). */
+BPPP_API size_t bppp_reciprocal_agg_prove_draws(size_t k, size_t dim_nd); /* k + 18 + (dim_nd + 1) + k dim_nd */
+BPPP_API int bppp_reciprocal_agg_prove_values_batch(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                    size_t dim_np, const uint8_t* x, const uint8_t* s, const uint8_t* rnd, uint8_t* proofs,
+                                                    uint8_t* commitments, int32_t* status /* n or NULL */);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_seeded(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                           size_t dim_nd, size_t dim_np, const uint8_t* x, const uint8_t* s,
+                                                           const uint8_t seed[32], uint64_t stream_base, uint8_t* proofs,
+                                                           uint8_t* commitments, int32_t* status /* n or NULL */);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                           size_t dim_nd, size_t dim_np, const void* d_x, const void* d_s, const void* d_rnd,
+                                                           void* d_proofs, void* d_commitments, void* d_status);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_seeded_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                                  size_t dim_nd, size_t dim_np, const void* d_x, const void* d_s,
+                                                                  const uint8_t seed[32], uint64_t stream_base, void* d_proofs,
+                                                                  void* d_commitments, void* d_status);
 
 /* Profiling aid for bench.py: when enabled, every kernel launch of the verify pipeline is bracketed by HIP events on
  * the context's stream; bppp_ctx_get_timings returns accumulated milliseconds and launch counts per kernel since the
