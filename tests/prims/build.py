@@ -2,13 +2,17 @@
 
   libbppp_prims_gcc.so    g++ host build (prims_host.cpp): the code path of the tests/emul emulation
   libbppp_prims_clang.so  ROCm's clang++ host build (prims_host.cpp): field.h's __builtin_addc / __builtin_subc carry chains
-  libbppp_prims_hip.so    hipcc gfx950 build (prims_device.hip, bucket_device.hip) with the product's BASE_FLAGS: the code the GPU runs
+  libbppp_prims_hip.so    hipcc gfx950 build (prims_device.hip, bucket_device.hip, agg_device.hip) with the product's BASE_FLAGS: the code
+                          the GPU runs
 
 Each library exports the dispatcher (prims_run_host / prims_run_device) and the variable-base sums (prims_run_sums_host: the one-lane
 forms; prims_run_sums_device: those and the lane-group forms) and the transcript primitives (prims_run_transcript_host: the register
 sponge; prims_run_transcript_device: that and the LDS sponge, in the uniform and the grouped launch layout) and the bucket stage of the
 RLC batch mode (tests/test_prims_bucket.py, arguments in bucket_prims.h; prims_run_bucket_host: the single-thread form of bucket_core.h;
-prims_run_bucket_device: the product's own k_bkt_* kernels, whose translation unit bucket_device.hip includes as it is).  A library is
+prims_run_bucket_device: the product's own k_bkt_* kernels, whose translation unit bucket_device.hip includes as it is) and the
+aggregated range proof's phase 1, C0 stage and prover stages (tests/test_prims_agg.py, arguments in agg_prims.h;
+prims_run_agg_verify_host / prims_run_agg_prove_host: the single-thread forms; prims_run_agg_*_device: the product's own k_agg_* and
+k_aprove_* kernels, whose translation units agg_device.hip includes as they are).  A library is
 rebuilt when it is missing or older than any bp_pp_amd/csrc/*.h, an included kernel unit or any tests/prims/* source."""
 import ctypes as C
 import glob
@@ -29,8 +33,9 @@ SO = {
     "gfx950": os.path.join(HERE, "libbppp_prims_hip.so"),
 }
 HOST_FLAGS = ["-O2", "-shared", "-fPIC", "-std=c++17"]
-DEVICE_UNITS = ("prims_device.hip", "bucket_device.hip")
-INCLUDED_KERNEL_UNITS = ("k_verify_bucket.hip",)      # bp_pp_amd/csrc units that bucket_device.hip includes
+DEVICE_UNITS = ("prims_device.hip", "bucket_device.hip", "agg_device.hip")
+# bp_pp_amd/csrc units that bucket_device.hip and agg_device.hip include
+INCLUDED_KERNEL_UNITS = ("k_verify_bucket.hip", "k_agg.hip", "k_aggprove.hip")
 
 
 def _hipcc():
@@ -120,6 +125,11 @@ def load(backend):
     run_bkt.argtypes = [sz, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     run_bkt.restype = C.c_int
     L.run_bucket = run_bkt
+    for name in ("verify", "prove"):
+        fn = getattr(L, f"prims_run_agg_{name}_" + ("device" if backend == "gfx950" else "host"))
+        fn.argtypes = [vp, vp, vp]
+        fn.restype = C.c_int
+        setattr(L, f"run_agg_{name}", fn)
     if backend != "gfx950":
         L.prims_is_clang.restype = C.c_int
     return L

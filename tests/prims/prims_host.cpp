@@ -11,6 +11,7 @@
 
 #include "prims_core.h"
 #include "bucket_prims.h"
+#include "agg_prims.h"
 
 #define PRIMS_API extern "C" __attribute__((visibility("default")))
 
@@ -106,5 +107,66 @@ PRIMS_API int prims_run_bucket_host(size_t N, uint32_t M, int nb, const uint64_t
         if (ok)
             for (size_t j = c * M; j < c * M + M && j < N; j++) accept[j] = status[j] == bppp::ST_OK ? 1 : 0;
     }
+    return 0;
+}
+
+// The aggregate verifier's phase 1 and C0 stage (agg_prims.h has the arguments) in the single-thread form of agg_core.h, as
+// tests/emul/agg_emul.cpp walks it: the G runs of an instance one after the other (last first) with their sums added here, where the
+// device adds them by shuffles; the fixed-base half as fb_sum_serial over the form's lane count (1, BPPP_FB_LANES, 64); the
+// variable-base half on the window tables or on the projective tables.  Returns 0, or -1 for arguments out of range.
+PRIMS_API int prims_run_agg_verify_host(const int64_t* dims, const void* const* in, void* const* io) {
+    using namespace bppp;
+    aggp::VerifyShape s;
+    if (!aggp::verify_shape(s, dims)) return -1;
+    std::vector<apt_packed> atab(aggp::verify_atab_entries(s));
+    std::vector<u32> tscr(aggp::verify_tscr_words(s));
+    std::vector<pt_slot> straus(aggp::verify_straus_slots(s));
+    const AggWs r = aggp::verify_ws(s, (const uint8_t*)in[0], in[1], in[2], in[3], io, atab.data(), tscr.data(), straus.data());
+    const size_t n = s.N;
+    for (size_t t = 0; t < n; t++) {
+        if (s.G == 1) { agg_phase1(r, t); continue; }
+        AggHead h;
+        sc ps, musum, p, m;
+        agg_phase1_head(r, t, h);
+        sc_set_u32(ps, 0); sc_set_u32(musum, 0);
+        for (int q = s.G - 1; q >= 0; q--) { agg_phase1_run(r, t, h, q, s.G, p, m); sc_add(ps, ps, p); sc_add(musum, musum, m); }
+        agg_phase1_tail(r, t, h, ps, musum);
+    }
+    const int lanes = s.fb == AGGV_FB_L1 ? 1 : s.fb == AGGV_FB_L64 ? 64 : BPPP_FB_LANES;
+    for (size_t t = 0; t < n; t++) {
+        pt a;
+        FbRanges rg;
+        agg_c0_fixed_ranges(rg, r);
+        fb_sum_serial(a, r.fb, t, r.sc0, rg, lanes);
+        agg_c0_fixed_store(r, t, a);
+    }
+    if (r.atab) for (size_t t = 0; t < n; t++) agg_c0_tables(r, t);
+    for (size_t t = 0; t < n; t++) agg_c0_var(r, t);
+    for (size_t t = 0; t < n; t++) ((uint8_t*)io[aggp::V_FELL])[t] = aggp::fallback_mask(r, t);
+    for (size_t t = 0; t < n; t++) agg_c0_finish(r, t);
+    return 0;
+}
+
+// The aggregate prover's witness, r1, msm and r2 stages, each over all instances (the msm: all N k rows, a serial fixed-base sum per
+// row) before the next.  Returns 0, or -1 for arguments out of range.
+PRIMS_API int prims_run_agg_prove_host(const int64_t* dims, const void* const* in, void* const* io) {
+    aggp::ProveShape s;
+    if (!aggp::prove_shape(s, dims)) return -1;
+    if ((s.stages & AGGP_MSM) && !in[1]) return -1;
+    const bppp::AggProveWs a = aggp::prove_ws(s, (const uint8_t*)in[0], in[1], io);
+    if (s.stages & AGGP_WITNESS) for (size_t t = 0; t < s.N; t++) bppp::agg_prove_witness(a, t);
+    if (s.stages & AGGP_R1) for (size_t t = 0; t < s.N; t++) bppp::agg_prove_stage_r1(a, t);
+    if (s.stages & AGGP_MSM) {
+        const size_t rows = s.N * s.k;
+        bppp::FbRanges rg;
+        bppp::agg_prove_pole_ranges(rg, a);
+        for (size_t row = 0; row < rows; row++) {
+            bppp::pt acc;
+            if (a.ct) bppp::fb_sum_serial_ct(acc, a.fb_ct, row, a.rsc, rg);
+            else bppp::fb_sum_serial(acc, a.fb, row, a.rsc, rg);
+            bppp::ws_st_pt(a.rpb, rows, row, acc);
+        }
+    }
+    if (s.stages & AGGP_R2) for (size_t t = 0; t < s.N; t++) bppp::agg_prove_stage_r2(a, t);
     return 0;
 }
