@@ -746,6 +746,15 @@ class ArithmeticCircuit:
             self._circuit = None
         self._w.close()
 
+    def _w_o(self, w_o, B: int):
+        """w_o [B, dim_no, 32] -> (array, its address for the C ABI); a circuit with dim_no = 0 has none: None or an empty array -> a null pointer"""
+        if self.dim_no == 0:
+            if w_o is not None and np.asarray(w_o).size:
+                raise ValueError("the circuit has dim_no = 0: w_o must be None or empty")
+            return None, None
+        arr = _u8(w_o, (B, self.dim_no, 32))
+        return arr, arr.ctypes.data
+
     def prove_batch(self, label: bytes, v_commitments, v, s_v, w_l, w_r, w_o, rnd, transcripts=None):
         """circuit.rs:260-556 for a batch: v_commitments [B, k, 64], v [B, k, dim_nv, 32], s_v [B, k, 32], w_l / w_r [B, dim_nm, 32],
         w_o [B, dim_no, 32], rnd [B, 18 + dim_nv + dim_nm, 32] (the prover's random scalars in the reference's draw order)
@@ -756,7 +765,7 @@ class ArithmeticCircuit:
         B = v_commitments.shape[0]
         v, s_v = _u8(v, (B, self.k, self.dim_nv, 32)), _u8(s_v, (B, self.k, 32))
         w_l, w_r = _u8(w_l, (B, self.dim_nm, 32)), _u8(w_r, (B, self.dim_nm, 32))
-        w_o = _u8(w_o, (B, self.dim_no, 32))
+        w_o_arr, w_o = self._w_o(w_o, B)                  # (the array lives until the call returns)
         rnd = _u8(rnd, (B, 18 + self.dim_nv + self.dim_nm, 32))
         rounds, nl, nn = C.c_size_t(), C.c_size_t(), C.c_size_t()
         _capi.lib().bppp_wnla_proof_shape(self._w.nh, self._w.ng, C.byref(rounds), C.byref(nl), C.byref(nn))
@@ -766,11 +775,11 @@ class ArithmeticCircuit:
             S, out = _states(transcripts), np.zeros((B, 203), np.uint8)
             _capi.check(_capi.lib().bppp_circuit_prove_batch_transcript(self._w._ctx, self._circuit, B, S.ctypes.data, S.shape[0],
                                                                         v_commitments.ctypes.data, v.ctypes.data, s_v.ctypes.data, w_l.ctypes.data,
-                                                                        w_r.ctypes.data, w_o.ctypes.data, rnd.ctypes.data, proofs.ctypes.data,
+                                                                        w_r.ctypes.data, w_o, rnd.ctypes.data, proofs.ctypes.data,
                                                                         st.ctypes.data, out.ctypes.data))
             return proofs, st, (rounds.value, nl.value, nn.value), out
         _capi.check(_capi.lib().bppp_circuit_prove_batch(self._w._ctx, self._circuit, label, len(label), B, v_commitments.ctypes.data,
-                                                         v.ctypes.data, s_v.ctypes.data, w_l.ctypes.data, w_r.ctypes.data, w_o.ctypes.data,
+                                                         v.ctypes.data, s_v.ctypes.data, w_l.ctypes.data, w_r.ctypes.data, w_o,
                                                          rnd.ctypes.data, proofs.ctypes.data, st.ctypes.data))
         return proofs, st, (rounds.value, nl.value, nn.value)
 
@@ -783,7 +792,7 @@ class ArithmeticCircuit:
         B = v_commitments.shape[0]
         v, s_v = _u8(v, (B, self.k, self.dim_nv, 32)), _u8(s_v, (B, self.k, 32))
         w_l, w_r = _u8(w_l, (B, self.dim_nm, 32)), _u8(w_r, (B, self.dim_nm, 32))
-        w_o = _u8(w_o, (B, self.dim_no, 32))
+        w_o_arr, w_o = self._w_o(w_o, B)                  # (the array lives until the call returns)
         seed, stream_base = _seed_args(seed, stream_base, B)
         rounds, nl, nn = C.c_size_t(), C.c_size_t(), C.c_size_t()
         _capi.lib().bppp_wnla_proof_shape(self._w.nh, self._w.ng, C.byref(rounds), C.byref(nl), C.byref(nn))
@@ -791,7 +800,7 @@ class ArithmeticCircuit:
         st = np.zeros(B, np.int32)
         _capi.check(_capi.lib().bppp_circuit_prove_batch_seeded(self._w._ctx, self._circuit, label, len(label), B, v_commitments.ctypes.data,
                                                                 v.ctypes.data, s_v.ctypes.data, w_l.ctypes.data, w_r.ctypes.data,
-                                                                w_o.ctypes.data, seed, stream_base, proofs.ctypes.data, st.ctypes.data))
+                                                                w_o, seed, stream_base, proofs.ctypes.data, st.ctypes.data))
         return proofs, st, (rounds.value, nl.value, nn.value)
 
     def commit_batch(self, v, s):
@@ -909,13 +918,13 @@ class ArithmeticCircuit:
         B = v_commitments33.shape[0]
         v, s_v = _u8(v, (B, self.k, self.dim_nv, 32)), _u8(s_v, (B, self.k, 32))
         w_l, w_r = _u8(w_l, (B, self.dim_nm, 32)), _u8(w_r, (B, self.dim_nm, 32))
-        w_o = _u8(w_o, (B, self.dim_no, 32))
+        w_o_arr, w_o = self._w_o(w_o, B)                  # (the array lives until the call returns)
         rnd = _u8(rnd, (B, 18 + self.dim_nv + self.dim_nm, 32))
         rounds, nl, nn = C.c_size_t(), C.c_size_t(), C.c_size_t()
         _capi.lib().bppp_wnla_proof_shape(self._w.nh, self._w.ng, C.byref(rounds), C.byref(nl), C.byref(nn))
         proofs = np.zeros((B, 33 * (4 + 2 * rounds.value) + 32 * (nl.value + nn.value)), np.uint8)
         st = np.zeros(B, np.int32)
         _capi.check(_capi.lib().bppp_circuit_prove_batch_sec1(self._w._ctx, self._circuit, label, len(label), B, v_commitments33.ctypes.data,
-                                                              v.ctypes.data, s_v.ctypes.data, w_l.ctypes.data, w_r.ctypes.data, w_o.ctypes.data,
+                                                              v.ctypes.data, s_v.ctypes.data, w_l.ctypes.data, w_r.ctypes.data, w_o,
                                                               rnd.ctypes.data, proofs.ctypes.data, st.ctypes.data))
         return proofs, st, (rounds.value, nl.value, nn.value)

@@ -83,6 +83,67 @@ STATEMENTS = {
 }
 
 
+def _part(nm, nv, **at):
+    """partition tables with w_o index `i` at position `j` of type `typ` for typ=(j, i) or typ=[(j, i), ...]; None everywhere else"""
+    p = {"LO": [-1] * nv, "LL": [-1] * nv, "LR": [-1] * nv, "NO": [-1] * nm}
+    for typ, where in at.items():
+        for j, i in ([where] if isinstance(where, tuple) else where):
+            p[typ][j] = i
+    return p
+
+
+def _family(tag, nm, no, nv, k, f_l, f_m, **at):
+    fn = lambda: random_statement(b"family-" + tag, nm, no, nv, k, f_l, f_m, _part(nm, nv, **at))
+    fn.dims = (nm, no, nv, k)
+    return fn
+
+
+# The shape family: what the statement's shape steers in circuit_core.h / circuit_prove_core.h.  With P = 4 + k points in C0's variable-base
+# sum: the lane-per-point form runs on L = the power of two >= P (at least 8) lanes up to L = 64 and the one-lane kernels walk the points in
+# chunks of five; NH = the power of two >= nv + 9, NG = the power of two >= nm.  LR entries stay at position nv - 1 (an LR entry in front of it
+# leaves the reference's prover incomplete, as f_l + f_m and f_m with nv > 1 do: COMPLETE below).
+FAMILY = {
+    "k4": _family(b"k4", 2, 2, 2, 4, True, False, LO=(0, 0), LL=(1, 1)),                 # P = 8: L = 8 with no idle lane, chunks 5 + 3
+    "k5": _family(b"k5", 2, 1, 1, 5, True, False, LO=(0, 0)),                            # P = 9: L = 16, chunks 5 + 4
+    "k11": _family(b"k11", 2, 1, 1, 11, True, False, LL=(0, 0)),                         # P = 15: L = 16, three full chunks
+    "k13": _family(b"k13", 3, 0, 1, 13, True, False),                                    # P = 17: L = 32, 5 + 5 + 5 + 2; no w_o at all
+    "k60": _family(b"k60", 2, 1, 1, 60, True, False, LO=(0, 0)),                         # P = 64: L = 64, a whole wavefront, no idle lane
+    "k61": _family(b"k61", 2, 1, 1, 61, True, False, LR=(0, 0)),                         # P = 65: the one-lane kernels at any size, 13 chunks
+    "nv8": _family(b"nv8", 4, 2, 8, 2, True, False, LO=(0, 0), LL=(3, 1)),               # nv + 9 = 17: NH = 32
+    "nm5": _family(b"nm5", 5, 2, 2, 1, True, False, NO=(0, 0), LL=(1, 1)),               # NG = 8 with three padding generators
+    "nm7": _family(b"nm7", 7, 2, 2, 1, True, False, NO=(6, 0), LO=(1, 1)),               # NG = 8 with one
+    "nm8": _family(b"nm8", 8, 2, 2, 1, True, False, NO=(3, 0), LL=(0, 1)),               # NG = nm = 8
+    "nm16": _family(b"nm16", 16, 2, 2, 1, True, False, NO=[(0, 0), (15, 1)]),            # NG = nm = NH = 16
+    "nof": _family(b"nof", 2, 2, 2, 2, False, False, LO=(0, 0), LR=(1, 1)),              # neither flag: every 2 tau^3 coef_i is zero
+    "fm_nv2": _family(b"fm2", 4, 2, 2, 2, False, True, LO=(0, 0), LL=(1, 1)),            # f_m at more than one position (nl = nm)
+    "fl_fm_k5": _family(b"flfm5", 5, 1, 1, 5, True, True, LO=(0, 0)),                    # collect_lambda's tensor terms past k = 2 (nl = nm), L = 16
+}
+STATEMENTS.update(FAMILY)
+
+# Whether the reference's verifier accepts its own prover's output: the C oracle's verdict on the honest proofs of make(name, .), recorded
+# here and checked against that verdict by tests/test_circuit_emul.py (test_complete_table_is_the_oracles_verdict).
+COMPLETE = {
+    "ac_works": True, "mixed_k2": True, "fl_fm": False, "fm_nv1": True,
+    "k4": True, "k5": True, "k11": True, "k13": True, "k60": True, "k61": True, "nv8": True, "nm5": True, "nm7": True, "nm8": True,
+    "nm16": True, "nof": True, "fm_nv2": False, "fl_fm_k5": False,
+}
+
+
+def c0_lanes(name):
+    """L of the lane-per-point form for the statement: the power of two >= 4 + k, at least 8"""
+    k = FAMILY[name].dims[3] if name in FAMILY else STATEMENTS[name]()["k"]
+    return max(8, _pow2_at_least(4 + k))
+
+
+# the launch forms the family is there for -> the statements that reach each
+LAUNCH_FORMS = {
+    "L=8": [n for n in FAMILY if c0_lanes(n) == 8], "L=16": [n for n in FAMILY if c0_lanes(n) == 16],
+    "L=32": [n for n in FAMILY if c0_lanes(n) == 32], "L=64": [n for n in FAMILY if c0_lanes(n) == 64],
+    "one lane past 64 points": [n for n in FAMILY if c0_lanes(n) > 64],
+    "NH=32": ["nv8"], "NG padded": ["nm5", "nm7", "fl_fm_k5"], "NG exact": ["nm8", "nm16"], "no flag": ["nof"],
+}
+
+
 def make(name: str, B: int, label: bytes = b"circuit test"):
     st = STATEMENTS[name]()
     nm, no, nv, k = st["nm"], st["no"], st["nv"], st["k"]
@@ -112,6 +173,9 @@ def make(name: str, B: int, label: bytes = b"circuit test"):
         sv_all.append(_b(s_v))
         rnd_all.append(rnd[:32 * used])
         com = C.create_string_buffer(64 * k)
+        # room for 16 rounds and 16 final scalars: every round halves the longer of the two vectors, so there are at most
+        # log2(max(NG, NH)) of them, and the C oracle ends with at most 8 + 8 scalars (checked again on the shape it reports)
+        assert max(NG, NH) <= 1 << 16
         pbuf = C.create_string_buffer(64 * (4 + 2 * 16) + 32 * 16)
         rounds, pl, pn = sz(0), sz(0), sz(0)
         rc = L.bppp_oracle_circuit_prove(g, b"".join(gv), b"".join(hv), b"".join(gv_), sz(len(gv_)), b"".join(hv_), sz(len(hv_)), dims,
@@ -122,6 +186,7 @@ def make(name: str, B: int, label: bytes = b"circuit test"):
                                          _b(st["w_o"]), rnd, sz(n_rnd), com, pbuf, C.byref(rounds), C.byref(pl), C.byref(pn))
         assert rc == 0, rc
         sh = (rounds.value, pl.value, pn.value)
+        assert sh[0] <= 16 and sh[1] + sh[2] <= 16, (name, sh)
         shape = shape or sh
         assert sh == shape
         nbytes = 64 * (4 + 2 * sh[0]) + 32 * (sh[1] + sh[2])

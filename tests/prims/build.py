@@ -2,8 +2,8 @@
 
   libbppp_prims_gcc.so    g++ host build (prims_host.cpp): the code path of the tests/emul emulation
   libbppp_prims_clang.so  ROCm's clang++ host build (prims_host.cpp): field.h's __builtin_addc / __builtin_subc carry chains
-  libbppp_prims_hip.so    hipcc gfx950 build (prims_device.hip, bucket_device.hip, agg_device.hip) with the product's BASE_FLAGS: the code
-                          the GPU runs
+  libbppp_prims_hip.so    hipcc gfx950 build (prims_device.hip, bucket_device.hip, agg_device.hip, circuit_device.hip) with the product's
+                          BASE_FLAGS: the code the GPU runs
 
 Each library exports the dispatcher (prims_run_host / prims_run_device) and the variable-base sums (prims_run_sums_host: the one-lane
 forms; prims_run_sums_device: those and the lane-group forms) and the transcript primitives (prims_run_transcript_host: the register
@@ -12,7 +12,10 @@ RLC batch mode (tests/test_prims_bucket.py, arguments in bucket_prims.h; prims_r
 prims_run_bucket_device: the product's own k_bkt_* kernels, whose translation unit bucket_device.hip includes as it is) and the
 aggregated range proof's phase 1, C0 stage and prover stages (tests/test_prims_agg.py, arguments in agg_prims.h;
 prims_run_agg_verify_host / prims_run_agg_prove_host: the single-thread forms; prims_run_agg_*_device: the product's own k_agg_* and
-k_aprove_* kernels, whose translation units agg_device.hip includes as they are).  A library is
+k_aprove_* kernels, whose translation units agg_device.hip includes as they are) and the generic circuit verifier's phase 1 and C0
+stage (tests/test_prims_circuit.py, arguments in circuit_prims.h; prims_run_circuit_host: the single-thread form; prims_run_circuit_device:
+the product's own k_circuit_* kernels, circuit_device.hip includes k_generic.hip as it is; prims_circuit_plan, host builds: plan_generic's
+choices for a circuit call).  A library is
 rebuilt when it is missing or older than any bp_pp_amd/csrc/*.h, an included kernel unit or any tests/prims/* source."""
 import ctypes as C
 import glob
@@ -33,9 +36,9 @@ SO = {
     "gfx950": os.path.join(HERE, "libbppp_prims_hip.so"),
 }
 HOST_FLAGS = ["-O2", "-shared", "-fPIC", "-std=c++17"]
-DEVICE_UNITS = ("prims_device.hip", "bucket_device.hip", "agg_device.hip")
-# bp_pp_amd/csrc units that bucket_device.hip and agg_device.hip include
-INCLUDED_KERNEL_UNITS = ("k_verify_bucket.hip", "k_agg.hip", "k_aggprove.hip")
+DEVICE_UNITS = ("prims_device.hip", "bucket_device.hip", "agg_device.hip", "circuit_device.hip")
+# bp_pp_amd/csrc units that bucket_device.hip, agg_device.hip and circuit_device.hip include
+INCLUDED_KERNEL_UNITS = ("k_verify_bucket.hip", "k_agg.hip", "k_aggprove.hip", "k_generic.hip")
 
 
 def _hipcc():
@@ -75,15 +78,35 @@ def build(backend, force=False):
     if why:
         raise RuntimeError(why)
     if backend == "gfx950":
-        from bp_pp_amd._build import BASE_FLAGS
-        cmd = [_hipcc(), *BASE_FLAGS, "-shared", "-Wl,-rpath,/opt/rocm/lib", "-o", so + ".tmp",
-               *[os.path.join(HERE, u) for u in DEVICE_UNITS]]
-    else:
-        cxx = "g++" if backend == "gcc" else clangxx()
-        cmd = [cxx, *HOST_FLAGS, "-o", so + ".tmp", os.path.join(HERE, "prims_host.cpp")]
+        return _build_device(so)
+    cxx = "g++" if backend == "gcc" else clangxx()
+    cmd = [cxx, *HOST_FLAGS, "-o", so + ".tmp", os.path.join(HERE, "prims_host.cpp")]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"building {os.path.basename(so)} failed:\n{r.stderr[-6000:]}")
+    os.replace(so + ".tmp", so)
+    return so
+
+
+def _build_device(so):
+    """The device units side by side, one hipcc -c each (a unit that includes a product kernel unit takes minutes, and one command
+    compiles its inputs one after the other), then one link.  The objects live in a temporary directory."""
+    import tempfile
+    from concurrent.futures import ThreadPoolExecutor
+    from bp_pp_amd._build import BASE_FLAGS
+    with tempfile.TemporaryDirectory(prefix="bppp_prims_") as tmp:
+        def compile_one(unit):
+            obj = os.path.join(tmp, unit[:-4] + ".o")
+            r = subprocess.run([_hipcc(), *BASE_FLAGS, "-c", os.path.join(HERE, unit), "-o", obj], capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"building {os.path.basename(so)} failed on {unit}:\n{r.stderr[-6000:]}")
+            return obj
+        with ThreadPoolExecutor(max_workers=min(len(DEVICE_UNITS), os.cpu_count() or 1)) as ex:
+            objs = list(ex.map(compile_one, DEVICE_UNITS))
+        r = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-rpath,/opt/rocm/lib", "-o", so + ".tmp", *objs],
+                           capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"linking {os.path.basename(so)} failed:\n{r.stderr[-6000:]}")
     os.replace(so + ".tmp", so)
     return so
 
@@ -130,6 +153,12 @@ def load(backend):
         fn.argtypes = [vp, vp, vp]
         fn.restype = C.c_int
         setattr(L, f"run_agg_{name}", fn)
+    run_circ = L.prims_run_circuit_device if backend == "gfx950" else L.prims_run_circuit_host
+    run_circ.argtypes = [vp, vp, vp]
+    run_circ.restype = C.c_int
+    L.run_circuit = run_circ
     if backend != "gfx950":
         L.prims_is_clang.restype = C.c_int
+        L.prims_circuit_plan.argtypes = [sz, sz, sz, C.c_int, C.c_int, vp]
+        L.prims_circuit_plan.restype = None
     return L

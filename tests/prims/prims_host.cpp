@@ -12,6 +12,7 @@
 #include "prims_core.h"
 #include "bucket_prims.h"
 #include "agg_prims.h"
+#include "circuit_prims.h"
 
 #define PRIMS_API extern "C" __attribute__((visibility("default")))
 
@@ -169,4 +170,50 @@ PRIMS_API int prims_run_agg_prove_host(const int64_t* dims, const void* const* i
     }
     if (s.stages & AGGP_R2) for (size_t t = 0; t < s.N; t++) bppp::agg_prove_stage_r2(a, t);
     return 0;
+}
+
+// The circuit verifier's phase 1 and C0 stage (circuit_prims.h has the arguments) in the single-thread form of circuit_core.h, as
+// tests/emul/bppp_emul.cpp walks it: the fixed-base half as fb_sum_serial over the plan's lane count (64 or BPPP_FB_LANES), the
+// variable-base half on the window tables or on the projective tables.  The lane-per-point form meets by shuffles and has no host
+// form.  Returns 0, or -1 for arguments out of range.
+PRIMS_API int prims_run_circuit_host(const int64_t* dims, const void* const* in, void* const* io) {
+    using namespace bppp;
+    circp::Shape s;
+    if (!circp::shape(s, dims) || s.form == CIRC_VAR_POINTS) return -1;
+    CircuitHostData hd;
+    if (!circp::host_data(hd, s, in)) return -1;
+    const void* arr[9];
+    size_t arr_bytes[9];
+    circp::host_arrays(hd, arr, arr_bytes);
+    std::vector<apt_packed> atab(circp::atab_entries(s));
+    std::vector<u32> tscr(circp::tscr_words(s));
+    std::vector<pt_slot> straus(circp::straus_slots(s));
+    const CircuitWs r = circp::workspace(s, (const uint8_t*)in[circp::I_LABEL], in[circp::I_TABLE], in[circp::I_COM], in[circp::I_PROOFS], arr, io,
+                                         atab.data(), tscr.data(), straus.data());
+    const size_t n = s.N;
+    for (size_t t = 0; t < n; t++) circuit_phase1(r, t);
+    const int lanes = s.plan.fb == bppp_host::GENERIC_FB_WAVEFRONT ? 64 : BPPP_FB_LANES;
+    for (size_t t = 0; t < n; t++) {
+        pt a;
+        FbRanges rg;
+        circuit_c0_fixed_ranges(rg, r);
+        fb_sum_serial(a, r.fb, t, r.sc0, rg, lanes);
+        circuit_c0_fixed_store(r, t, a);
+    }
+    if (r.atab) for (size_t t = 0; t < n; t++) circuit_c0_tables(r, t);
+    for (size_t t = 0; t < n; t++) circuit_c0_var(r, t);
+    for (size_t t = 0; t < n; t++) circuit_c0_finish(r, t);
+    circp::plan_words(s, (int32_t*)io[circp::B_PLAN]);
+    return 0;
+}
+// plan_generic's choices for a circuit verify call of n instances on the default knobs (circuit_prims.h: plan_words), or with
+// no_lane_groups / slow_rounds set as BPPP_NO_LANE_GROUPS / BPPP_GENERIC_SLOW_ROUNDS set them: what "last_generic_form" of a call through
+// the C ABI is compared with
+PRIMS_API void prims_circuit_plan(size_t n, size_t rounds, size_t k, int no_lane_groups, int slow_rounds, int32_t out[CIRC_PLAN_WORDS]) {
+    bppp_host::GenericKnobs knobs;
+    knobs.no_lane_groups = no_lane_groups != 0;
+    knobs.slow_rounds = slow_rounds != 0;
+    circp::Shape s{};
+    s.plan = bppp_host::plan_generic(bppp_host::GENERIC_FORM_CIRCUIT, n, rounds, knobs, n, 1, 4 + k);
+    circp::plan_words(s, out);
 }

@@ -1,12 +1,46 @@
 """GPU parity tests of the generic batched ArithmeticCircuit::verify (circuit.rs:154-256) through the C ABI against the oracle: the
-reference's own `ac_works` statement (tests.rs:45-136), k = 2 with every partition type, the f_m path, the f_l + f_m shape."""
+reference's own `ac_works` statement (tests.rs:45-136), k = 2 with every partition type, the f_m path, the f_l + f_m shape, and the shape
+family of tests/circuit_cases.py (FAMILY: every lane count of the lane-per-point form, the one-lane kernels past 64 points, NH = 32, NG
+with and without padding, no w_o, no flag), each call checked on the launch form it took."""
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
+# instances per call for the family's statements
+FAMILY_B = {"k4": 9, "k5": 5, "k11": 4, "k13": 3, "k60": 3, "k61": 3, "nv8": 4, "nm5": 5, "nm7": 3, "nm8": 4, "nm16": 3, "nof": 6, "fm_nv2": 4,
+            "fl_fm_k5": 3}
 
-@pytest.mark.parametrize("name,B", [("ac_works", 70), ("mixed_k2", 9), ("fm_nv1", 5), ("fl_fm", 4)])
+
+def _assert_form(circ, case, name, B, no_lane_groups=0, slow_rounds=0):
+    """The call just made took the kernels the statement is there for: "last_generic_form" equals the code of plan_generic (plan_core.h,
+    through the host build of tests/prims) for this call, whose c0_lanes is the L of the family table and whose per_point says which form
+    of C0's variable-base sum ran."""
+    import ctypes as C
+    import circuit_cases
+    from prims import build as PB
+    plan = (C.c_int32 * 6)()
+    PB.load("gcc").prims_circuit_plan(B, case["rounds"], case["k"], no_lane_groups, slow_rounds, plan)
+    c0_lanes, per_point, _, _, fast, code = list(plan)
+    assert circ.get_option("n_simds") == 1024
+    assert circ.get_option("last_generic_form") == code & 0xFFFFFFFF
+    form = circ._w.generic_form()
+    L = circuit_cases.c0_lanes(name)
+    assert c0_lanes == L and form["protocol"] == "circuit"
+    assert form["per_point"] == per_point == (1 if L <= 64 and not no_lane_groups and not slow_rounds else 0)
+    assert fast == (0 if slow_rounds else 1)
+
+
+def _circuit(case):
+    from bp_pp_amd.wnla import ArithmeticCircuit
+    part = lambda typ, j: (None if case["part"][typ][j] < 0 else int(case["part"][typ][j]))
+    arr = lambda b: np.frombuffer(b, np.uint8).reshape(-1, 32)
+    return ArithmeticCircuit(case["nm"], case["no"], case["k"], case["nv"], case["g"], case["gv"], case["hv"], arr(case["Wm_bytes"]),
+                             arr(case["Wl_bytes"]), arr(case["am_bytes"]), arr(case["al_bytes"]), case["f_l"], case["f_m"], case["gv_"],
+                             case["hv_"], part, device=0, fb_window_bits=16)
+
+
+@pytest.mark.parametrize("name,B", [("ac_works", 70), ("mixed_k2", 9), ("fm_nv1", 5), ("fl_fm", 4)] + list(FAMILY_B.items()))
 def test_circuit_verify_vs_oracle(name, B):
     import torch
     if torch.cuda.device_count() == 0:
@@ -24,8 +58,8 @@ def test_circuit_verify_vs_oracle(name, B):
         exp = [circuit_cases.oracle_verify(case, case["commitments"][b].tobytes(), case["proofs"][b].tobytes()) for b in range(B)]
         acc, st = circ.verify_batch(case["label"], case["commitments"], case["proofs"], *shape)
         assert acc.tolist() == exp and not st.any()
-        if name != "fl_fm":
-            assert all(exp)                     # shapes the prover is complete for
+        _assert_form(circ, case, name, B)
+        assert exp == [int(circuit_cases.COMPLETE[name])] * B      # accepted exactly at the shapes the prover is complete for
         # tampered instances: accept bits must equal the oracle's, instance by instance
         P = case["proofs"].copy()
         P[0, -1] ^= 1
@@ -55,7 +89,7 @@ def test_circuit_verify_vs_oracle(name, B):
         circ.close()
 
 
-@pytest.mark.parametrize("name,B", [("mixed_k2", 9), ("ac_works", 5)])
+@pytest.mark.parametrize("name,B", [("mixed_k2", 9), ("ac_works", 5), ("k4", 9), ("k5", 5), ("k11", 4)])
 def test_circuit_verify_one_lane_kernels_vs_oracle(name, B, monkeypatch):
     """Small calls take the per-point form of C0's variable-base sum and the wavefront-per-instance fixed-base sums (plan_core.h:
     plan_generic -- per_point, GENERIC_FB_WAVEFRONT); BPPP_NO_LANE_GROUPS=1 keeps the kernels large batches run -- one lane per instance, five
@@ -74,6 +108,34 @@ def test_circuit_verify_one_lane_kernels_vs_oracle(name, B, monkeypatch):
                              case["hv_"], part, device=0, fb_window_bits=16)
     try:
         shape = (case["rounds"], case["pl"], case["pn"])
+        P, com = case["proofs"].copy(), case["commitments"].copy()
+        P[0, -1] ^= 1
+        P[B - 1, 192:256] = P[B - 1, 0:64]
+        com[1, 0] = case["commitments"][2, 0]
+        exp = [circuit_cases.oracle_verify(case, com[b].tobytes(), P[b].tobytes()) for b in range(B)]
+        acc, st = circ.verify_batch(case["label"], com, P, *shape)
+        assert acc.tolist() == exp and not st.any() and sum(exp) == B - 3
+        _assert_form(circ, case, name, B, no_lane_groups=1)
+    finally:
+        circ.close()
+
+
+def test_circuit_verify_projective_tables_three_chunks_vs_oracle(monkeypatch):
+    """BPPP_GENERIC_SLOW_ROUNDS=1 at `k11`: circuit_c0_var without window tables (w.atab == nullptr) over three chunks of five points, the
+    projective-table Straus and complete additions in the rounds behind it; verdicts against the oracle, honest and tampered."""
+    import torch
+    if torch.cuda.device_count() == 0:
+        pytest.fail("needs a GPU")
+    import circuit_cases
+    monkeypatch.setenv("BPPP_GENERIC_SLOW_ROUNDS", "1")
+    name, B = "k11", 5
+    case = circuit_cases.make(name, B)
+    circ = _circuit(case)
+    try:
+        shape = (case["rounds"], case["pl"], case["pn"])
+        acc, st = circ.verify_batch(case["label"], case["commitments"], case["proofs"], *shape)
+        assert acc.tolist() == [1] * B and not st.any()
+        _assert_form(circ, case, name, B, slow_rounds=1)
         P, com = case["proofs"].copy(), case["commitments"].copy()
         P[0, -1] ^= 1
         P[B - 1, 192:256] = P[B - 1, 0:64]
@@ -161,7 +223,7 @@ def test_commit_functions_vs_oracle():
         proto.close()
 
 
-@pytest.mark.parametrize("name,B", [("ac_works", 33), ("mixed_k2", 6), ("fm_nv1", 4), ("fl_fm", 3)])
+@pytest.mark.parametrize("name,B", [("ac_works", 33), ("mixed_k2", 6), ("fm_nv1", 4), ("fl_fm", 3)] + list(FAMILY_B.items()))
 def test_circuit_prove_byte_identical_and_verifies(name, B):
     """Generic ArithmeticCircuit::prove on the GPU (bppp_circuit_prove_batch): commitments via commit_batch, proof bytes equal to
     the reference-shaped prover's for the same witness and prover scalars, and the GPU verifier's verdict on them equals the
@@ -181,16 +243,17 @@ def test_circuit_prove_byte_identical_and_verifies(name, B):
         k, nv = case["k"], case["nv"]
         com, st = circ.commit_batch(case["v_bytes"].reshape(B * k, nv, 32), case["s_v"].reshape(B * k, 32))
         assert not st.any() and (com.reshape(B, k, 64) == case["commitments"]).all()
+        w_o = case["wo_bytes"] if case["no"] else None      # (`k13`: no w_o at all -- the wrapper and the C ABI take a null pointer)
         proofs, st, shape = circ.prove_batch(case["label"], com.reshape(B, k, 64), case["v_bytes"], case["s_v"], case["wl_bytes"],
-                                             case["wr_bytes"], case["wo_bytes"], case["rnd"])
+                                             case["wr_bytes"], w_o, case["rnd"])
         assert not st.any() and shape == (case["rounds"], case["pl"], case["pn"])
         assert (proofs == case["proofs"]).all()
         acc, st = circ.verify_batch(case["label"], com.reshape(B, k, 64), proofs, *shape)
-        assert acc.tolist() == [0 if name == "fl_fm" else 1] * B and not st.any()
+        assert acc.tolist() == [int(circuit_cases.COMPLETE[name])] * B and not st.any()
         bad = case["wl_bytes"].copy()
         bad[0, 0] = 0xFF                                  # non-canonical witness scalar: that instance is flagged, its proof zeroed
         proofs2, st2, _ = circ.prove_batch(case["label"], com.reshape(B, k, 64), case["v_bytes"], case["s_v"], bad, case["wr_bytes"],
-                                           case["wo_bytes"], case["rnd"])
+                                           w_o, case["rnd"])
         assert st2[0] == 1 and not st2[1:].any() and not proofs2[0].any() and (proofs2[1:] == proofs[1:]).all()
     finally:
         circ.close()
