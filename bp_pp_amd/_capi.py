@@ -60,9 +60,18 @@ EXPORTS += AGG_EXPORTS
 AGG_PROVE_EXPORTS = ["bppp_reciprocal_agg_prove_draws", "bppp_reciprocal_agg_prove_values_batch", "bppp_reciprocal_agg_prove_values_batch_seeded",
                      "bppp_reciprocal_agg_prove_values_batch_device", "bppp_reciprocal_agg_prove_values_batch_seeded_device"]
 EXPORTS += AGG_PROVE_EXPORTS
+# the aggregate's wire (SEC1) form and RLC mode (include/bppp.h: "The aggregate in the WIRE form", "The aggregate in RLC mode")
+AGG_WIRE_VERIFY_EXPORTS = ["bppp_reciprocal_agg_verify_batch_sec1", "bppp_reciprocal_agg_verify_batch_sec1_device",
+                           "bppp_reciprocal_agg_verify_batch_rlc", "bppp_reciprocal_agg_verify_batch_rlc_device",
+                           "bppp_reciprocal_agg_verify_batch_rlc_sec1", "bppp_reciprocal_agg_verify_batch_rlc_sec1_device"]
+AGG_WIRE_PROVE_EXPORTS = ["bppp_reciprocal_agg_prove_values_batch_sec1", "bppp_reciprocal_agg_prove_values_batch_seeded_sec1"]
+AGG_WIRE_EXPORTS = ["bppp_reciprocal_agg_proof_sec1_bytes"] + AGG_WIRE_VERIFY_EXPORTS + AGG_WIRE_PROVE_EXPORTS
 
 # the entry points of the wire form's RLC mode and single-proof front end (a subset of EXPORTS)
-RLC_SEC1_EXPORTS = [name for name in EXPORTS if name.endswith(("_rlc_sec1", "_rlc_sec1_device")) or "_one_sec1" in name]
+EXPORTS += AGG_WIRE_EXPORTS
+# (the aggregate's *_rlc_sec1 forms are not of this list: they are bound with AGG_WIRE_EXPORTS, in a block of their own in lib())
+RLC_SEC1_EXPORTS = [name for name in EXPORTS
+                    if (name.endswith(("_rlc_sec1", "_rlc_sec1_device")) or "_one_sec1" in name) and name not in AGG_WIRE_EXPORTS]
 
 _lib = None
 
@@ -285,6 +294,19 @@ def lib():
         L.bppp_reciprocal_agg_prove_values_batch_device.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]
         L.bppp_reciprocal_agg_prove_values_batch_seeded_device.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
         for name in AGG_PROVE_EXPORTS[1:]:
+            getattr(L, name).restype = i32
+    # the aggregate's wire form and RLC mode: the 64-byte twins' lists, the RLC forms with the seed behind them
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_reciprocal_agg_verify_batch_sec1"):
+        L.bppp_reciprocal_agg_proof_sec1_bytes.argtypes = [sz, sz, sz, sz]
+        L.bppp_reciprocal_agg_proof_sec1_bytes.restype = sz
+        host = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        L.bppp_reciprocal_agg_verify_batch_sec1.argtypes = host
+        L.bppp_reciprocal_agg_verify_batch_sec1_device.argtypes = host + [vp]
+        L.bppp_reciprocal_agg_verify_batch_rlc.argtypes = L.bppp_reciprocal_agg_verify_batch_rlc_sec1.argtypes = host + [u8p]
+        L.bppp_reciprocal_agg_verify_batch_rlc_device.argtypes = L.bppp_reciprocal_agg_verify_batch_rlc_sec1_device.argtypes = host + [vp, u8p]
+        L.bppp_reciprocal_agg_prove_values_batch_sec1.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_seeded_sec1.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        for name in AGG_WIRE_VERIFY_EXPORTS + AGG_WIRE_PROVE_EXPORTS:
             getattr(L, name).restype = i32
     L.bppp_strerror.argtypes = [i32]
     L.bppp_strerror.restype = C.c_char_p

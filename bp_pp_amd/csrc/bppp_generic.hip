@@ -710,10 +710,11 @@ static int recip_verify_host_impl(bppp_ctx* c, const uint8_t* label, size_t labe
 }
 
 // ---------------------------------------------------------------- aggregated reciprocal range proof: k values under one proof
-// (agg_core.h has the protocol; tests/agg_cases.py states it on the oracle).  Verifier only, exact mode, 64-byte points: phase 1 and the
-// C0 stage of its own, then the WNLA stage.  k = 1 IS ReciprocalRangeProofProtocol and goes to that verifier's entry points.
-struct AggVerifyLayout { size_t ts, sc0, pts, a, pf, inv, vs, wc, wcv, rho, mu, ys, tab, msc, total; };
-static AggVerifyLayout agg_verify_layout(const bppp_ctx* c, size_t n, size_t k, size_t dim_nd, size_t dim_np, size_t rounds) {
+// (agg_core.h has the protocol; tests/agg_cases.py states it on the oracle).  The verifier: phase 1 and the C0 stage of its own, then
+// the WNLA stage, whose final sum runs exact or in RLC mode (a seed given).  k = 1 IS ReciprocalRangeProofProtocol and goes to that
+// verifier's entry points.  The wire (SEC1) forms are with the other verifiers' at the end of this file.
+struct AggVerifyLayout { size_t ts, sc0, pts, a, pf, inv, vs, wc, wcv, rho, mu, ys, tab, msc; WnlaRlcLayout rlc; size_t total; };
+static AggVerifyLayout agg_verify_layout(const bppp_ctx* c, size_t n, size_t k, size_t dim_nd, size_t dim_np, size_t rounds, bool rlc = false) {
     const size_t NB = (size_t)c->nbases, T = (size_t)1 << rounds, NH = (size_t)c->nh, nm = k * dim_nd;
     size_t off = 0;
     auto take = [&](size_t bytes) { return take_bytes(off, bytes); };
@@ -722,6 +723,8 @@ static AggVerifyLayout agg_verify_layout(const bppp_ctx* c, size_t n, size_t k, 
     o.pf = take(30 * n * 4); o.inv = take(dim_np * 8 * n * 4); o.vs = take(k * 40 * n * 4); o.wc = take(n * 64); o.wcv = take(n * NH * 32);
     o.rho = take(n * 32); o.mu = take(n * 32); o.ys = take((rounds ? rounds : 1) * 8 * n * 4); o.tab = take(2 * T * 8 * n * 4);
     o.msc = take(NB * 8 * n * 4);
+    o.rlc = {0, 0, 0, 0};
+    if (rlc) o.rlc = wnla_rlc_take(off, n, NB);      // behind the aggregate's own buffers
     o.total = off;
     return o;
 }
@@ -734,11 +737,14 @@ static int agg_verify_check_args(const bppp_ctx* c, size_t k, size_t dim_nd, siz
     return BPPP_OK;
 }
 // the launch sequence of one call (or of one max_batch part of it), every buffer in device memory; d_ws holds agg_verify_layout().total
+// rlc_seed: the final sum in RLC mode -- by the WNLA and circuit verifiers' rule (wnla_rlc_applies), so a part of fewer than 8
+// instances runs the exact sum; everything before the final sum is the exact pipeline in the plan's launch form either way
 static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                                   const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
-                                  int32_t* d_st, uint8_t* d_ws) {
+                                  int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed = nullptr) {
     const GenericPlan plan = plan_generic(GENERIC_FORM_AGGREGATE, n, rounds, generic_knobs_of(c), n, 1, 4 + k);
-    const AggVerifyLayout o = agg_verify_layout(c, n, k, dim_nd, dim_np, rounds);
+    const bool rlc = rlc_seed && wnla_rlc_applies(n);
+    const AggVerifyLayout o = agg_verify_layout(c, n, k, dim_nd, dim_np, rounds, rlc);
     uint8_t* d = d_ws;
     hipStream_t s = c->stream;
     AggWs r;
@@ -788,21 +794,93 @@ static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t labe
         HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
     }
     GLAUNCH(s, K_AGG_C0_FINISH, k_agg_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    return wnla_verify_stage(c, w, plan, s, beside);
+    return wnla_verify_stage(c, w, plan, s, beside, rlc ? rlc_seed : nullptr, d, o.rlc);
 }
 // a call of more than max_batch instances runs as consecutive parts on the context's stream over one workspace, as the u64 verifier's
 // (instances are independent); d_ws: agg_verify_layout(min(n, max_batch)).total
 static size_t agg_part_size(const bppp_ctx* c, size_t n) { return n < c->max_batch ? n : c->max_batch; }
 static int agg_verify_parts(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                             const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
-                            int32_t* d_st, uint8_t* d_ws) {
+                            int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed) {
     const size_t per = agg_part_size(c, n), pb = agg_proof_bytes(k, rounds, nl, nn);
+    unsigned first_super_m = 0, first_chunk = 0;
     for (size_t lo = 0; lo < n; lo += per) {
         const size_t m = n - lo < per ? n - lo : per;
         const int rc = agg_verify_device_impl(c, label, label_len, m, k, dim_nd, dim_np, d_com + 64 * k * lo, d_proofs + pb * lo, rounds, nl, nn,
-                                              d_acc + lo, d_st + lo, d_ws);
+                                              d_acc + lo, d_st + lo, d_ws, rlc_seed);
         if (rc != BPPP_OK) return rc;
+        if (lo == 0) { first_super_m = c->last_rlc_super_m; first_chunk = c->last_rlc_chunk; }
     }
+    // "last_rlc_*": what the first part used (every part but the last has its size); (0, 0) where it ran the exact sum
+    if (rlc_seed) { c->last_rlc_super_m = first_super_m; c->last_rlc_chunk = first_chunk; }
+    return BPPP_OK;
+}
+// what a call allocates in front of its parts besides its workspace; "last_rlc_*" reset first, so that a failing call reports nothing stale
+static int agg_verify_prepare(bppp_ctx* c, size_t per, const uint8_t* rlc_seed) {
+    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
+    const int rc = ensure_straus_capacity(c, per);
+    if (rc != BPPP_OK) return rc;
+    return rlc_seed && wnla_rlc_applies(per) ? wnla_rlc_prepare(c, per) : BPPP_OK;
+}
+// a call over device buffers, arguments checked and k > 1: asynchronous on the context's stream, the workspace in the grow-only d_gws
+static int agg_verify_device_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                                 const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                 void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
+    if (n == 0) return BPPP_OK;
+    const size_t per = agg_part_size(c, n);
+    int rc = agg_verify_prepare(c, per, rlc_seed);
+    if (rc != BPPP_OK) return rc;
+    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_verify_layout(c, per, k, dim_nd, dim_np, rounds, rlc_seed != nullptr).total);
+    if (rc != BPPP_OK) return rc;
+    rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, rounds, nl, nn,
+                          (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws, rlc_seed);
+    if (rc != BPPP_OK || !d_reject_count) return rc;
+    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
+    HIP_TRY(hipGetLastError());
+    return BPPP_OK;
+}
+static int agg_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                                   const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                   void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
+    if (!c || !label_ok(label, label_len) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
+    const int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (k == 1)
+        return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
+                                         rlc_seed, d_reject_count);
+    return agg_verify_device_run(c, label, label_len, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
+                                 d_reject_count, rlc_seed);
+}
+static int agg_verify_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                                const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                int32_t* status, const uint8_t* rlc_seed) {
+    if (!c || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
+    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (k == 1)
+        return recip_verify_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr, rlc_seed);
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t per = agg_part_size(c, n);
+    rc = agg_verify_prepare(c, per, rlc_seed);
+    if (rc != BPPP_OK) return rc;
+    const size_t pb = agg_proof_bytes(k, rounds, nl, nn);
+    const size_t o_com = 0, o_pr = align16(n * k * 64), o_acc = align16(o_pr + n * pb), o_st = align16(o_acc + n), o_ws = align16(o_st + n * 4),
+                 total = o_ws + agg_verify_layout(c, per, k, dim_nd, dim_np, rounds, rlc_seed != nullptr).total;
+    WnlaBlob blob;
+    { const int rc_b = blob.take(c, total); if (rc_b != BPPP_OK) return rc_b; }
+    uint8_t* d = blob.d;
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * k * 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_pr, proofs, n * pb, hipMemcpyHostToDevice, s));
+    rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, d + o_com, d + o_pr, rounds, nl, nn, d + o_acc, (int32_t*)(d + o_st), d + o_ws,
+                          rlc_seed);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return BPPP_OK;
 }
 size_t bppp_reciprocal_agg_proof_bytes(size_t k, size_t rounds, size_t nl, size_t nn) { return agg_proof_bytes(k, rounds, nl, nn); }
@@ -810,55 +888,29 @@ int bppp_reciprocal_agg_verify_batch_device(bppp_ctx* c, const uint8_t* label, s
                                             size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
                                             size_t nn, void* d_accept, void* d_status, void* d_reject_count) {
     CtxLock lock_(c);
-    if (!c || !label_ok(label, label_len) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
-    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
-    if (rc != BPPP_OK) return rc;
-    if (k == 1)
-        return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
-                                         nullptr, d_reject_count);
-    HIP_TRY(hipSetDevice(c->device));
-    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
-    if (n == 0) return BPPP_OK;
-    const size_t per = agg_part_size(c, n);
-    rc = ensure_straus_capacity(c, per);
-    if (rc != BPPP_OK) return rc;
-    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_verify_layout(c, per, k, dim_nd, dim_np, rounds).total);
-    if (rc != BPPP_OK) return rc;
-    rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, rounds, nl, nn,
-                          (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws);
-    if (rc != BPPP_OK || !d_reject_count) return rc;
-    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
-    HIP_TRY(hipGetLastError());
-    return BPPP_OK;
+    return agg_verify_device_entry(c, label, label_len, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
+                                   d_reject_count, nullptr);
+}
+int bppp_reciprocal_agg_verify_batch_rlc_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
+                                                size_t nn, void* d_accept, void* d_status, void* d_reject_count, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_verify_device_entry(c, label, label_len, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
+                                   d_reject_count, seed);
 }
 int bppp_reciprocal_agg_verify_batch(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                                      const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
                                      int32_t* status) {
     CtxLock lock_(c);
-    if (!c || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
-    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
-    if (rc != BPPP_OK) return rc;
-    if (k == 1) return recip_verify_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr);
-    if (n == 0) return BPPP_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t per = agg_part_size(c, n);
-    rc = ensure_straus_capacity(c, per);
-    if (rc != BPPP_OK) return rc;
-    const size_t pb = agg_proof_bytes(k, rounds, nl, nn);
-    const size_t o_com = 0, o_pr = align16(n * k * 64), o_acc = align16(o_pr + n * pb), o_st = align16(o_acc + n), o_ws = align16(o_st + n * 4),
-                 total = o_ws + agg_verify_layout(c, per, k, dim_nd, dim_np, rounds).total;
-    WnlaBlob blob;
-    { const int rc_b = blob.take(c, total); if (rc_b != BPPP_OK) return rc_b; }
-    uint8_t* d = blob.d;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * k * 64, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_pr, proofs, n * pb, hipMemcpyHostToDevice, s));
-    rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, d + o_com, d + o_pr, rounds, nl, nn, d + o_acc, (int32_t*)(d + o_st), d + o_ws);
-    if (rc != BPPP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    return agg_verify_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr);
+}
+int bppp_reciprocal_agg_verify_batch_rlc(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                                         const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                         int32_t* status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_verify_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, seed);
 }
 
 // ---------------------------------------------------------------- generic ArithmeticCircuit (circuit.rs:95-256)
@@ -1594,8 +1646,24 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
         k_gprove_assemble<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(a);
         HIP_TRY(hipGetLastError());
         const hipMemcpyKind back = device_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (!device_io) HIP_TRY(hipMemcpyAsync(proofs, d + o_pout, n * proof_bytes, back, s));
-        HIP_TRY(hipMemcpyAsync(values->commitments_out, d + o_com, n * 64, back, s));
+        if (sec1 && !device_io) {
+            // the aggregate's k = 1 wire form: the assembled proofs and the commitments compressed into the wire buffer, copied back from there
+            const size_t wP = 5 + 2 * sh.rounds, wS = sh.nl_f + sh.nn_f, wire_pb = wire_proof_bytes(wP, wS), o_wc = align16(n * wire_pb);
+            const int rc_w = ensure_buffer(c, c->d_wire, c->wire_bytes, o_wc + n * 33);
+            if (rc_w != BPPP_OK) return rc_w;
+            WireMap wm;
+            wire_map_init(wm, n);
+            wire_map_add(wm, false, d + o_pout, proof_bytes, c->d_wire, wire_pb, wP);
+            wire_map_add(wm, true, d + o_pout + 64 * wP, proof_bytes, c->d_wire + 33 * wP, wire_pb, wS);
+            wire_map_add(wm, false, d + o_com, 64, c->d_wire + o_wc, 33, 1);
+            rc = wire_launch(wm, false, s);
+            if (rc != BPPP_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(proofs, c->d_wire, n * wire_pb, back, s));
+            HIP_TRY(hipMemcpyAsync(values->commitments_out, c->d_wire + o_wc, n * 33, back, s));
+        } else {
+            if (!device_io) HIP_TRY(hipMemcpyAsync(proofs, d + o_pout, n * proof_bytes, back, s));
+            HIP_TRY(hipMemcpyAsync(values->commitments_out, d + o_com, n * 64, back, s));
+        }
         if (status) HIP_TRY(hipMemcpyAsync(status, p.status, n * 4, back, s));
         HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
         if (!device_io) HIP_TRY(hipStreamSynchronize(s));
@@ -1634,7 +1702,7 @@ static size_t recip_sec1_exp_bytes(size_t n, size_t rounds, size_t nl, size_t nn
 // arguments checked; d_exp: recip_sec1_exp_bytes in the wire buffer
 static int recip_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np, const uint8_t* d_com33,
                           const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status, uint8_t* d_exp,
-                          const uint8_t* rlc_seed) {
+                          const uint8_t* rlc_seed, void* d_reject_count = nullptr) {
     const size_t P = 5 + 2 * rounds, S = nl + nn, o_p = align16(n * 64);
     WireMap m;
     wire_map_init(m, n);
@@ -1643,24 +1711,31 @@ static int recip_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, s
     // on c->stream: a call split into parts forks them from c->stream behind this (ev_twin_fork in recip_verify_device_entry)
     int rc = wire_launch(m, true, c->stream);
     if (rc != BPPP_OK) return rc;
-    return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, rlc_seed, nullptr);
+    return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, rlc_seed,
+                                     d_reject_count);
 }
 // rlc_seed (the *_rlc_sec1 entry points of all three verifiers): the expansion is the same launch; what runs behind it is the 64-byte
 // RLC twin's pipeline on the expanded bytes, so a flagged instance is kept out of the weighted sums exactly as there
+// d_reject_count (the aggregate's k = 1 forward only): the number of rejected instances, as recip_verify_device_entry's
 static int recip_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
                                   const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
-                                  void* d_accept, void* d_status, const uint8_t* rlc_seed) {
+                                  void* d_accept, void* d_status, const uint8_t* rlc_seed, void* d_reject_count = nullptr) {
     if (!c || !label_ok(label, label_len) || !d_commitments33 || !d_proofs33 || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
     int rc = recip_verify_check_args(c, dim_nd, dim_np, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
+    if (n == 0) {      // (nothing to verify at either shape; the counter, where one is given, reads zero as after any other call)
+        if (!d_reject_count) return BPPP_OK;
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
+        return BPPP_OK;
+    }
     if (recip_is_u64_shape(c, dim_nd, dim_np, rounds, nl, nn))      // the u64 wire form is the same 33 + 525 bytes: its own expand kernel
-        return verify_sec1_device_impl(c, label, label_len, n, d_commitments33, d_proofs33, d_accept, d_status, nullptr, nullptr, rlc_seed);
-    if (n == 0) return BPPP_OK;
+        return verify_sec1_device_impl(c, label, label_len, n, d_commitments33, d_proofs33, d_accept, d_status, nullptr, d_reject_count, rlc_seed);
     HIP_TRY(hipSetDevice(c->device));
     rc = ensure_buffer(c, c->d_wire, c->wire_bytes, recip_sec1_exp_bytes(n, rounds, nl, nn));
     if (rc != BPPP_OK) return rc;
     return recip_sec1_run(c, label, label_len, n, dim_nd, dim_np, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, rounds, nl, nn,
-                          d_accept, d_status, c->d_wire, rlc_seed);
+                          d_accept, d_status, c->d_wire, rlc_seed, d_reject_count);
 }
 int bppp_reciprocal_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
                                              const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
@@ -1764,6 +1839,106 @@ int recip_verify_sec1_transcript_host(bppp_ctx* c, size_t n, const uint8_t* stat
     if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return BPPP_OK;
+}
+
+// ---- aggregate: n x k commitments and the proof c_l c_r c_o c_s | r | x | R_0 .. R_{k-1} | l | n, 4 + 2 rounds + k points in front of
+//      the scalars.  One expansion over the whole call on the context's stream, in front of the max_batch parts; k = 1 is the
+//      reciprocal wire form and goes to its entry points
+static size_t agg_sec1_exp_bytes(size_t n, size_t k, size_t rounds, size_t nl, size_t nn) {
+    return align16(n * k * 64) + n * agg_proof_bytes(k, rounds, nl, nn);
+}
+// arguments checked, k > 1; d_exp: agg_sec1_exp_bytes in the wire buffer
+static int agg_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                        const uint8_t* d_com33, const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status,
+                        void* d_reject_count, uint8_t* d_exp, const uint8_t* rlc_seed) {
+    const size_t o_p = align16(n * k * 64);
+    WireMap m;
+    wire_map_init(m, n);
+    wire_map_add(m, false, d_com33, 33 * k, d_exp, 64 * k, k);
+    wire_add_proof(m, d_proofs33, d_exp + o_p, 4 + 2 * rounds + k, nl + nn);
+    const int rc = wire_launch(m, true, c->stream);
+    if (rc != BPPP_OK) return rc;
+    return agg_verify_device_run(c, label, label_len, n, k, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status,
+                                 d_reject_count, rlc_seed);
+}
+static int agg_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                                const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
+    if (!c || !label_ok(label, label_len) || !d_commitments33 || !d_proofs33 || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
+    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (k == 1)
+        return recip_sec1_device_impl(c, label, label_len, n, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status,
+                                      rlc_seed, d_reject_count);
+    HIP_TRY(hipSetDevice(c->device));
+    if (n == 0) {
+        if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
+        return BPPP_OK;
+    }
+    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, agg_sec1_exp_bytes(n, k, rounds, nl, nn));
+    if (rc != BPPP_OK) return rc;
+    return agg_sec1_run(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, rounds, nl, nn,
+                        d_accept, d_status, d_reject_count, c->d_wire, rlc_seed);
+}
+int bppp_reciprocal_agg_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                 size_t dim_np, const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl,
+                                                 size_t nn, void* d_accept, void* d_status, void* d_reject_count) {
+    CtxLock lock_(c);
+    return agg_sec1_device_impl(c, label, label_len, n, k, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status,
+                                d_reject_count, nullptr);
+}
+int bppp_reciprocal_agg_verify_batch_rlc_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                     size_t dim_np, const void* d_commitments33, const void* d_proofs33, size_t rounds,
+                                                     size_t nl, size_t nn, void* d_accept, void* d_status, void* d_reject_count,
+                                                     const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_sec1_device_impl(c, label, label_len, n, k, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status,
+                                d_reject_count, seed);
+}
+// host buffers: the 33-byte input staged in the wire buffer too, in front of accept, status and the expanded form
+static int agg_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                              const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                              int32_t* status, const uint8_t* rlc_seed) {
+    if (!c || !label_ok(label, label_len) || !commitments33 || !proofs33 || !accept) return BPPP_ERR_INVALID_ARG;
+    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (k == 1)
+        return recip_sec1_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, rlc_seed);
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
+    const size_t pb = wire_proof_bytes(4 + 2 * rounds + k, nl + nn);
+    const size_t o_c = 0, o_p = align16(n * k * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_e = align16(o_s + n * 4),
+                 total = o_e + agg_sec1_exp_bytes(n, k, rounds, nl, nn);
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
+    if (rc != BPPP_OK) return rc;
+    WireQuiesce guard{c};
+    uint8_t* d = c->d_wire;
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * k * 33, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
+    rc = agg_sec1_run(c, label, label_len, n, k, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, nullptr, d + o_e, rlc_seed);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPPP_OK;
+}
+size_t bppp_reciprocal_agg_proof_sec1_bytes(size_t k, size_t rounds, size_t nl, size_t nn) { return wire_proof_bytes(4 + 2 * rounds + k, nl + nn); }
+int bppp_reciprocal_agg_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
+                                          const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn,
+                                          uint8_t* accept, int32_t* status) {
+    CtxLock lock_(c);
+    return agg_sec1_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, nullptr);
+}
+int bppp_reciprocal_agg_verify_batch_rlc_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                              size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl,
+                                              size_t nn, uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_sec1_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, seed);
 }
 
 // ---- circuit
@@ -2093,9 +2268,12 @@ static size_t agg_prove_part_size(const bppp_ctx* c, size_t n, size_t k, size_t 
 }
 // one part of m instances: the launch chain on the context's stream.  Host forms: inputs uploaded into the blob, outputs copied back
 // (queued; the caller waits).  Device forms: x, s, rnd, proofs, commitments, status used where they are.
+// sec1 (host forms only): the assembled proofs and commitments compressed on the device into the wire buffer (the caller has grown it
+// to agg_prove_wire_bytes of a part) and copied back from there, 33-byte points
+static size_t agg_prove_wire_bytes(size_t n, size_t k, size_t wire_pb) { return align16(n * wire_pb) + n * k * 33; }
 static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t m, size_t k, size_t nd, size_t np, const AggProveShapeDev& shp,
                           const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd, const uint8_t* seed, uint64_t stream, uint8_t* proofs,
-                          uint8_t* commitments, int32_t* status, bool device_io, const WnlaProveShape& sh0, size_t proof_bytes) {
+                          uint8_t* commitments, int32_t* status, bool device_io, const WnlaProveShape& sh0, size_t proof_bytes, bool sec1) {
     const size_t n = m, nm = k * nd, nv = nd + 1, rows = n * k, n_rnd = agg_prove_draws(k, nd);
     WnlaProveShape sh = sh0;
     sh.n = n;
@@ -2191,7 +2369,19 @@ static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, s
     words = n * (k * 16);
     k_gprove_assemble<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(ac);
     HIP_TRY(hipGetLastError());
-    if (!device_io) {
+    if (sec1) {
+        // (a flagged instance's zero bytes come out as the identity's zero bytes: a zeroed 33-byte-point proof and k x 33 zero bytes)
+        const size_t wP = 4 + 2 * sh.rounds + k, wS = sh.nl_f + sh.nn_f, wire_pb = wire_proof_bytes(wP, wS), o_wc = align16(n * wire_pb);
+        WireMap wm;
+        wire_map_init(wm, n);
+        wire_map_add(wm, false, d + o.pout, proof_bytes, c->d_wire, wire_pb, wP);
+        wire_map_add(wm, true, d + o.pout + 64 * wP, proof_bytes, c->d_wire + 33 * wP, wire_pb, wS);
+        wire_map_add(wm, false, d + o.cout, 64 * k, c->d_wire + o_wc, 33 * k, k);
+        rc = wire_launch(wm, false, s);
+        if (rc != BPPP_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(proofs, c->d_wire, n * wire_pb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(commitments, c->d_wire + o_wc, rows * 33, hipMemcpyDeviceToHost, s));
+    } else if (!device_io) {
         HIP_TRY(hipMemcpyAsync(proofs, d + o.pout, n * proof_bytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(commitments, d + o.cout, rows * 64, hipMemcpyDeviceToHost, s));
     }
@@ -2201,14 +2391,14 @@ static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, s
 }
 static int agg_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t nd, size_t np, const uint8_t* x,
                           const uint8_t* sblind, const uint8_t* rnd, const uint8_t* seed, uint64_t stream_base, uint8_t* proofs,
-                          uint8_t* commitments, int32_t* status, bool device_io) {
+                          uint8_t* commitments, int32_t* status, bool device_io, bool sec1 = false) {
     if (!c || !label_ok(label, label_len) || !x || !sblind || (!rnd && !seed) || !proofs || !commitments) return BPPP_ERR_INVALID_ARG;
     if (!agg_prove_shape_ok(k, nd, np, (size_t)c->ng, (size_t)c->nh)) return BPPP_ERR_INVALID_ARG;
     const size_t n_rnd = agg_prove_draws(k, nd);
     if (seed && !draw_args_ok(seed, stream_base, n, n_rnd)) return BPPP_ERR_INVALID_ARG;
     if (k == 1) {
         const RecipValues v = {device_io, commitments};
-        return recip_prove_impl(c, label, label_len, nullptr, n, nd, np, nullptr, x, sblind, nullptr, nullptr, rnd, proofs, status, false, seed,
+        return recip_prove_impl(c, label, label_len, nullptr, n, nd, np, nullptr, x, sblind, nullptr, nullptr, rnd, proofs, status, sec1, seed,
                                 stream_base, &v);
     }
     if (n == 0) return BPPP_OK;
@@ -2224,11 +2414,14 @@ static int agg_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, s
     const size_t blob_bytes = agg_prove_layout(c, per, k, nd, np, sh, proof_bytes).total;
     if (device_io) { const int rc_b = ensure_blob(c, blob_bytes); if (rc_b != BPPP_OK) return rc_b; }
     else { const int rc_b = blob.take(c, blob_bytes); if (rc_b != BPPP_OK) return rc_b; }
+    const size_t wire_pb = wire_proof_bytes(4 + 2 * sh.rounds + k, sh.nl_f + sh.nn_f);
+    if (sec1) { const int rc_w = ensure_buffer(c, c->d_wire, c->wire_bytes, agg_prove_wire_bytes(per, k, wire_pb)); if (rc_w != BPPP_OK) return rc_w; }
+    const size_t out_pb = sec1 ? wire_pb : proof_bytes, out_cb = sec1 ? 33 : 64;
     for (size_t lo = 0; lo < n; lo += per) {
         const size_t m = n - lo < per ? n - lo : per;
         const int rc = agg_prove_part(c, label, label_len, m, k, nd, np, shp, x + lo * k * 32, sblind + lo * k * 32,
-                                      rnd ? rnd + lo * n_rnd * 32 : nullptr, seed, stream_base + lo, proofs + lo * proof_bytes,
-                                      commitments + lo * k * 64, status ? status + lo : nullptr, device_io, sh, proof_bytes);
+                                      rnd ? rnd + lo * n_rnd * 32 : nullptr, seed, stream_base + lo, proofs + lo * out_pb,
+                                      commitments + lo * k * out_cb, status ? status + lo : nullptr, device_io, sh, proof_bytes, sec1);
         if (rc != BPPP_OK) return rc;
     }
     if (!device_io) HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2248,6 +2441,22 @@ int bppp_reciprocal_agg_prove_values_batch_seeded(bppp_ctx* c, const uint8_t* la
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
     return agg_prove_impl(c, label, label_len, n, k, dim_nd, dim_np, x, sblind, nullptr, seed, stream_base, proofs, commitments, status, false);
+}
+// the wire form (host buffers only): the same calls with the proofs and the commitments compressed on the device before the copy back
+int bppp_reciprocal_agg_prove_values_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                size_t dim_np, const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd, uint8_t* proofs33,
+                                                uint8_t* commitments33, int32_t* status) {
+    CtxLock lock_(c);
+    if (!rnd) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_impl(c, label, label_len, n, k, dim_nd, dim_np, x, sblind, rnd, nullptr, 0, proofs33, commitments33, status, false, true);
+}
+int bppp_reciprocal_agg_prove_values_batch_seeded_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                       size_t dim_np, const uint8_t* x, const uint8_t* sblind, const uint8_t seed[32],
+                                                       uint64_t stream_base, uint8_t* proofs33, uint8_t* commitments33, int32_t* status) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_impl(c, label, label_len, n, k, dim_nd, dim_np, x, sblind, nullptr, seed, stream_base, proofs33, commitments33, status, false,
+                          true);
 }
 int bppp_reciprocal_agg_prove_values_batch_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
                                                   size_t dim_np, const void* d_x, const void* d_s, const void* d_rnd, void* d_proofs,

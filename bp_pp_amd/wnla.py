@@ -604,7 +604,8 @@ class ReciprocalRangeProofProtocol:
 
 class AggregatedReciprocalRangeProofProtocol:
     """k values of dim_nd base-dim_np digits under ONE reciprocal range proof (include/bppp.h: "AGGREGATED reciprocal range proofs";
-    bp_pp_amd/csrc/agg_core.h, agg_prove_core.h).  Exact mode, 64-byte points.  The verifier takes commitments [B, k, 64] and proofs; the
+    bp_pp_amd/csrc/agg_core.h, agg_prove_core.h).  The verifier takes commitments [B, k, 64] and proofs, exact or in RLC mode
+    (verify_batch_rlc*), in the 64-byte or the wire form (*_sec1: wire.pack of the 64-byte layouts, 33-byte points); the
     prover takes the integers: prove_values_batch* make the k value commitments and the proof on the device (include/bppp.h:
     "AGGREGATED range proofs from integers"; tests/agg_cases.py states the protocol on the oracle).  k = 1 is
     ReciprocalRangeProofProtocol."""
@@ -692,6 +693,85 @@ class AggregatedReciprocalRangeProofProtocol:
         _capi.check(_capi.symbol("bppp_reciprocal_agg_verify_batch_device")(self._w._ctx, label, len(label), n, self.k, self.dim_nd,
                                                                             self.dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept,
                                                                             d_status, d_reject_count or None))
+
+    def proof_sec1_bytes(self, rounds: int, nl: int, nn: int) -> int:
+        """Bytes of a proof in the wire form: 33 (4 + 2 rounds + k) + 32 (nl + nn)."""
+        return int(_capi.symbol("bppp_reciprocal_agg_proof_sec1_bytes")(self.k, rounds, nl, nn))
+
+    def _verify_host(self, name: str, point: int, label: bytes, commitments, proofs, rounds: int, nl: int, nn: int, seed=None):
+        commitments = _u8(commitments, (-1, self.k, point))
+        B = commitments.shape[0]
+        proofs = _u8(proofs, (B, (self.proof_sec1_bytes if point == 33 else self.proof_bytes)(rounds, nl, nn)))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        tail = () if seed is None else (_rlc_seed(seed),)
+        _capi.check(_capi.symbol(name)(self._w._ctx, label, len(label), B, self.k, self.dim_nd, self.dim_np, commitments.ctypes.data,
+                                       proofs.ctypes.data, rounds, nl, nn, acc.ctypes.data, st.ctypes.data, *tail))
+        return acc, st
+
+    def _verify_device(self, name: str, label: bytes, n: int, d_commitments: int, d_proofs: int, rounds: int, nl: int, nn: int,
+                       d_accept: int, d_status: int, d_reject_count: int, seed=None) -> None:
+        tail = () if seed is None else (_rlc_seed(seed),)
+        _capi.check(_capi.symbol(name)(self._w._ctx, label, len(label), n, self.k, self.dim_nd, self.dim_np, d_commitments, d_proofs,
+                                       rounds, nl, nn, d_accept, d_status, d_reject_count or None, *tail))
+
+    def verify_batch_sec1(self, label: bytes, commitments33, proofs33, rounds: int, nl: int, nn: int):
+        """verify_batch over the wire form (wire.pack of the 64-byte layouts): commitments33 [B, k, 33], proofs33 [B, proof_sec1_bytes];
+        an undecodable point flags its instance ST_BAD_ENCODING."""
+        return self._verify_host("bppp_reciprocal_agg_verify_batch_sec1", 33, label, commitments33, proofs33, rounds, nl, nn)
+
+    def verify_batch_sec1_device(self, label: bytes, n: int, d_commitments33: int, d_proofs33: int, rounds: int, nl: int, nn: int,
+                                 d_accept: int, d_status: int, d_reject_count: int = 0) -> None:
+        """verify_batch_sec1 over device buffers (raw device pointers), asynchronous on the context's stream."""
+        self._verify_device("bppp_reciprocal_agg_verify_batch_sec1_device", label, n, d_commitments33, d_proofs33, rounds, nl, nn, d_accept,
+                            d_status, d_reject_count)
+
+    def verify_batch_rlc(self, label: bytes, commitments, proofs, rounds: int, nl: int, nn: int, seed: bytes):
+        """verify_batch with the final sum in RLC mode (one sum per chunk of 8 instances, behind the bucket stage; what does not pass
+        is re-checked exactly): the exact call's accept / status per instance.  seed: 32 bytes the prover cannot predict."""
+        return self._verify_host("bppp_reciprocal_agg_verify_batch_rlc", 64, label, commitments, proofs, rounds, nl, nn, seed)
+
+    def verify_batch_rlc_device(self, label: bytes, n: int, d_commitments: int, d_proofs: int, rounds: int, nl: int, nn: int, d_accept: int,
+                                d_status: int, seed: bytes, d_reject_count: int = 0) -> None:
+        """verify_batch_rlc over device buffers (raw device pointers), asynchronous on the context's stream."""
+        self._verify_device("bppp_reciprocal_agg_verify_batch_rlc_device", label, n, d_commitments, d_proofs, rounds, nl, nn, d_accept,
+                            d_status, d_reject_count, seed)
+
+    def verify_batch_rlc_sec1(self, label: bytes, commitments33, proofs33, rounds: int, nl: int, nn: int, seed: bytes):
+        """verify_batch_rlc over the wire form; a flagged instance is in no weighted sum."""
+        return self._verify_host("bppp_reciprocal_agg_verify_batch_rlc_sec1", 33, label, commitments33, proofs33, rounds, nl, nn, seed)
+
+    def verify_batch_rlc_sec1_device(self, label: bytes, n: int, d_commitments33: int, d_proofs33: int, rounds: int, nl: int, nn: int,
+                                     d_accept: int, d_status: int, seed: bytes, d_reject_count: int = 0) -> None:
+        """verify_batch_rlc_sec1 over device buffers (raw device pointers), asynchronous on the context's stream."""
+        self._verify_device("bppp_reciprocal_agg_verify_batch_rlc_sec1_device", label, n, d_commitments33, d_proofs33, rounds, nl, nn,
+                            d_accept, d_status, d_reject_count, seed)
+
+    def prove_values_batch_sec1(self, label: bytes, x, s, rnd):
+        """prove_values_batch with the outputs in the wire form: (proofs33 [B, proof_sec1_bytes], commitments33 [B, k, 33], status [B],
+        (rounds, nl, nn)) -- wire.pack of prove_values_batch's outputs, compressed on the device."""
+        x, s = _u8(x, (-1, self.k, 32)), _u8(s, (-1, self.k, 32))
+        B = x.shape[0]
+        rnd = _u8(rnd, (B, self.prove_draws(), 32))
+        shape = self.proof_shape()
+        proofs, com, st = np.zeros((B, self.proof_sec1_bytes(*shape)), np.uint8), np.zeros((B, self.k, 33), np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_sec1")(self._w._ctx, label, len(label), B, self.k, self.dim_nd,
+                                                                                self.dim_np, x.ctypes.data, s.ctypes.data, rnd.ctypes.data,
+                                                                                proofs.ctypes.data, com.ctypes.data, st.ctypes.data))
+        return proofs, com, st, shape
+
+    def prove_values_batch_seeded_sec1(self, label: bytes, x, s, seed: bytes, stream_base: int):
+        """prove_values_batch_seeded with the outputs in the wire form."""
+        from .range_proof import _seed_args
+        x, s = _u8(x, (-1, self.k, 32)), _u8(s, (-1, self.k, 32))
+        B = x.shape[0]
+        seed, stream_base = _seed_args(seed, stream_base, B)
+        shape = self.proof_shape()
+        proofs, com, st = np.zeros((B, self.proof_sec1_bytes(*shape)), np.uint8), np.zeros((B, self.k, 33), np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_seeded_sec1")(self._w._ctx, label, len(label), B, self.k, self.dim_nd,
+                                                                                       self.dim_np, x.ctypes.data, s.ctypes.data, seed,
+                                                                                       stream_base, proofs.ctypes.data, com.ctypes.data,
+                                                                                       st.ctypes.data))
+        return proofs, com, st, shape
 
     def synchronize(self) -> None:
         self._w.synchronize()

@@ -687,8 +687,8 @@ BPPP_API int bppp_reciprocal_verify_batch_device(bppp_ctx* ctx, const uint8_t* l
  * k dim_nd <= |g_vec|, dim_nd + 10 <= |h_vec|, dim_np <= dim_nd + 1, rounds <= 12, nl, nn <= 4096.  k = 1 IS
  * bppp_reciprocal_verify_batch[_device] (and so the u64 kernels for the u64 shape).  The device form takes device buffers (d_status
  * required; d_reject_count: optional device int32, the number of rejected instances), is asynchronous on the context's stream and
- * runs a call of more than "max_batch" instances as consecutive parts.  Exact mode, 64-byte points: there is no SEC1 form, RLC
- * mode, caller-transcript form, sharded form or single-proof front end yet.  The prover from integers is below
+ * runs a call of more than "max_batch" instances as consecutive parts.  The wire (SEC1) form and the RLC mode follow; a
+ * caller-transcript form, a sharded form and a single-proof front end are not built.  The prover from integers is below
  * (bppp_reciprocal_agg_prove_values_batch*). */
 BPPP_API size_t bppp_reciprocal_agg_proof_bytes(size_t k, size_t rounds, size_t nl, size_t nn);
 BPPP_API int bppp_reciprocal_agg_verify_batch(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
@@ -698,6 +698,49 @@ BPPP_API int bppp_reciprocal_agg_verify_batch_device(bppp_ctx* ctx, const uint8_
                                                      size_t dim_nd, size_t dim_np, const void* d_commitments, const void* d_proofs,
                                                      size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status,
                                                      void* d_reject_count);
+/* The aggregate in the WIRE form (as bppp_reciprocal_verify_batch_sec1 below): the layout above with every point 33-byte
+ * SEC1-compressed in place (02 | 03 by the parity of y, then x; the identity is 33 zero bytes) and the scalars unchanged.
+ *   commitments33  n x k x 33, value-major
+ *   proofs33       n x bppp_reciprocal_agg_proof_sec1_bytes(k, rounds, nl, nn) = 33 (4 + 2 rounds + k) + 32 (nl + nn):
+ *                  1216 bytes at (16, 6, 1, 4); k = 1, rounds 4, nl 2, nn 1: the 525 bytes of the u64 wire proof
+ * The points are decompressed on the device by one launch over the whole call, on the context's stream in front of the "max_batch"
+ * parts, into the context's wire buffer (the host form stages its input there too); return code, accept, status and reject count
+ * are exactly those of the 64-byte form on the expanded input.  An undecodable point -- a tag other than 02 / 03 on a non-zero
+ * encoding, x >= p, x^3 + 7 not a square -- flags its instance BPPP_ST_BAD_ENCODING and touches no other.  Arguments and error
+ * codes as the 64-byte forms; k = 1 IS bppp_reciprocal_verify_batch_sec1[_device]. */
+BPPP_API size_t bppp_reciprocal_agg_proof_sec1_bytes(size_t k, size_t rounds, size_t nl, size_t nn);
+BPPP_API int bppp_reciprocal_agg_verify_batch_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                   size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds,
+                                                   size_t nl, size_t nn, uint8_t* accept, int32_t* status);
+BPPP_API int bppp_reciprocal_agg_verify_batch_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                          size_t dim_nd, size_t dim_np, const void* d_commitments33,
+                                                          const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                                          void* d_status, void* d_reject_count);
+/* The aggregate in RLC mode (as bppp_wnla_verify_batch_rlc / bppp_circuit_verify_batch_rlc): everything before the final sum is the
+ * exact pipeline in the same launch form; the final sum over the 1 + |g_vec| + |h_vec| generators runs through the bucket stage
+ * where the superchunk rule asks for it, then once per chunk of 8 instances on secretly weighted sums, and whatever does not pass
+ * is re-checked exactly.  accept / status are per instance and equal the exact call's, except with probability <= 2^-128 per invalid
+ * chunk.  seed: 32 bytes the prover cannot predict; NULL is BPPP_ERR_INVALID_ARG.  A part of fewer than 8 instances runs the exact
+ * final sum; "last_rlc_superchunk" / "last_rlc_chunk" report what the call's FIRST part used (every part but the last has its
+ * size), (0, 0) when that part had fewer than 8 instances, and are reset before the call's first allocation.  The _sec1 forms run
+ * the same expansion in front: a flagged instance has weight zero in the bucket stage, makes its chunk of 8 fall through to the
+ * exact check and is in no weighted sum.  k = 1 IS bppp_reciprocal_verify_batch_rlc[_sec1][_device]. */
+BPPP_API int bppp_reciprocal_agg_verify_batch_rlc(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
+                                                  size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl,
+                                                  size_t nn, uint8_t* accept, int32_t* status, const uint8_t seed[32]);
+BPPP_API int bppp_reciprocal_agg_verify_batch_rlc_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                         size_t dim_nd, size_t dim_np, const void* d_commitments, const void* d_proofs,
+                                                         size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status,
+                                                         void* d_reject_count, const uint8_t seed[32]);
+BPPP_API int bppp_reciprocal_agg_verify_batch_rlc_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                       size_t dim_nd, size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33,
+                                                       size_t rounds, size_t nl, size_t nn, uint8_t* accept, int32_t* status,
+                                                       const uint8_t seed[32]);
+BPPP_API int bppp_reciprocal_agg_verify_batch_rlc_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                              size_t dim_nd, size_t dim_np, const void* d_commitments33,
+                                                              const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                                                              void* d_accept, void* d_status, void* d_reject_count,
+                                                              const uint8_t seed[32]);
 /* The optional random-linear-combination mode (as bppp_u64_verify_batch_rlc above) for the reciprocal verifier at any dimensions:
  * the final MSM over all 1 + |g_vec| + |h_vec| generators -- 769 bases for BASELINE configs[4]'s shape, about half of that
  * verifier's time -- is done once per chunk of 8 instances on secretly weighted sums; chunks that do not pass are re-checked
@@ -890,6 +933,18 @@ BPPP_API int bppp_reciprocal_agg_prove_values_batch_seeded_device(bppp_ctx* ctx,
                                                                   size_t dim_nd, size_t dim_np, const void* d_x, const void* d_s,
                                                                   const uint8_t seed[32], uint64_t stream_base, void* d_proofs,
                                                                   void* d_commitments, void* d_status);
+/* the same with the outputs in the wire form: proofs33 n x bppp_reciprocal_agg_proof_sec1_bytes(k, rounds, nl, nn), commitments33
+ * n x k x 33 -- byte for byte the calls above with every point compressed (on the device, per part, before the copy back).  A
+ * flagged instance gets a zeroed proof and k x 33 zero bytes (the identity's encoding).  Host buffers only: device-buffer SEC1
+ * provers are not built.  k = 1: the reciprocal prover from integers, its outputs compressed the same way. */
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                         size_t dim_nd, size_t dim_np, const uint8_t* x, const uint8_t* s,
+                                                         const uint8_t* rnd, uint8_t* proofs33, uint8_t* commitments33,
+                                                         int32_t* status /* n or NULL */);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_seeded_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k,
+                                                                size_t dim_nd, size_t dim_np, const uint8_t* x, const uint8_t* s,
+                                                                const uint8_t seed[32], uint64_t stream_base, uint8_t* proofs33,
+                                                                uint8_t* commitments33, int32_t* status /* n or NULL */);
 
 /* Profiling aid for bench.py: when enabled, every kernel launch of the verify pipeline is bracketed by HIP events on
  * the context's stream; bppp_ctx_get_timings returns accumulated milliseconds and launch counts per kernel since the
