@@ -73,6 +73,15 @@ EXPORTS += AGG_WIRE_EXPORTS
 RLC_SEC1_EXPORTS = [name for name in EXPORTS
                     if (name.endswith(("_rlc_sec1", "_rlc_sec1_device")) or "_one_sec1" in name) and name not in AGG_WIRE_EXPORTS]
 
+# the aggregate on the caller's transcripts (include/bppp.h: "The aggregate on the CALLER'S transcripts", "The aggregate prover on
+# the CALLER'S transcripts"); bound only when the library has them, in a block of their own in lib()
+AGG_TRANSCRIPT_VERIFY_EXPORTS = ["bppp_reciprocal_agg_verify_batch_transcript", "bppp_reciprocal_agg_verify_batch_transcript_device",
+                                 "bppp_reciprocal_agg_verify_batch_transcript_sec1"]
+AGG_TRANSCRIPT_PROVE_EXPORTS = ["bppp_reciprocal_agg_prove_values_batch_transcript", "bppp_reciprocal_agg_prove_values_batch_transcript_seeded",
+                                "bppp_reciprocal_agg_prove_values_batch_transcript_device"]
+AGG_TRANSCRIPT_EXPORTS = AGG_TRANSCRIPT_VERIFY_EXPORTS + AGG_TRANSCRIPT_PROVE_EXPORTS
+EXPORTS += AGG_TRANSCRIPT_EXPORTS
+
 _lib = None
 
 
@@ -307,6 +316,16 @@ def lib():
         L.bppp_reciprocal_agg_prove_values_batch_sec1.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp]
         L.bppp_reciprocal_agg_prove_values_batch_seeded_sec1.argtypes = [vp, u8p, sz, sz, sz, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
         for name in AGG_WIRE_VERIFY_EXPORTS + AGG_WIRE_PROVE_EXPORTS:
+            getattr(L, name).restype = i32
+    # the aggregate on the caller's transcripts: the label forms' lists with (label, label_len, n) -> (n, states, n_states), states_out last
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_reciprocal_agg_verify_batch_transcript"):
+        host = [vp, sz, vp, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        L.bppp_reciprocal_agg_verify_batch_transcript.argtypes = L.bppp_reciprocal_agg_verify_batch_transcript_sec1.argtypes = host + [vp]
+        L.bppp_reciprocal_agg_verify_batch_transcript_device.argtypes = host + [vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_transcript.argtypes = [vp, sz, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_transcript_seeded.argtypes = [vp, sz, vp, sz, sz, sz, sz, vp, vp, u8p, u64, vp, vp, vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_transcript_device.argtypes = [vp, sz, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        for name in AGG_TRANSCRIPT_EXPORTS:
             getattr(L, name).restype = i32
     L.bppp_strerror.argtypes = [i32]
     L.bppp_strerror.restype = C.c_char_p

@@ -2,7 +2,8 @@
 // (reciprocal.rs:150-214) written for k values that share one multiplicity vector, verified by ArithmeticCircuit::verify with k
 // commitments (circuit.rs:154-256); tests/agg_cases.py states it on the oracle.  nv = nd + 1, nm = k nd, J = i nd + d (value i, digit d).
 //
-// Transcript: app_point("reciprocal_commitment", V_i) for i < k | e | circuit.verify([V_i + R_i], t, circuit_proof).
+// Transcript: app_point("reciprocal_commitment", V_i) for i < k | e | circuit.verify([V_i + R_i], t, circuit_proof), on
+// Transcript::new(label) or on the caller's own transcript (AggWs::tio, as the other generic verifiers: verify_ws.h).
 // Proof layout (per instance, proof_bytes = 64 (4 + 2 rounds + k) + 32 (nl + nn)):
 //   c_l, c_r, c_o, c_s | r[rounds] | x[rounds] | R_0 .. R_{k-1} | l[nl] | n[nn];   commitments: k x 64, value-major.
 //
@@ -46,7 +47,7 @@ struct AggWs {
     uint8_t* wn_mu;                  // N x 32
     FbTable fb;                      // bases: 0 g | 1..NG g_vec||g_vec_ | NG+1.. h_vec||h_vec_
     strobe base;
-    TranscriptIo tio;                // (unused: every instance starts from Transcript::new(label); the WNLA stage's setup reads it)
+    TranscriptIo tio;                // the caller's transcripts (the _transcript entry points); states null: Transcript::new(label)
 };
 
 HD void agg_st_fe(u32* base, size_t N, size_t t, int slot, const fe& a) {
@@ -64,6 +65,10 @@ HD void agg_ld_fe(fe& a, const u32* base, size_t N, size_t t, int slot, int mag)
 // k nd entries of pn_tau, almost the whole kernel at 16 x 16, is cut into G RUNS of consecutive entries; the TAIL belongs to lane 0.
 // (The host emulation calls the pieces itself and adds the runs' sums where the device shuffles.)
 struct AggHead { sc e, lambda, beta, delta, tau, mu, mu_inv, tau_inv, tau2, S, lam_nv; int32_t status; };
+// TX: the instance's transcript begins through tio_begin (the caller's pre-loaded state, or `base` when there is none).  The label
+// forms' kernels are the TX = false instantiation -- `tr = w.base`, the code they always were -- and the _transcript forms' kernels
+// the TX = true one, so that the label path's registers and scratch do not pay for the 200-byte state tio_begin decodes.
+template <bool TX = false>
 HD void agg_phase1_head(const AggWs& w, size_t t, AggHead& h) {
     const size_t N = w.N;
     const int k = w.k, nd = w.nd, np = w.np;
@@ -78,7 +83,10 @@ HD void agg_phase1_head(const AggWs& w, size_t t, AggHead& h) {
 #pragma nounroll
     for (int i = 0; i < k; i++) { apt P; ok &= apt_from_xy64(P, pv + 64 * i); ok &= apt_from_xy64(P, pr + 64 * i); }
     if (!ok) { status |= ST_BAD_ENCODING; CL = zero_pt; CR = zero_pt; CO = zero_pt; CS = zero_pt; }
+    // TX: the caller's pre-loaded transcript; a state merlin cannot be in flags the instance, which then runs from `base` and gets its
+    // input state back (tio_export)
     strobe tr = w.base;
+    if (TX) tio_begin(tr, status, w.tio, w.base, t);
     // V_i into the transcript; V_i + R_i by the complete law (V_i = R_i, V_i = -R_i and identities included), kept projective with the
     // running products of their Z: ONE field inversion brings all k to affine
     fe one_fe, prodz;
@@ -295,10 +303,11 @@ HD void agg_phase1_tail(const AggWs& w, size_t t, const AggHead& h, const sc& ps
     w.status[t] = h.status;
 }
 // q, G: lane q of the G consecutive lanes of instance t (every lane of a group must be active); G = 1: the one-lane form
+template <bool TX = false>
 HD void agg_phase1(const AggWs& w, size_t t, int q = 0, int G = 1) {
     AggHead h;
     sc ps, musum;
-    agg_phase1_head(w, t, h);
+    agg_phase1_head<TX>(w, t, h);
     agg_phase1_run(w, t, h, q, G, ps, musum);
 #if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
     if (G > 1) { sc_group_sum16(ps, G); sc_group_sum16(musum, G); }

@@ -1,6 +1,6 @@
 // Batched PROVER of the aggregated reciprocal range proof: k values of dim_nd base-dim_np digits under one proof, from the integers
 // (agg_core.h has the verifier and the circuit; tests/agg_cases.py::prove states the protocol on the oracle).  Per instance:
-//   transcript = Transcript::new(label); app_point("reciprocal_commitment", V_i) for i < k; e = challenge("reciprocal_challenge");
+//   transcript = Transcript::new(label), or the caller's own (AggProveWs::tio); app_point("reciprocal_commitment", V_i) for i < k; e = challenge("reciprocal_challenge");
 //   r_{i,d} = (digit_{i,d} + e)^-1;  R_i = rb_i h_vec[0] + sum_d r_{i,d} h_vec[9 + d];
 //   ArithmeticCircuit::prove over the k commitments V_i + R_i with v_i = [x_i, r_i...], s_v[i] = s_i + rb_i, w_l = all digits
 //   (value-major), w_r = all reciprocals, w_o = the multiplicities over all k nd digits.
@@ -60,6 +60,8 @@ struct AggProveWs {
     FbTable fb_ct;             // "ct_prover": the reciprocals and rb_i are secret
     int ct;
     strobe base;
+    TranscriptIo tio;          // the caller's transcripts (the _transcript entry points); states null: Transcript::new(label)
+    int divergent_positions;   // 1: the instances of one wavefront may sit at different sponge positions (per-instance input states)
 };
 HD void agg_prove_pole_ranges(FbRanges& rg, const AggProveWs& w) {
     rg.n = 2;
@@ -128,6 +130,8 @@ HD int32_t agg_prove_witness(const AggProveWs& w, size_t t) {
 
 // transcript over the k value commitments to e; reciprocals and the circuit's per-instance values from one inversion; the circuit
 // prover's inputs; the scalar rows of the pole commitments
+// TX: as agg_phase1_head's -- the label forms' kernel is the TX = false instantiation, `tr = w.base`
+template <bool TX = false>
 HD void agg_prove_stage_r1(const AggProveWs& w, size_t t) {
     const size_t N = w.N, rows = N * (size_t)w.k;
     const int k = w.k, nd = w.nd, np = w.np, nm = k * nd, nv = nd + 1;
@@ -135,7 +139,9 @@ HD void agg_prove_stage_r1(const AggProveWs& w, size_t t) {
     bool ok = true;
     sc one, e;
     sc_set_u32(one, 1);
+    // TX: the caller's pre-loaded transcript; a state merlin cannot be in flags the instance: a zeroed proof, and its input state back
     strobe tr = w.base;
+    if (TX) tio_begin(tr, status, w.tio, w.base, t);
 #pragma nounroll
     for (int i = 0; i < k; i++) {
         apt V;
@@ -197,6 +203,11 @@ HD void agg_prove_stage_r1(const AggProveWs& w, size_t t) {
     }
     if (!ok) status |= ST_BAD_ENCODING;
     w.status[t] = status;
+}
+// The caller's transcript after the prove: tio_export with every status bit in its mask -- an instance whose proof is zeroed (out of
+// range, a non-canonical input, a degenerate challenge, an invalid state) gets its input state back: nothing was proved on it.
+HD void agg_prove_export(const TranscriptIo& io, const strobe& base, const u32* tstate, size_t N, const int32_t* status, size_t t) {
+    tio_export(io, base, tstate, N, status, t, ~0);
 }
 // R_i and V_i + R_i (the complete law: V_i = R_i, V_i = -R_i and identities included) to affine, 2 k points from one field inversion
 HD void agg_prove_stage_r2(const AggProveWs& w, size_t t) {

@@ -75,9 +75,12 @@ struct TxDev {
         return BPPP_OK;
     }
     // after the last prover kernel: serialize every instance's transcript and queue the copy back
-    int finish(const HostTranscripts* tx, const TranscriptIo& io, const strobe& base, const u32* tstate, size_t n, const int32_t* status, hipStream_t s) {
+    // flagged_back (the provers from integers): every instance whose proof is zeroed -- any status -- gets its input state back
+    int finish(const HostTranscripts* tx, const TranscriptIo& io, const strobe& base, const u32* tstate, size_t n, const int32_t* status, hipStream_t s,
+               bool flagged_back = false) {
         if (!tx || !tx->states_out) return BPPP_OK;
-        k_gprove_export_states<<<(unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(io, base, tstate, n, status);
+        if (flagged_back) k_aprove_export_states<<<(unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(io, base, tstate, n, status);
+        else k_gprove_export_states<<<(unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(io, base, tstate, n, status);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(tx->states_out, d_out, n * 203, hipMemcpyDeviceToHost, s));
         return BPPP_OK;
@@ -741,7 +744,7 @@ static int agg_verify_check_args(const bppp_ctx* c, size_t k, size_t dim_nd, siz
 // instances runs the exact sum; everything before the final sum is the exact pipeline in the plan's launch form either way
 static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                                   const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
-                                  int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed = nullptr) {
+                                  int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed = nullptr, const TranscriptIo* dtio = nullptr) {
     const GenericPlan plan = plan_generic(GENERIC_FORM_AGGREGATE, n, rounds, generic_knobs_of(c), n, 1, 4 + k);
     const bool rlc = rlc_seed && wnla_rlc_applies(n);
     const AggVerifyLayout o = agg_verify_layout(c, n, k, dim_nd, dim_np, rounds, rlc);
@@ -758,6 +761,7 @@ static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t labe
     r.wn_commit = d + o.wc; r.wn_c = d + o.wcv; r.wn_rho = d + o.rho; r.wn_mu = d + o.mu;
     r.fb = fb_table_of(c, n);
     t_new(r.base, label, (u32)label_len);
+    if (dtio) r.tio = *dtio;      // the caller's transcripts: phase 1 starts on them, the WNLA stage (tio, divergent_positions) exports them
     WnlaWs w = wnla_ws_continuing(c, r, 4 + k, nl, nn, d_acc, (u32*)(d + o.ys), (u32*)(d + o.tab), (u32*)(d + o.msc));
     const unsigned blocks = blocks_of(n);
     int rc;
@@ -776,7 +780,11 @@ static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t labe
         HIP_TRY(hipStreamWaitEvent(a, c->ev_tab, 0));
         GLAUNCH(a, K_WNLA_TABLES, launch_wnla_tables(w, plan.tab_parts, n, blocks, a));
     }
-    if (G > 1) GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1_grp<<<(unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK), BPPP_BLOCK, 0, s>>>(r, G));
+    const unsigned p1_blocks = G > 1 ? (unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK) : blocks;
+    if (r.tio.states) {      // the caller's transcripts: the _tx kernels, same launch form
+        if (G > 1) GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1_grp_tx<<<p1_blocks, BPPP_BLOCK, 0, s>>>(r, G));
+        else GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1_tx<<<p1_blocks, BPPP_BLOCK, 0, s>>>(r));
+    } else if (G > 1) GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1_grp<<<p1_blocks, BPPP_BLOCK, 0, s>>>(r, G));
     else GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(r));
     if (beside) {
         HIP_TRY(hipEventRecord(c->ev_fork, s));
@@ -801,13 +809,20 @@ static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t labe
 static size_t agg_part_size(const bppp_ctx* c, size_t n) { return n < c->max_batch ? n : c->max_batch; }
 static int agg_verify_parts(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                             const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
-                            int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed) {
+                            int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed, const TranscriptIo* dtio = nullptr) {
     const size_t per = agg_part_size(c, n), pb = agg_proof_bytes(k, rounds, nl, nn);
     unsigned first_super_m = 0, first_chunk = 0;
     for (size_t lo = 0; lo < n; lo += per) {
         const size_t m = n - lo < per ? n - lo : per;
+        // a part's own slice of the caller's states (or the one shared state) and of states_out
+        TranscriptIo pio = {nullptr, 0, nullptr, 0};
+        if (dtio) {
+            const bool shared = dtio->n_states == 1;
+            pio.states = dtio->states + (shared ? 0 : 203 * lo); pio.n_states = shared ? 1 : m;
+            pio.states_out = dtio->states_out ? dtio->states_out + 203 * lo : nullptr;
+        }
         const int rc = agg_verify_device_impl(c, label, label_len, m, k, dim_nd, dim_np, d_com + 64 * k * lo, d_proofs + pb * lo, rounds, nl, nn,
-                                              d_acc + lo, d_st + lo, d_ws, rlc_seed);
+                                              d_acc + lo, d_st + lo, d_ws, rlc_seed, dtio ? &pio : nullptr);
         if (rc != BPPP_OK) return rc;
         if (lo == 0) { first_super_m = c->last_rlc_super_m; first_chunk = c->last_rlc_chunk; }
     }
@@ -825,7 +840,7 @@ static int agg_verify_prepare(bppp_ctx* c, size_t per, const uint8_t* rlc_seed) 
 // a call over device buffers, arguments checked and k > 1: asynchronous on the context's stream, the workspace in the grow-only d_gws
 static int agg_verify_device_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                                  const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
-                                 void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
+                                 void* d_status, void* d_reject_count, const uint8_t* rlc_seed, const TranscriptIo* dtio = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
     if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
     if (n == 0) return BPPP_OK;
@@ -835,7 +850,7 @@ static int agg_verify_device_run(bppp_ctx* c, const uint8_t* label, size_t label
     rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_verify_layout(c, per, k, dim_nd, dim_np, rounds, rlc_seed != nullptr).total);
     if (rc != BPPP_OK) return rc;
     rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, rounds, nl, nn,
-                          (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws, rlc_seed);
+                          (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws, rlc_seed, dtio);
     if (rc != BPPP_OK || !d_reject_count) return rc;
     k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
     HIP_TRY(hipGetLastError());
@@ -855,19 +870,24 @@ static int agg_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t lab
 }
 static int agg_verify_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                                 const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
-                                int32_t* status, const uint8_t* rlc_seed) {
+                                int32_t* status, const uint8_t* rlc_seed, const HostTranscripts* tx = nullptr) {
+    // tx (the _transcript form): the callers' transcripts in (1 or n), each instance's advanced transcript out; label null
     if (!c || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
     int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
+    if (tx && (!tx->states || (tx->n_states != 1 && tx->n_states != n))) return BPPP_ERR_INVALID_ARG;
     if (k == 1)
-        return recip_verify_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr, rlc_seed);
+        return recip_verify_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, tx, rlc_seed);
     if (n == 0) return BPPP_OK;
+    rc = check_host_transcripts(tx, n);
+    if (rc != BPPP_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t per = agg_part_size(c, n);
     rc = agg_verify_prepare(c, per, rlc_seed);
     if (rc != BPPP_OK) return rc;
     const size_t pb = agg_proof_bytes(k, rounds, nl, nn);
-    const size_t o_com = 0, o_pr = align16(n * k * 64), o_acc = align16(o_pr + n * pb), o_st = align16(o_acc + n), o_ws = align16(o_st + n * 4),
+    const size_t o_com = 0, o_pr = align16(n * k * 64), o_acc = align16(o_pr + n * pb), o_st = align16(o_acc + n), o_ti = align16(o_st + n * 4),
+                 o_to = align16(o_ti + (tx ? tx->n_states * 203 : 0)), o_ws = align16(o_to + (tx && tx->states_out ? n * 203 : 0)),
                  total = o_ws + agg_verify_layout(c, per, k, dim_nd, dim_np, rounds, rlc_seed != nullptr).total;
     WnlaBlob blob;
     { const int rc_b = blob.take(c, total); if (rc_b != BPPP_OK) return rc_b; }
@@ -875,9 +895,15 @@ static int agg_verify_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_
     hipStream_t s = c->stream;
     HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * k * 64, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_pr, proofs, n * pb, hipMemcpyHostToDevice, s));
+    TranscriptIo dtio = {nullptr, 0, nullptr, 0};
+    if (tx) {
+        HIP_TRY(hipMemcpyAsync(d + o_ti, tx->states, tx->n_states * 203, hipMemcpyHostToDevice, s));
+        dtio.states = d + o_ti; dtio.n_states = tx->n_states; dtio.states_out = tx->states_out ? d + o_to : nullptr;
+    }
     rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, d + o_com, d + o_pr, rounds, nl, nn, d + o_acc, (int32_t*)(d + o_st), d + o_ws,
-                          rlc_seed);
+                          rlc_seed, tx ? &dtio : nullptr);
     if (rc != BPPP_OK) return rc;
+    if (dtio.states_out) HIP_TRY(hipMemcpyAsync(tx->states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -911,6 +937,57 @@ int bppp_reciprocal_agg_verify_batch_rlc(bppp_ctx* c, const uint8_t* label, size
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
     return agg_verify_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, seed);
+}
+// ---- the aggregate on the CALLER'S transcripts (`t: &mut Transcript`): the states in (1 shared or n), every instance's advanced
+//      transcript out; an instance flagged BPPP_ST_BAD_ENCODING gets its input state back.  No RLC form, as for the other protocols.
+int bppp_reciprocal_agg_verify_batch_transcript(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, size_t k, size_t dim_nd,
+                                                size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl,
+                                                size_t nn, uint8_t* accept, int32_t* status, uint8_t* states_out) {
+    CtxLock lock_(c);
+    if (!states) return BPPP_ERR_INVALID_ARG;
+    const HostTranscripts tx = {states, n_states, states_out};
+    return agg_verify_host_impl(c, nullptr, 0, n, k, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr, &tx);
+}
+// k = 1 over device buffers: the reciprocal verifier on the caller's device states (the u64 kernels for the u64 shape), one launch chain
+// on the context's stream with the workspace in the grow-only buffer
+static int recip_verify_transcript_device(bppp_ctx* c, size_t n, const void* d_states, size_t n_states, size_t dim_nd, size_t dim_np,
+                                          const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                          void* d_status, void* d_reject_count, void* d_states_out) {
+    int rc = recip_verify_check_args(c, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (recip_is_u64_shape(c, dim_nd, dim_np, rounds, nl, nn)) {
+        const VerifyTranscripts tx = {d_states, n_states, d_states_out};
+        return verify_device_impl(c, nullptr, 0, n, d_commitments, d_proofs, d_accept, d_status, nullptr, d_reject_count, nullptr, &tx);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
+    if (n == 0) return BPPP_OK;
+    rc = ensure_straus_capacity(c, n);
+    if (rc != BPPP_OK) return rc;
+    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, recip_verify_ws_bytes(c, n, dim_nd, dim_np, rounds, false));
+    if (rc != BPPP_OK) return rc;
+    const TranscriptIo dtio = {(const uint8_t*)d_states, n_states, (uint8_t*)d_states_out, 0};
+    rc = recip_verify_device_impl(c, nullptr, 0, n, dim_nd, dim_np, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, rounds, nl, nn,
+                                  (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws, &dtio, nullptr);
+    if (rc != BPPP_OK || !d_reject_count) return rc;
+    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
+    HIP_TRY(hipGetLastError());
+    return BPPP_OK;
+}
+// device buffers: the states cannot be read here, so a state merlin cannot be in flags its instance (BPPP_ST_BAD_ENCODING) on the device
+int bppp_reciprocal_agg_verify_batch_transcript_device(bppp_ctx* c, size_t n, const void* d_states, size_t n_states, size_t k, size_t dim_nd,
+                                                       size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
+                                                       size_t nn, void* d_accept, void* d_status, void* d_reject_count, void* d_states_out) {
+    CtxLock lock_(c);
+    if (!c || !d_states || (n_states != 1 && n_states != n) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
+    const int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (k == 1)
+        return recip_verify_transcript_device(c, n, d_states, n_states, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
+                                              d_reject_count, d_states_out);
+    const TranscriptIo dtio = {(const uint8_t*)d_states, n_states, (uint8_t*)d_states_out, 0};
+    return agg_verify_device_run(c, nullptr, 0, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status, d_reject_count,
+                                 nullptr, &dtio);
 }
 
 // ---------------------------------------------------------------- generic ArithmeticCircuit (circuit.rs:95-256)
@@ -1513,7 +1590,8 @@ static int recip_pattern_get(bppp_ctx* c, size_t nd, size_t np, RecipPatternDev&
 // made on the device from x and s (recip_witness_core.h; recip_prove_core.h: RecipCommitWs), and the commitments go back to the caller.
 // device: x, s, rnd, proofs, commitments_out and status are DEVICE memory, read and written in place, and the call is asynchronous on
 // the context's stream.
-struct RecipValues { bool device; uint8_t* commitments_out; };
+// d_tx (the aggregate prover's k = 1 on the caller's transcripts, device buffers): the states where they are, in place of `tx`
+struct RecipValues { bool device; uint8_t* commitments_out; const TranscriptIo* d_tx = nullptr; };
 
 // ReciprocalRangeProofProtocol::prove (reciprocal.rs:110-146) for runtime dim_nd / dim_np: the inputs placed in the call's blob (uploaded;
 // in the device-resident forms used where they are), then the launch chain, then the proofs back.
@@ -1583,6 +1661,7 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
     TxDev txd;
     int rc = txd.begin(c, tx, n, s, r.tio, r.divergent_positions);
     if (rc != BPPP_OK) return rc;
+    if (values && values->d_tx) { r.tio = *values->d_tx; r.divergent_positions = r.tio.n_states != 1; }
     CircuitProveWs p;
     std::memset(&p, 0, sizeof p);
     p.base = r.base; p.tio = r.tio; p.divergent_positions = r.divergent_positions;
@@ -1662,9 +1741,26 @@ static int recip_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len,
             HIP_TRY(hipMemcpyAsync(values->commitments_out, c->d_wire + o_wc, n * 33, back, s));
         } else {
             if (!device_io) HIP_TRY(hipMemcpyAsync(proofs, d + o_pout, n * proof_bytes, back, s));
-            HIP_TRY(hipMemcpyAsync(values->commitments_out, d + o_com, n * 64, back, s));
+            if (values->d_tx) {
+                // device states can be invalid, which stage r1 finds behind the commitment kernels: the commitments through the
+                // assembly kernel too, so that such an instance's is zeroed with its proof (as agg_prove_part's)
+                ProofAssembleWs ac;
+                std::memset(&ac, 0, sizeof ac);
+                ac.N = n; ac.proof_bytes = 64; ac.nseg = 1; ac.status = p.status; ac.out = values->commitments_out;
+                ac.src[0] = d + o_com; ac.bytes[0] = 64;
+                k_gprove_assemble<<<(unsigned)((n * 16 + 255) / 256), 256, 0, s>>>(ac);
+                HIP_TRY(hipGetLastError());
+            } else HIP_TRY(hipMemcpyAsync(values->commitments_out, d + o_com, n * 64, back, s));
         }
         if (status) HIP_TRY(hipMemcpyAsync(status, p.status, n * 4, back, s));
+        // the caller's transcripts (the aggregate's k = 1): a zeroed instance gets its input state back
+        if (values->d_tx && p.tio.states_out) {
+            k_aprove_export_states<<<blocks, BPPP_BLOCK, 0, s>>>(p.tio, p.base, p.tstate, n, p.status);
+            HIP_TRY(hipGetLastError());
+        } else {
+            rc = txd.finish(tx, p.tio, p.base, p.tstate, n, p.status, s, true);
+            if (rc != BPPP_OK) return rc;
+        }
         HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
         if (!device_io) HIP_TRY(hipStreamSynchronize(s));
         return BPPP_OK;
@@ -1850,7 +1946,7 @@ static size_t agg_sec1_exp_bytes(size_t n, size_t k, size_t rounds, size_t nl, s
 // arguments checked, k > 1; d_exp: agg_sec1_exp_bytes in the wire buffer
 static int agg_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                         const uint8_t* d_com33, const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status,
-                        void* d_reject_count, uint8_t* d_exp, const uint8_t* rlc_seed) {
+                        void* d_reject_count, uint8_t* d_exp, const uint8_t* rlc_seed, const TranscriptIo* dtio = nullptr) {
     const size_t o_p = align16(n * k * 64);
     WireMap m;
     wire_map_init(m, n);
@@ -1859,7 +1955,7 @@ static int agg_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, siz
     const int rc = wire_launch(m, true, c->stream);
     if (rc != BPPP_OK) return rc;
     return agg_verify_device_run(c, label, label_len, n, k, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status,
-                                 d_reject_count, rlc_seed);
+                                 d_reject_count, rlc_seed, dtio);
 }
 static int agg_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                                 const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
@@ -1900,17 +1996,26 @@ int bppp_reciprocal_agg_verify_batch_rlc_sec1_device(bppp_ctx* c, const uint8_t*
 // host buffers: the 33-byte input staged in the wire buffer too, in front of accept, status and the expanded form
 static int agg_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                               const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
-                              int32_t* status, const uint8_t* rlc_seed) {
+                              int32_t* status, const uint8_t* rlc_seed, const HostTranscripts* tx = nullptr) {
+    // tx (the _transcript_sec1 form): as agg_verify_host_impl's; the states staged in the wire buffer with the rest
     if (!c || !label_ok(label, label_len) || !commitments33 || !proofs33 || !accept) return BPPP_ERR_INVALID_ARG;
     int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
-    if (k == 1)
+    if (tx && (!tx->states || (tx->n_states != 1 && tx->n_states != n))) return BPPP_ERR_INVALID_ARG;
+    if (k == 1) {
+        if (tx)
+            return recip_verify_sec1_transcript_host(c, n, tx->states, tx->n_states, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept,
+                                                     status, tx->states_out);
         return recip_sec1_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, rlc_seed);
+    }
     if (n == 0) return BPPP_OK;
+    rc = check_host_transcripts(tx, n);
+    if (rc != BPPP_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
     const size_t pb = wire_proof_bytes(4 + 2 * rounds + k, nl + nn);
-    const size_t o_c = 0, o_p = align16(n * k * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_e = align16(o_s + n * 4),
+    const size_t o_c = 0, o_p = align16(n * k * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_ti = align16(o_s + n * 4),
+                 o_to = align16(o_ti + (tx ? tx->n_states * 203 : 0)), o_e = align16(o_to + (tx && tx->states_out ? n * 203 : 0)),
                  total = o_e + agg_sec1_exp_bytes(n, k, rounds, nl, nn);
     rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
     if (rc != BPPP_OK) return rc;
@@ -1919,8 +2024,15 @@ static int agg_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_le
     hipStream_t s = c->stream;
     HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * k * 33, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
-    rc = agg_sec1_run(c, label, label_len, n, k, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, nullptr, d + o_e, rlc_seed);
+    TranscriptIo dtio = {nullptr, 0, nullptr, 0};
+    if (tx) {
+        HIP_TRY(hipMemcpyAsync(d + o_ti, tx->states, tx->n_states * 203, hipMemcpyHostToDevice, s));
+        dtio.states = d + o_ti; dtio.n_states = tx->n_states; dtio.states_out = tx->states_out ? d + o_to : nullptr;
+    }
+    rc = agg_sec1_run(c, label, label_len, n, k, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, nullptr, d + o_e, rlc_seed,
+                      tx ? &dtio : nullptr);
     if (rc != BPPP_OK) return rc;
+    if (dtio.states_out) HIP_TRY(hipMemcpyAsync(tx->states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1932,6 +2044,15 @@ int bppp_reciprocal_agg_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, siz
                                           uint8_t* accept, int32_t* status) {
     CtxLock lock_(c);
     return agg_sec1_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, nullptr);
+}
+// the wire form on the caller's transcripts (host buffers): the expansion in front is the label form's
+int bppp_reciprocal_agg_verify_batch_transcript_sec1(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, size_t k, size_t dim_nd,
+                                                     size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds,
+                                                     size_t nl, size_t nn, uint8_t* accept, int32_t* status, uint8_t* states_out) {
+    CtxLock lock_(c);
+    if (!states) return BPPP_ERR_INVALID_ARG;
+    const HostTranscripts tx = {states, n_states, states_out};
+    return agg_sec1_host_impl(c, nullptr, 0, n, k, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, nullptr, &tx);
 }
 int bppp_reciprocal_agg_verify_batch_rlc_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
                                               size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl,
@@ -2273,7 +2394,9 @@ static size_t agg_prove_part_size(const bppp_ctx* c, size_t n, size_t k, size_t 
 static size_t agg_prove_wire_bytes(size_t n, size_t k, size_t wire_pb) { return align16(n * wire_pb) + n * k * 33; }
 static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t m, size_t k, size_t nd, size_t np, const AggProveShapeDev& shp,
                           const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd, const uint8_t* seed, uint64_t stream, uint8_t* proofs,
-                          uint8_t* commitments, int32_t* status, bool device_io, const WnlaProveShape& sh0, size_t proof_bytes, bool sec1) {
+                          uint8_t* commitments, int32_t* status, bool device_io, const WnlaProveShape& sh0, size_t proof_bytes, bool sec1,
+                          const HostTranscripts* tx = nullptr) {
+    // tx: this part's slice of the caller's transcripts -- host pointers in the host forms, device pointers in the device form
     const size_t n = m, nm = k * nd, nv = nd + 1, rows = n * k, n_rnd = agg_prove_draws(k, nd);
     WnlaProveShape sh = sh0;
     sh.n = n;
@@ -2300,6 +2423,14 @@ static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, s
     a.fb = fb_table_of(c, rows);
     { const int rc_ct = ct_setup(c, a.fb_ct, a.ct, rows); if (rc_ct != BPPP_OK) return rc_ct; }      // x_i, s_i, rb_i and the reciprocals are secret
     t_new(a.base, label, (u32)label_len);
+    TxDev txd;
+    if (tx && device_io) {
+        a.tio.states = tx->states; a.tio.n_states = tx->n_states; a.tio.states_out = tx->states_out;
+        a.divergent_positions = tx->n_states != 1;
+    } else {
+        rc = txd.begin(c, tx, n, s, a.tio, a.divergent_positions);
+        if (rc != BPPP_OK) return rc;
+    }
     // the value commitments: the reciprocal prover's commitment kernels over N k rows
     RecipCommitWs cw;
     std::memset(&cw, 0, sizeof cw);
@@ -2308,7 +2439,7 @@ static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, s
     // the circuit prover on the aggregate's circuit: closed-form collect, so no pattern
     CircuitProveWs p;
     std::memset(&p, 0, sizeof p);
-    p.base = a.base;
+    p.base = a.base; p.tio = a.tio; p.divergent_positions = a.divergent_positions;
     CircuitDev& cd = p.cd;
     cd.nm = (int)nm; cd.no = (int)np; cd.k = (int)k; cd.nl = (int)(k * nv); cd.nv = (int)nv; cd.nw = (int)(2 * nm + np); cd.f_l = 1; cd.f_m = 0;
     cd.a_l = (const u32*)(shp.d + shp.al); cd.a_m = (const u32*)(shp.d + shp.am); cd.inst_vals = a.inst_vals;
@@ -2329,7 +2460,8 @@ static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, s
         k_rprove_commit_store<<<row_blocks, BPPP_BLOCK, 0, s>>>(cw);
     });
     GLAUNCH(s, K_APROVE_POLES, {
-        k_aprove_stage_r1<<<blocks, BPPP_BLOCK, 0, s>>>(a);
+        if (a.tio.states) k_aprove_stage_r1_tx<<<blocks, BPPP_BLOCK, 0, s>>>(a);
+        else k_aprove_stage_r1<<<blocks, BPPP_BLOCK, 0, s>>>(a);
         k_aprove_msm<<<row_fb_blocks, BPPP_FB_BLOCK, 0, s>>>(a);
         k_aprove_stage_r2<<<blocks, BPPP_BLOCK, 0, s>>>(a);
     });
@@ -2338,7 +2470,8 @@ static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, s
         k_cprove_stage_a<<<blocks, BPPP_BLOCK, 0, s>>>(p);
         for (int set = 0; set < 3; set++) k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, set, 0);
     });
-    GLAUNCH(s, K_APROVE_STAGE_B, k_aprove_stage_b<<<blocks, BPPP_BLOCK, 0, s>>>(p));
+    if (p.tio.states) GLAUNCH(s, K_APROVE_STAGE_B, k_aprove_stage_b_tx<<<blocks, BPPP_BLOCK, 0, s>>>(p));
+    else GLAUNCH(s, K_APROVE_STAGE_B, k_aprove_stage_b<<<blocks, BPPP_BLOCK, 0, s>>>(p));
     if (c->timing) GLAUNCH(s, K_APROVE_COLLECT, k_aprove_collect<<<blocks, BPPP_BLOCK, 0, s>>>(p));      // (same values again: its time alone)
     GLAUNCH(s, K_APROVE_TAIL, {
         k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 0);
@@ -2386,20 +2519,35 @@ static int agg_prove_part(bppp_ctx* c, const uint8_t* label, size_t label_len, s
         HIP_TRY(hipMemcpyAsync(commitments, d + o.cout, rows * 64, hipMemcpyDeviceToHost, s));
     }
     if (status) HIP_TRY(hipMemcpyAsync(status, p.status, n * 4, device_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    // every instance's transcript as the prover left it; an instance whose proof is zeroed gets its input state back
+    if (tx && device_io) {
+        if (a.tio.states_out) {
+            k_aprove_export_states<<<blocks, BPPP_BLOCK, 0, s>>>(a.tio, a.base, p.tstate, n, p.status);
+            HIP_TRY(hipGetLastError());
+        }
+    } else {
+        rc = txd.finish(tx, a.tio, a.base, p.tstate, n, p.status, s, true);
+        if (rc != BPPP_OK) return rc;
+    }
     HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
     return BPPP_OK;
 }
 static int agg_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t nd, size_t np, const uint8_t* x,
                           const uint8_t* sblind, const uint8_t* rnd, const uint8_t* seed, uint64_t stream_base, uint8_t* proofs,
-                          uint8_t* commitments, int32_t* status, bool device_io, bool sec1 = false) {
+                          uint8_t* commitments, int32_t* status, bool device_io, bool sec1 = false, const HostTranscripts* tx = nullptr) {
+    // tx (the _transcript forms): the callers' transcripts in (1 or n) and out, pointers of the kind the call's other buffers are; the
+    // host forms check the states here, the device form flags an invalid one per instance
     if (!c || !label_ok(label, label_len) || !x || !sblind || (!rnd && !seed) || !proofs || !commitments) return BPPP_ERR_INVALID_ARG;
     if (!agg_prove_shape_ok(k, nd, np, (size_t)c->ng, (size_t)c->nh)) return BPPP_ERR_INVALID_ARG;
     const size_t n_rnd = agg_prove_draws(k, nd);
     if (seed && !draw_args_ok(seed, stream_base, n, n_rnd)) return BPPP_ERR_INVALID_ARG;
+    if (tx && (!tx->states || (tx->n_states != 1 && tx->n_states != n))) return BPPP_ERR_INVALID_ARG;
+    if (tx && !device_io && n) { const int rc_t = check_host_transcripts(tx, n); if (rc_t != BPPP_OK) return rc_t; }
     if (k == 1) {
-        const RecipValues v = {device_io, commitments};
-        return recip_prove_impl(c, label, label_len, nullptr, n, nd, np, nullptr, x, sblind, nullptr, nullptr, rnd, proofs, status, sec1, seed,
-                                stream_base, &v);
+        const TranscriptIo d_tx = {tx ? tx->states : nullptr, tx ? tx->n_states : 0, tx ? tx->states_out : nullptr, 0};
+        const RecipValues v = {device_io, commitments, tx && device_io ? &d_tx : nullptr};
+        return recip_prove_impl(c, label, label_len, device_io ? nullptr : tx, n, nd, np, nullptr, x, sblind, nullptr, nullptr, rnd, proofs, status,
+                                sec1, seed, stream_base, &v);
     }
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -2419,9 +2567,17 @@ static int agg_prove_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, s
     const size_t out_pb = sec1 ? wire_pb : proof_bytes, out_cb = sec1 ? 33 : 64;
     for (size_t lo = 0; lo < n; lo += per) {
         const size_t m = n - lo < per ? n - lo : per;
+        // a part's own slice of the caller's states (or the one shared state) and of states_out
+        HostTranscripts ptx = {nullptr, 0, nullptr};
+        if (tx) {
+            const bool shared = tx->n_states == 1;
+            ptx.states = tx->states + (shared ? 0 : 203 * lo); ptx.n_states = shared ? 1 : m;
+            ptx.states_out = tx->states_out ? tx->states_out + 203 * lo : nullptr;
+        }
         const int rc = agg_prove_part(c, label, label_len, m, k, nd, np, shp, x + lo * k * 32, sblind + lo * k * 32,
                                       rnd ? rnd + lo * n_rnd * 32 : nullptr, seed, stream_base + lo, proofs + lo * out_pb,
-                                      commitments + lo * k * out_cb, status ? status + lo : nullptr, device_io, sh, proof_bytes, sec1);
+                                      commitments + lo * k * out_cb, status ? status + lo : nullptr, device_io, sh, proof_bytes, sec1,
+                                      tx ? &ptx : nullptr);
         if (rc != BPPP_OK) return rc;
     }
     if (!device_io) HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2473,6 +2629,34 @@ int bppp_reciprocal_agg_prove_values_batch_seeded_device(bppp_ctx* c, const uint
     if (!seed) return BPPP_ERR_INVALID_ARG;
     return agg_prove_impl(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_x, (const uint8_t*)d_s, nullptr, seed, stream_base,
                           (uint8_t*)d_proofs, (uint8_t*)d_commitments, (int32_t*)d_status, true);
+}
+// the same on the CALLER'S transcripts: states in (1 shared or n), every instance's transcript as the prover left it out; an instance
+// whose proof is zeroed gets its input state back
+int bppp_reciprocal_agg_prove_values_batch_transcript(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, size_t k, size_t dim_nd,
+                                                      size_t dim_np, const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd, uint8_t* proofs,
+                                                      uint8_t* commitments, int32_t* status, uint8_t* states_out) {
+    CtxLock lock_(c);
+    if (!rnd || !states) return BPPP_ERR_INVALID_ARG;
+    const HostTranscripts tx = {states, n_states, states_out};
+    return agg_prove_impl(c, nullptr, 0, n, k, dim_nd, dim_np, x, sblind, rnd, nullptr, 0, proofs, commitments, status, false, false, &tx);
+}
+int bppp_reciprocal_agg_prove_values_batch_transcript_seeded(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, size_t k,
+                                                             size_t dim_nd, size_t dim_np, const uint8_t* x, const uint8_t* sblind,
+                                                             const uint8_t seed[32], uint64_t stream_base, uint8_t* proofs,
+                                                             uint8_t* commitments, int32_t* status, uint8_t* states_out) {
+    CtxLock lock_(c);
+    if (!seed || !states) return BPPP_ERR_INVALID_ARG;
+    const HostTranscripts tx = {states, n_states, states_out};
+    return agg_prove_impl(c, nullptr, 0, n, k, dim_nd, dim_np, x, sblind, nullptr, seed, stream_base, proofs, commitments, status, false, false, &tx);
+}
+int bppp_reciprocal_agg_prove_values_batch_transcript_device(bppp_ctx* c, size_t n, const void* d_states, size_t n_states, size_t k,
+                                                             size_t dim_nd, size_t dim_np, const void* d_x, const void* d_s, const void* d_rnd,
+                                                             void* d_proofs, void* d_commitments, void* d_status, void* d_states_out) {
+    CtxLock lock_(c);
+    if (!d_rnd || !d_states) return BPPP_ERR_INVALID_ARG;
+    const HostTranscripts tx = {(const uint8_t*)d_states, n_states, (uint8_t*)d_states_out};
+    return agg_prove_impl(c, nullptr, 0, n, k, dim_nd, dim_np, (const uint8_t*)d_x, (const uint8_t*)d_s, (const uint8_t*)d_rnd, nullptr, 0,
+                          (uint8_t*)d_proofs, (uint8_t*)d_commitments, (int32_t*)d_status, true, false, &tx);
 }
 
 }  // extern "C"

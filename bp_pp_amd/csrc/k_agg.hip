@@ -15,6 +15,23 @@ __global__ __launch_bounds__(BPPP_BLOCK) void k_agg_phase1_grp(AggWs w, int G) {
     if (t >= w.N) return;                     // whole groups leave together (G divides the block)
     agg_phase1(w, t, (int)(g % (size_t)G), G);
 }
+// The same two on the CALLER'S transcripts (w.tio.states set: the _transcript entry points), kernels of their own so that the label
+// forms' code objects above stay what they were.  Per-instance states may sit at different sponge positions: the body runs once per
+// position present in the wavefront (kernels.h: for_each_position_group), one trip when the state is shared.
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_phase1_tx(AggWs w) {
+    size_t t = (size_t)blockIdx.x * BPPP_BLOCK + threadIdx.x;
+    if (t >= w.N) return;
+    const u32 key = preloaded_position_key(w.tio.states, w.tio.n_states, t);
+    for_each_position_group(key, [&]() { agg_phase1<true>(w, t); });
+}
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_phase1_grp_tx(AggWs w, int G) {
+    const size_t g = (size_t)blockIdx.x * BPPP_BLOCK + threadIdx.x;
+    const size_t t = g / (size_t)G;
+    if (t >= w.N) return;                     // whole groups leave together (G divides the block)
+    const int q = (int)(g % (size_t)G);
+    const u32 key = preloaded_position_key(w.tio.states, w.tio.n_states, t);      // (the lanes of a group share their instance's key)
+    for_each_position_group(key, [&]() { agg_phase1<true>(w, t, q, G); });
+}
 template <int NL>
 __device__ __forceinline__ void agg_c0_fixed_lanes(const AggWs& w) {
     size_t g = (size_t)blockIdx.x * BPPP_FB_BLOCK + threadIdx.x;

@@ -244,6 +244,8 @@ __global__ __launch_bounds__(BPPP_BLOCK) void k_recip_c0_finish(bppp::RecipWs w)
 // aggregated reciprocal range proof verifier (k_agg.hip, agg_core.h)
 __global__ __launch_bounds__(BPPP_BLOCK) void k_agg_phase1(bppp::AggWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_agg_phase1_grp(bppp::AggWs w, int G);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_phase1_tx(bppp::AggWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_phase1_grp_tx(bppp::AggWs w, int G);
 __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_agg_c0_fixed(bppp::AggWs w);
 __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_agg_c0_fixed_l1(bppp::AggWs w);
 __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_agg_c0_fixed_l64(bppp::AggWs w);
@@ -257,6 +259,9 @@ __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_aprove_msm
 __global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_r2(bppp::AggProveWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_b(bppp::CircuitProveWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_collect(bppp::CircuitProveWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_r1_tx(bppp::AggProveWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_b_tx(bppp::CircuitProveWs w);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_export_states(bppp::TranscriptIo io, bppp::strobe base, const bppp::u32* tstate, size_t N, const int32_t* status);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_bkt_prepare(bppp::BucketWs w);
 __global__ __launch_bounds__(256) void k_bkt_accumulate(bppp::BucketWs w);
 __global__ __launch_bounds__(256) void k_bkt_scalars(bppp::BucketWs w);

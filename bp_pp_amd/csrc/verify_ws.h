@@ -215,10 +215,12 @@ __device__ __forceinline__ void ws_st_transcript(u32* base, size_t N, size_t t, 
     base[(size_t)51 * N + t] = s.pos_begin;
 }
 #endif
-HD void tio_export(const TranscriptIo& io, const strobe& base, const u32* tstate, size_t N, const int32_t* status, size_t t) {
+// back_mask: the status bits that give an instance its input state back (the provers from integers: any bit, their proof is zeroed)
+HD void tio_export(const TranscriptIo& io, const strobe& base, const u32* tstate, size_t N, const int32_t* status, size_t t,
+                   int32_t back_mask = ST_BAD_ENCODING) {
     if (!io.states_out) return;
     uint8_t* out = io.states_out + (size_t)BPPP_TRANSCRIPT_STATE_BYTES * t;
-    if ((status[t] & ST_BAD_ENCODING) || io.no_ops) {
+    if ((status[t] & back_mask) || io.no_ops) {
         if (io.states) {
             const uint8_t* in = io.states + (size_t)BPPP_TRANSCRIPT_STATE_BYTES * (io.n_states == 1 ? 0 : t);
 #pragma nounroll

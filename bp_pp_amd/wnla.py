@@ -773,6 +773,77 @@ class AggregatedReciprocalRangeProofProtocol:
                                                                                        st.ctypes.data))
         return proofs, com, st, shape
 
+    # ---- on the caller's transcripts (include/bppp.h: "The aggregate on the CALLER'S transcripts"): states [1 or B, 203] in --
+    #      bppp_transcript_new / _append_message states -- and every instance's advanced transcript [B, 203] out
+    def _verify_transcript(self, name: str, point: int, states, commitments, proofs, rounds: int, nl: int, nn: int):
+        commitments = _u8(commitments, (-1, self.k, point))
+        B = commitments.shape[0]
+        proofs = _u8(proofs, (B, (self.proof_sec1_bytes if point == 33 else self.proof_bytes)(rounds, nl, nn)))
+        states = _u8(states, (-1, 203))
+        acc, st, out = np.zeros(B, np.uint8), np.zeros(B, np.int32), np.zeros((B, 203), np.uint8)
+        _capi.check(_capi.symbol(name)(self._w._ctx, B, states.ctypes.data, states.shape[0], self.k, self.dim_nd, self.dim_np,
+                                       commitments.ctypes.data, proofs.ctypes.data, rounds, nl, nn, acc.ctypes.data, st.ctypes.data,
+                                       out.ctypes.data))
+        return acc, st, out
+
+    def verify_batch_transcript(self, states, commitments, proofs, rounds: int, nl: int, nn: int):
+        """verify_batch on the caller's transcripts: states [1, 203] (shared) or [B, 203] -> (accept [B], status [B], states_out
+        [B, 203]).  A flagged instance (ST_BAD_ENCODING) gets its input state back; an invalid state is refused."""
+        return self._verify_transcript("bppp_reciprocal_agg_verify_batch_transcript", 64, states, commitments, proofs, rounds, nl, nn)
+
+    def verify_batch_transcript_sec1(self, states, commitments33, proofs33, rounds: int, nl: int, nn: int):
+        """verify_batch_transcript over the wire form."""
+        return self._verify_transcript("bppp_reciprocal_agg_verify_batch_transcript_sec1", 33, states, commitments33, proofs33, rounds, nl, nn)
+
+    def verify_batch_transcript_device(self, n: int, d_states: int, n_states: int, d_commitments: int, d_proofs: int, rounds: int, nl: int,
+                                       nn: int, d_accept: int, d_status: int, d_reject_count: int = 0, d_states_out: int = 0) -> None:
+        """verify_batch_transcript over device buffers (raw device pointers; 0 = none for the last two), asynchronous on the context's
+        stream.  An invalid state flags its instance ST_BAD_ENCODING and comes back unchanged."""
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_verify_batch_transcript_device")(self._w._ctx, n, d_states, n_states, self.k, self.dim_nd,
+                                                                                       self.dim_np, d_commitments, d_proofs, rounds, nl, nn,
+                                                                                       d_accept, d_status, d_reject_count or None,
+                                                                                       d_states_out or None))
+
+    def prove_values_batch_transcript(self, states, x, s, rnd):
+        """prove_values_batch on the caller's transcripts -> (proofs, commitments, status, (rounds, nl, nn), states_out [B, 203]); an
+        instance whose proof is zeroed gets its input state back."""
+        x, s = _u8(x, (-1, self.k, 32)), _u8(s, (-1, self.k, 32))
+        B = x.shape[0]
+        rnd = _u8(rnd, (B, self.prove_draws(), 32))
+        states = _u8(states, (-1, 203))
+        shape = self.proof_shape()
+        proofs, com, st = np.zeros((B, self.proof_bytes(*shape)), np.uint8), np.zeros((B, self.k, 64), np.uint8), np.zeros(B, np.int32)
+        out = np.zeros((B, 203), np.uint8)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_transcript")(self._w._ctx, B, states.ctypes.data, states.shape[0], self.k,
+                                                                                      self.dim_nd, self.dim_np, x.ctypes.data, s.ctypes.data,
+                                                                                      rnd.ctypes.data, proofs.ctypes.data, com.ctypes.data,
+                                                                                      st.ctypes.data, out.ctypes.data))
+        return proofs, com, st, shape, out
+
+    def prove_values_batch_transcript_seeded(self, states, x, s, seed: bytes, stream_base: int):
+        """prove_values_batch_transcript with instance i's draws taken from ChaCha20 stream stream_base + i of `seed` on the device."""
+        from .range_proof import _seed_args
+        x, s = _u8(x, (-1, self.k, 32)), _u8(s, (-1, self.k, 32))
+        B = x.shape[0]
+        seed, stream_base = _seed_args(seed, stream_base, B)
+        states = _u8(states, (-1, 203))
+        shape = self.proof_shape()
+        proofs, com, st = np.zeros((B, self.proof_bytes(*shape)), np.uint8), np.zeros((B, self.k, 64), np.uint8), np.zeros(B, np.int32)
+        out = np.zeros((B, 203), np.uint8)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_transcript_seeded")(self._w._ctx, B, states.ctypes.data, states.shape[0],
+                                                                                             self.k, self.dim_nd, self.dim_np, x.ctypes.data,
+                                                                                             s.ctypes.data, seed, stream_base, proofs.ctypes.data,
+                                                                                             com.ctypes.data, st.ctypes.data, out.ctypes.data))
+        return proofs, com, st, shape, out
+
+    def prove_values_batch_transcript_device(self, n: int, d_states: int, n_states: int, d_x: int, d_s: int, d_rnd: int, d_proofs: int,
+                                             d_commitments: int, d_status: int = 0, d_states_out: int = 0) -> None:
+        """prove_values_batch_transcript over device buffers (raw device addresses; 0 = none for the last two); asynchronous on the
+        context's stream."""
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_transcript_device")(self._w._ctx, n, d_states, n_states, self.k,
+                                                                                             self.dim_nd, self.dim_np, d_x, d_s, d_rnd, d_proofs,
+                                                                                             d_commitments, d_status or None, d_states_out or None))
+
     def synchronize(self) -> None:
         self._w.synchronize()
 

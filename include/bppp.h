@@ -687,8 +687,8 @@ BPPP_API int bppp_reciprocal_verify_batch_device(bppp_ctx* ctx, const uint8_t* l
  * k dim_nd <= |g_vec|, dim_nd + 10 <= |h_vec|, dim_np <= dim_nd + 1, rounds <= 12, nl, nn <= 4096.  k = 1 IS
  * bppp_reciprocal_verify_batch[_device] (and so the u64 kernels for the u64 shape).  The device form takes device buffers (d_status
  * required; d_reject_count: optional device int32, the number of rejected instances), is asynchronous on the context's stream and
- * runs a call of more than "max_batch" instances as consecutive parts.  The wire (SEC1) form and the RLC mode follow; a
- * caller-transcript form, a sharded form and a single-proof front end are not built.  The prover from integers is below
+ * runs a call of more than "max_batch" instances as consecutive parts.  The wire (SEC1) form, the RLC mode and the
+ * caller-transcript forms follow; a sharded form and a single-proof front end are not built.  The prover from integers is below
  * (bppp_reciprocal_agg_prove_values_batch*). */
 BPPP_API size_t bppp_reciprocal_agg_proof_bytes(size_t k, size_t rounds, size_t nl, size_t nn);
 BPPP_API int bppp_reciprocal_agg_verify_batch(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
@@ -716,6 +716,31 @@ BPPP_API int bppp_reciprocal_agg_verify_batch_sec1_device(bppp_ctx* ctx, const u
                                                           size_t dim_nd, size_t dim_np, const void* d_commitments33,
                                                           const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
                                                           void* d_status, void* d_reject_count);
+/* The aggregate on the CALLER'S transcripts -- `t: &mut Transcript` -- as bppp_reciprocal_verify_batch_transcript: the label forms
+ * above with (label, label_len, n) replaced by (n, states, n_states), as in every other _transcript entry point, and states_out last.
+ *   states      n_states x 203 (bppp_transcript_new / _append_message): 1 = one pre-loaded transcript shared by all instances,
+ *               n = one per instance (their lengths may differ)
+ *   states_out  n x 203 or NULL: every instance's transcript as the verifier leaves it (after the last WNLA challenge); an instance
+ *               flagged BPPP_ST_BAD_ENCODING gets its input state back
+ * Arguments and error codes as the label forms; n_states other than 1 or n, a NULL states, or (host forms) a state merlin cannot be
+ * in -- byte 200 >= 166 or byte 201 > 166 -- is BPPP_ERR_INVALID_ARG before anything touches the GPU.  The device form cannot read
+ * the states: it flags such an instance BPPP_ST_BAD_ENCODING (rejected, its state returned unchanged, no other instance touched).
+ * A call of more than "max_batch" instances runs as consecutive parts, each on its own slice of states and states_out.  k = 1 IS
+ * bppp_reciprocal_verify_batch_transcript (the device form: that verifier's device path; the _sec1 form: its wire form), which runs
+ * the whole call as ONE part whatever "max_batch" is, as that entry point does.  There is no RLC transcript form, for the aggregate
+ * as for every other protocol. */
+BPPP_API int bppp_reciprocal_agg_verify_batch_transcript(bppp_ctx* ctx, size_t n, const uint8_t* states, size_t n_states, size_t k,
+                                                         size_t dim_nd, size_t dim_np, const uint8_t* commitments, const uint8_t* proofs,
+                                                         size_t rounds, size_t nl, size_t nn, uint8_t* accept, int32_t* status,
+                                                         uint8_t* states_out);
+BPPP_API int bppp_reciprocal_agg_verify_batch_transcript_device(bppp_ctx* ctx, size_t n, const void* d_states, size_t n_states, size_t k,
+                                                                size_t dim_nd, size_t dim_np, const void* d_commitments,
+                                                                const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                                                void* d_status, void* d_reject_count, void* d_states_out);
+BPPP_API int bppp_reciprocal_agg_verify_batch_transcript_sec1(bppp_ctx* ctx, size_t n, const uint8_t* states, size_t n_states, size_t k,
+                                                              size_t dim_nd, size_t dim_np, const uint8_t* commitments33,
+                                                              const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn,
+                                                              uint8_t* accept, int32_t* status, uint8_t* states_out);
 /* The aggregate in RLC mode (as bppp_wnla_verify_batch_rlc / bppp_circuit_verify_batch_rlc): everything before the final sum is the
  * exact pipeline in the same launch form; the final sum over the 1 + |g_vec| + |h_vec| generators runs through the bucket stage
  * where the superchunk rule asks for it, then once per chunk of 8 instances on secretly weighted sums, and whatever does not pass
@@ -933,6 +958,24 @@ BPPP_API int bppp_reciprocal_agg_prove_values_batch_seeded_device(bppp_ctx* ctx,
                                                                   size_t dim_nd, size_t dim_np, const void* d_x, const void* d_s,
                                                                   const uint8_t seed[32], uint64_t stream_base, void* d_proofs,
                                                                   void* d_commitments, void* d_status);
+/* The aggregate prover on the CALLER'S transcripts: the calls above with (label, label_len, n) replaced by (n, states, n_states)
+ * and states_out (n x 203 or NULL) last, as bppp_reciprocal_agg_verify_batch_transcript.  Every instance's transcript comes back as
+ * the prover leaves it -- the state the verifier reaches on the same proof; an instance whose proof is zeroed (any status) gets its
+ * input state back.  The host forms refuse an invalid state with BPPP_ERR_INVALID_ARG; the device form flags its instance
+ * BPPP_ST_BAD_ENCODING.  Parts take their own slices of states and states_out.  No SEC1 form of these is built. */
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_transcript(bppp_ctx* ctx, size_t n, const uint8_t* states, size_t n_states, size_t k,
+                                                               size_t dim_nd, size_t dim_np, const uint8_t* x, const uint8_t* s,
+                                                               const uint8_t* rnd, uint8_t* proofs, uint8_t* commitments,
+                                                               int32_t* status /* n or NULL */, uint8_t* states_out);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_transcript_seeded(bppp_ctx* ctx, size_t n, const uint8_t* states, size_t n_states,
+                                                                      size_t k, size_t dim_nd, size_t dim_np, const uint8_t* x,
+                                                                      const uint8_t* s, const uint8_t seed[32], uint64_t stream_base,
+                                                                      uint8_t* proofs, uint8_t* commitments,
+                                                                      int32_t* status /* n or NULL */, uint8_t* states_out);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_transcript_device(bppp_ctx* ctx, size_t n, const void* d_states, size_t n_states,
+                                                                      size_t k, size_t dim_nd, size_t dim_np, const void* d_x,
+                                                                      const void* d_s, const void* d_rnd, void* d_proofs,
+                                                                      void* d_commitments, void* d_status, void* d_states_out);
 /* the same with the outputs in the wire form: proofs33 n x bppp_reciprocal_agg_proof_sec1_bytes(k, rounds, nl, nn), commitments33
  * n x k x 33 -- byte for byte the calls above with every point compressed (on the device, per part, before the copy back).  A
  * flagged instance gets a zeroed proof and k x 33 zero bytes (the identity's encoding).  Host buffers only: device-buffer SEC1
