@@ -81,6 +81,10 @@ AGG_TRANSCRIPT_PROVE_EXPORTS = ["bppp_reciprocal_agg_prove_values_batch_transcri
                                 "bppp_reciprocal_agg_prove_values_batch_transcript_device"]
 AGG_TRANSCRIPT_EXPORTS = AGG_TRANSCRIPT_VERIFY_EXPORTS + AGG_TRANSCRIPT_PROVE_EXPORTS
 EXPORTS += AGG_TRANSCRIPT_EXPORTS
+# aggregates of mixed value counts in one batch (include/bppp.h: "Aggregates of MIXED value counts"); bound only when the library has them
+AGG_MIXED_EXPORTS = ["bppp_reciprocal_agg_mixed_check_args", "bppp_reciprocal_agg_verify_batch_mixed",
+                     "bppp_reciprocal_agg_verify_batch_mixed_device"]
+EXPORTS += AGG_MIXED_EXPORTS
 
 _lib = None
 
@@ -326,6 +330,13 @@ def lib():
         L.bppp_reciprocal_agg_prove_values_batch_transcript_seeded.argtypes = [vp, sz, vp, sz, sz, sz, sz, vp, vp, u8p, u64, vp, vp, vp, vp]
         L.bppp_reciprocal_agg_prove_values_batch_transcript_device.argtypes = [vp, sz, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp]
         for name in AGG_TRANSCRIPT_EXPORTS:
+            getattr(L, name).restype = i32
+    # the mixed aggregate: the uniform lists with (k) -> (k_max, ks); the check is the same decision without a context
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_reciprocal_agg_verify_batch_mixed"):
+        L.bppp_reciprocal_agg_mixed_check_args.argtypes = [sz, sz, sz, sz, vp, i32, sz, sz, sz, sz, sz]
+        L.bppp_reciprocal_agg_verify_batch_mixed.argtypes = [vp, u8p, sz, sz, sz, vp, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        L.bppp_reciprocal_agg_verify_batch_mixed_device.argtypes = [vp, u8p, sz, sz, sz, vp, sz, sz, vp, vp, sz, sz, sz, vp, vp, vp]
+        for name in AGG_MIXED_EXPORTS:
             getattr(L, name).restype = i32
     L.bppp_strerror.argtypes = [i32]
     L.bppp_strerror.restype = C.c_char_p

@@ -733,11 +733,14 @@ static AggVerifyLayout agg_verify_layout(const bppp_ctx* c, size_t n, size_t k, 
 }
 static size_t agg_proof_bytes(size_t k, size_t rounds, size_t nl, size_t nn) { return 64 * (4 + 2 * rounds + k) + 32 * (nl + nn); }
 // 1 <= k <= 64, k dim_nd generators of g_vec and dim_nd + 10 of h_vec in the context, dim_np <= dim_nd + 1, the WNLA stage's bounds
-static int agg_verify_check_args(const bppp_ctx* c, size_t k, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn) {
-    if (k == 0 || k > 64 || dim_nd == 0 || dim_np == 0 || dim_nd > (size_t)c->ng || k * dim_nd > (size_t)c->ng || dim_nd + 10 > (size_t)c->nh ||
+static int agg_shape_check(size_t ng, size_t nh, size_t k, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn) {
+    if (k == 0 || k > 64 || dim_nd == 0 || dim_np == 0 || dim_nd > ng || k * dim_nd > ng || dim_nd + 10 > nh ||
         dim_np > dim_nd + 1 || rounds > 12 || nl > 4096 || nn > 4096)
         return BPPP_ERR_INVALID_ARG;
     return BPPP_OK;
+}
+static int agg_verify_check_args(const bppp_ctx* c, size_t k, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn) {
+    return agg_shape_check((size_t)c->ng, (size_t)c->nh, k, dim_nd, dim_np, rounds, nl, nn);
 }
 // the launch sequence of one call (or of one max_batch part of it), every buffer in device memory; d_ws holds agg_verify_layout().total
 // rlc_seed: the final sum in RLC mode -- by the WNLA and circuit verifiers' rule (wnla_rlc_applies), so a part of fewer than 8
@@ -988,6 +991,150 @@ int bppp_reciprocal_agg_verify_batch_transcript_device(bppp_ctx* c, size_t n, co
     const TranscriptIo dtio = {(const uint8_t*)d_states, n_states, (uint8_t*)d_states_out, 0};
     return agg_verify_device_run(c, nullptr, 0, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status, d_reject_count,
                                  nullptr, &dtio);
+}
+// ---- aggregates of MIXED value counts in one batch (agg_mixed_core.h): instance i has ks[i] values in slots laid out by k_max.  Exact
+//      mode, 64-byte points, label transcripts.  The launch sequence is agg_verify_device_impl's on the same plan, with phase 1 and the
+//      variable-base half of C0 on every instance's own k (k_agg_mixed.hip) and the WNLA stage reading l | n out of phase 1's copy;
+//      k_i = 1 runs on these kernels too.  The workspace is the uniform one for k_max with the l | n copies behind it.
+static size_t agg_mixed_ws_bytes(const bppp_ctx* c, size_t n, size_t k_max, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn) {
+    return agg_verify_layout(c, n, k_max, dim_nd, dim_np, rounds).total + align16(n * 32 * (nl + nn));
+}
+static int agg_mixed_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, const uint8_t* d_ks, size_t dim_nd,
+                                 size_t dim_np, const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn,
+                                 uint8_t* d_acc, int32_t* d_st, uint8_t* d_ws) {
+    const GenericPlan plan = plan_generic(GENERIC_FORM_AGGREGATE, n, rounds, generic_knobs_of(c), n, 1, 4 + k);
+    const AggVerifyLayout o = agg_verify_layout(c, n, k, dim_nd, dim_np, rounds);
+    uint8_t* d = d_ws;
+    hipStream_t s = c->stream;
+    AggMixedWs m;
+    std::memset(&m, 0, sizeof m);
+    AggWs& r = m.w;
+    r.N = n; r.k = (int)k; r.nd = (int)dim_nd; r.np = (int)dim_np; r.rounds = (int)rounds; r.nl = (int)nl; r.nn = (int)nn;
+    r.NG = c->ng; r.NH = c->nh; r.proof_bytes = agg_proof_bytes(k, rounds, nl, nn);
+    r.commitments = d_com; r.proofs = d_proofs; r.status = d_st; r.tstate = (u32*)(d + o.ts);
+    r.sc0 = (u32*)(d + o.sc0); r.pts = (u32*)(d + o.pts); r.acc = (u32*)(d + o.a); r.pfix = (u32*)(d + o.pf); r.inv = (u32*)(d + o.inv);
+    r.vsum = (u32*)(d + o.vs);
+    r.straus = c->d_straus;
+    r.wn_commit = d + o.wc; r.wn_c = d + o.wcv; r.wn_rho = d + o.rho; r.wn_mu = d + o.mu;
+    r.fb = fb_table_of(c, n);
+    t_new(r.base, label, (u32)label_len);
+    m.ks = d_ks; m.ln = d + o.total;
+    WnlaWs w = wnla_ws_continuing(c, r, 4 + k, nl, nn, d_acc, (u32*)(d + o.ys), (u32*)(d + o.tab), (u32*)(d + o.msc));
+    w.proof_l = m.ln; w.proof_n = m.ln + 32 * nl;       // (r and x sit at one offset for every k_i and are read in place)
+    w.stride_l = w.stride_n = 32 * (nl + nn);
+    const unsigned blocks = blocks_of(n);
+    int rc;
+    rc = wnla_fast_setup(c, w, plan, 4 + k);
+    if (rc != BPPP_OK) return rc;
+    r.atab = w.atab; r.tscr = w.tscr; r.atab_first = wnla_atab_first(plan, rounds);
+    const bool beside = plan.beside;
+    hipStream_t a = beside ? c->aux_stream : s;
+    const int G = plan.p1_group;
+    c->last_generic_form = plan.code();
+    if (beside) {
+        HIP_TRY(hipEventRecord(c->ev_tab, s));               // (the call's inputs are ready on s)
+        HIP_TRY(hipStreamWaitEvent(a, c->ev_tab, 0));
+        GLAUNCH(a, K_WNLA_TABLES, launch_wnla_tables(w, plan.tab_parts, n, blocks, a));
+    }
+    const unsigned p1_blocks = G > 1 ? (unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK) : blocks;
+    if (G > 1) GLAUNCH(s, K_AGG_PHASE1, k_agg_mixed_phase1_grp<<<p1_blocks, BPPP_BLOCK, 0, s>>>(m, G));
+    else GLAUNCH(s, K_AGG_PHASE1, k_agg_mixed_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(m));
+    if (beside) {
+        HIP_TRY(hipEventRecord(c->ev_fork, s));
+        HIP_TRY(hipStreamWaitEvent(a, c->ev_fork, 0));
+    }
+    // the uniform kernels over 1 + k_max dim_nd bases: the scalars behind an instance's k_i dim_nd are zero
+    if (plan.fb == GENERIC_FB_ONE_LANE) GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed_l1<<<fb1_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    else if (plan.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    else GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
+    GLAUNCH(a, K_AGG_C0_VAR, {
+        if (plan.fast) k_agg_mixed_c0_tables<<<blocks, BPPP_BLOCK, 0, a>>>(m);
+        k_agg_mixed_c0_var<<<blocks, BPPP_BLOCK, 0, a>>>(m);
+    });
+    if (beside) {
+        HIP_TRY(hipEventRecord(c->ev_join, a));
+        HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
+    }
+    GLAUNCH(s, K_AGG_C0_FINISH, k_agg_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
+    return wnla_verify_stage(c, w, plan, s, beside, nullptr, d, o.rlc);
+}
+// parts of max_batch over one workspace, each with its own slice of ks
+static int agg_mixed_parts(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, const uint8_t* d_ks, size_t dim_nd,
+                           size_t dim_np, const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
+                           int32_t* d_st, uint8_t* d_ws) {
+    const size_t per = agg_part_size(c, n), pb = agg_proof_bytes(k, rounds, nl, nn);
+    for (size_t lo = 0; lo < n; lo += per) {
+        const size_t m = n - lo < per ? n - lo : per;
+        const int rc = agg_mixed_device_impl(c, label, label_len, m, k, d_ks + lo, dim_nd, dim_np, d_com + 64 * k * lo, d_proofs + pb * lo, rounds,
+                                             nl, nn, d_acc + lo, d_st + lo, d_ws);
+        if (rc != BPPP_OK) return rc;
+    }
+    return BPPP_OK;
+}
+// what the two mixed calls decide about their arguments besides the NULL checks of the buffers, on a context of ng | nh generators in
+// g_vec || g_vec_ | h_vec || h_vec_; pure, so that it can be asked without a context or a device.  ks_on_device: ks is only checked
+// for NULL (the device form: an instance outside [1, k_max] is flagged where it is read)
+int bppp_reciprocal_agg_mixed_check_args(size_t ng, size_t nh, size_t n, size_t k_max, const uint8_t* ks, int ks_on_device, size_t dim_nd,
+                                         size_t dim_np, size_t rounds, size_t nl, size_t nn) {
+    if (!ks) return BPPP_ERR_INVALID_ARG;
+    const int rc = agg_shape_check(ng, nh, k_max, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK || ks_on_device) return rc;
+    for (size_t i = 0; i < n; i++)
+        if (ks[i] == 0 || ks[i] > k_max) return BPPP_ERR_INVALID_ARG;
+    return BPPP_OK;
+}
+int bppp_reciprocal_agg_verify_batch_mixed_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks,
+                                                  size_t dim_nd, size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds,
+                                                  size_t nl, size_t nn, void* d_accept, void* d_status, void* d_reject_count) {
+    CtxLock lock_(c);
+    if (!c || !label_ok(label, label_len) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
+    int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, (const uint8_t*)d_ks, 1, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
+    if (n == 0) return BPPP_OK;
+    const size_t per = agg_part_size(c, n);
+    rc = agg_verify_prepare(c, per, nullptr);
+    if (rc != BPPP_OK) return rc;
+    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_mixed_ws_bytes(c, per, k_max, dim_nd, dim_np, rounds, nl, nn));
+    if (rc != BPPP_OK) return rc;
+    rc = agg_mixed_parts(c, label, label_len, n, k_max, (const uint8_t*)d_ks, dim_nd, dim_np, (const uint8_t*)d_commitments,
+                         (const uint8_t*)d_proofs, rounds, nl, nn, (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws);
+    if (rc != BPPP_OK || !d_reject_count) return rc;
+    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
+    HIP_TRY(hipGetLastError());
+    return BPPP_OK;
+}
+int bppp_reciprocal_agg_verify_batch_mixed(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
+                                           size_t dim_nd, size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds,
+                                           size_t nl, size_t nn, uint8_t* accept, int32_t* status) {
+    CtxLock lock_(c);
+    if (!c || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
+    int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, ks, 0, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t per = agg_part_size(c, n);
+    rc = agg_verify_prepare(c, per, nullptr);
+    if (rc != BPPP_OK) return rc;
+    const size_t pb = agg_proof_bytes(k_max, rounds, nl, nn);
+    const size_t o_com = 0, o_pr = align16(n * k_max * 64), o_ks = align16(o_pr + n * pb), o_acc = align16(o_ks + n), o_st = align16(o_acc + n),
+                 o_ws = align16(o_st + n * 4), total = o_ws + agg_mixed_ws_bytes(c, per, k_max, dim_nd, dim_np, rounds, nl, nn);
+    WnlaBlob blob;
+    { const int rc_b = blob.take(c, total); if (rc_b != BPPP_OK) return rc_b; }
+    uint8_t* d = blob.d;
+    hipStream_t s = c->stream;
+    // (the whole slots go up; the kernels read an instance's first k_i commitments and proof_bytes(k_i) bytes only)
+    HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * k_max * 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_pr, proofs, n * pb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_ks, ks, n, hipMemcpyHostToDevice, s));
+    rc = agg_mixed_parts(c, label, label_len, n, k_max, d + o_ks, dim_nd, dim_np, d + o_com, d + o_pr, rounds, nl, nn, d + o_acc,
+                         (int32_t*)(d + o_st), d + o_ws);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPPP_OK;
 }
 
 // ---------------------------------------------------------------- generic ArithmeticCircuit (circuit.rs:95-256)

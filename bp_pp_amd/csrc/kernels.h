@@ -8,6 +8,7 @@
 #include "prove_core.h"
 #include "recip_core.h"
 #include "agg_core.h"
+#include "agg_mixed_core.h"
 #include "recip_prove_core.h"
 #include "agg_prove_core.h"
 #include "bucket_core.h"
@@ -252,6 +253,11 @@ __global__ __launch_bounds__(BPPP_FB_BLOCK, BPPP_FB_MIN_WAVES) void k_agg_c0_fix
 __global__ __launch_bounds__(BPPP_BLOCK, BPPP_TABLES_MIN_WAVES) void k_agg_c0_tables(bppp::AggWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_agg_c0_var(bppp::AggWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_agg_c0_finish(bppp::AggWs w);
+// the same for mixed value counts (k_agg_mixed.hip, agg_mixed_core.h): what depends on an instance's own k; the rest are the kernels above
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_mixed_phase1(bppp::AggMixedWs m);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_mixed_phase1_grp(bppp::AggMixedWs m, int G);
+__global__ __launch_bounds__(BPPP_BLOCK, BPPP_TABLES_MIN_WAVES) void k_agg_mixed_c0_tables(bppp::AggMixedWs m);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_agg_mixed_c0_var(bppp::AggMixedWs m);
 // aggregated reciprocal range proof prover (k_aggprove.hip, agg_prove_core.h)
 __global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_witness(bppp::AggProveWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_r1(bppp::AggProveWs w);

@@ -694,6 +694,31 @@ class AggregatedReciprocalRangeProofProtocol:
                                                                             self.dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept,
                                                                             d_status, d_reject_count or None))
 
+    def verify_batch_mixed(self, label: bytes, ks, commitments, proofs, rounds: int, nl: int, nn: int):
+        """Instances of different value counts in one call; the constructor's k is k_max.  ks [B] (1 <= ks[i] <= k), commitments
+        [B, k, 64] of which row i's first ks[i] are read, proofs [B, proof_bytes(k)] of which row i's first proof_bytes(ks[i]) are read
+        (the uniform layout for ks[i]) -> (accept [B], status [B]).  Every instance is verified as verify_batch with k = ks[i] on this
+        context verifies it."""
+        ks = _u8(ks, (-1,))
+        B = ks.shape[0]
+        commitments = _u8(commitments, (B, self.k, 64))
+        proofs = _u8(proofs, (B, self.proof_bytes(rounds, nl, nn)))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_verify_batch_mixed")(self._w._ctx, label, len(label), B, self.k, ks.ctypes.data,
+                                                                           self.dim_nd, self.dim_np, commitments.ctypes.data,
+                                                                           proofs.ctypes.data, rounds, nl, nn, acc.ctypes.data,
+                                                                           st.ctypes.data))
+        return acc, st
+
+    def verify_batch_mixed_device(self, label: bytes, n: int, d_ks: int, d_commitments: int, d_proofs: int, rounds: int, nl: int, nn: int,
+                                  d_accept: int, d_status: int, d_reject_count: int = 0) -> None:
+        """verify_batch_mixed over device buffers (raw device pointers; d_ks: n bytes), asynchronous on the context's stream.  A
+        d_ks[i] outside [1, k] flags instance i ST_BAD_ENCODING."""
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_verify_batch_mixed_device")(self._w._ctx, label, len(label), n, self.k, d_ks,
+                                                                                  self.dim_nd, self.dim_np, d_commitments, d_proofs,
+                                                                                  rounds, nl, nn, d_accept, d_status,
+                                                                                  d_reject_count or None))
+
     def proof_sec1_bytes(self, rounds: int, nl: int, nn: int) -> int:
         """Bytes of a proof in the wire form: 33 (4 + 2 rounds + k) + 32 (nl + nn)."""
         return int(_capi.symbol("bppp_reciprocal_agg_proof_sec1_bytes")(self.k, rounds, nl, nn))

@@ -287,6 +287,26 @@ impl U64RangeProofProtocolGpu {
         Ok((proofs.chunks(928).map(|b| b.to_vec()).collect(),
             coms.chunks(64).map(|b| get_point(b).expect("library emitted a point off the curve")).collect()))
     }
+
+    /// Aggregated reciprocal range proofs of MIXED value counts over this object's generators in one call
+    /// (bppp_reciprocal_agg_verify_batch_mixed, include/bppp.h): instance i proves `ks[i]` values of dim_nd base-dim_np digits under
+    /// one proof, 1 <= ks[i] <= k_max, k_max dim_nd <= 16 on these generators.  Slots are laid out by k_max: `commitments` is
+    /// n x k_max x 64 bytes of which instance i's first ks[i] are read, `proofs` n x (64 (4 + 2 rounds + k_max) + 32 (nl + nn)) of
+    /// which its first 64 (4 + 2 rounds + ks[i]) + 32 (nl + nn) are read, in the layout for ks[i] values; (rounds, nl, nn) are the
+    /// context's (4, 2, 1 here).  Every instance starts from `Transcript::new(label)`.
+    pub fn verify_agg_mixed(&self, label: &'static [u8], k_max: usize, ks: &[u8], dim_nd: usize, dim_np: usize, commitments: &[u8], proofs: &[u8], rounds: usize, nl: usize, nn: usize) -> Result<Vec<bool>, GpuError> {
+        let n = ks.len();
+        let stride = unsafe { bppp_reciprocal_agg_proof_bytes(k_max, rounds, nl, nn) };
+        assert!(commitments.len() == n * k_max * 64 && proofs.len() == n * stride);
+        let (mut acc, mut st) = (vec![0u8; n], vec![0i32; n]);
+        check(unsafe {
+            bppp_reciprocal_agg_verify_batch_mixed(self.ctx, label.as_ptr(), label.len(), n, k_max, ks.as_ptr(), dim_nd, dim_np, commitments.as_ptr(), proofs.as_ptr(), rounds, nl, nn, acc.as_mut_ptr(), st.as_mut_ptr())
+        })?;
+        if let Some(i) = st.iter().position(|s| s & BPPP_ST_DEGENERATE != 0) {
+            return Err(GpuError::ReferenceWouldPanic { index: i });
+        }
+        Ok(acc.iter().map(|a| *a == 1).collect())
+    }
 }
 
 impl Drop for U64RangeProofProtocolGpu {

@@ -698,6 +698,38 @@ BPPP_API int bppp_reciprocal_agg_verify_batch_device(bppp_ctx* ctx, const uint8_
                                                      size_t dim_nd, size_t dim_np, const void* d_commitments, const void* d_proofs,
                                                      size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status,
                                                      void* d_reject_count);
+/* Aggregates of MIXED value counts in ONE batch: the calls above take one k for the whole call; these take one per instance, so that
+ * a caller holding transactions with different numbers of outputs does not split them into classes (bp_pp_amd/csrc/agg_mixed_core.h).
+ *   k_max        the largest value count of the call; every slot is laid out by it
+ *   ks           n bytes: instance i has k_i = ks[i] values, 1 <= k_i <= k_max
+ *   commitments  n x k_max x 64: instance i's are the first k_i of its k_max slots
+ *   proofs       n x bppp_reciprocal_agg_proof_bytes(k_max, rounds, nl, nn): instance i's proof is the first
+ *                bppp_reciprocal_agg_proof_bytes(k_i, rounds, nl, nn) bytes of its slot, in the layout above for k = k_i:
+ *                c_l c_r c_o c_s | r | x | R_0 .. R_{k_i-1} | l | n.  The rest of both slots is never read.
+ * Every instance is verified on the context's generators as the call above with k = k_i on that same context verifies it: g_vec ||
+ * g_vec_ is one vector, of which the first k_i dim_nd entries carry pn_tau; rounds, nl and nn are the context's for every k_i.
+ * BPPP_ERR_INVALID_ARG, before anything touches the GPU: the conditions above with k = k_max; a NULL ks; in the host form a ks[i]
+ * outside [1, k_max].  The device form cannot read d_ks: there such an instance is flagged BPPP_ST_BAD_ENCODING and rejected, runs on
+ * harmless values as a malformed point does and touches no other instance.  bppp_reciprocal_agg_mixed_check_args is that decision as
+ * a pure function of the context's sizes (ng = |g_vec || g_vec_|, nh = |h_vec || h_vec_|; ks_on_device: ks only checked for NULL).
+ * k_i = 1 instances run on the aggregate's kernels -- nothing is forwarded inside a mixed call; a call whose ks are all equal gives
+ * the uniform call's accept bits, statuses and reject count (k_max = 1: the reciprocal verifier's).  "max_batch" parts (each on its
+ * own slice of ks), the asynchrony of the device form, d_reject_count, "last_generic_form" (the plan of the aggregate for the call's
+ * size and k_max) and the behaviour after an allocation failure are the uniform call's.  Cost: an instance pays phase 1 and the
+ * variable-base half of C0 for its own k_i -- a wavefront for the largest of its 64 -- and the fixed-base half for k_max (docs/design
+ * 07 section 7d has the measurements).
+ * Exact mode, 64-byte points and label transcripts only.  NOT built: the SEC1 form, the RLC form and the caller-transcript form of
+ * the mixed call, a mixed prover, reordering instances by k on the device; and, as above, the single-proof front end and sharded groups. */
+BPPP_API int bppp_reciprocal_agg_mixed_check_args(size_t ng, size_t nh, size_t n, size_t k_max, const uint8_t* ks, int ks_on_device,
+                                                  size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn);
+BPPP_API int bppp_reciprocal_agg_verify_batch_mixed(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                    const uint8_t* ks, size_t dim_nd, size_t dim_np, const uint8_t* commitments,
+                                                    const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                                    int32_t* status);
+BPPP_API int bppp_reciprocal_agg_verify_batch_mixed_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                           const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments,
+                                                           const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                                           void* d_status, void* d_reject_count);
 /* The aggregate in the WIRE form (as bppp_reciprocal_verify_batch_sec1 below): the layout above with every point 33-byte
  * SEC1-compressed in place (02 | 03 by the parity of y, then x; the identity is 33 zero bytes) and the scalars unchanged.
  *   commitments33  n x k x 33, value-major
