@@ -85,6 +85,11 @@ EXPORTS += AGG_TRANSCRIPT_EXPORTS
 AGG_MIXED_EXPORTS = ["bppp_reciprocal_agg_mixed_check_args", "bppp_reciprocal_agg_verify_batch_mixed",
                      "bppp_reciprocal_agg_verify_batch_mixed_device"]
 EXPORTS += AGG_MIXED_EXPORTS
+# the mixed call in RLC mode and in the wire form (include/bppp.h: "The mixed call in RLC mode and in the WIRE form")
+AGG_MIXED_WIRE_RLC_EXPORTS = ["bppp_reciprocal_agg_verify_batch_mixed_rlc", "bppp_reciprocal_agg_verify_batch_mixed_rlc_device",
+                              "bppp_reciprocal_agg_verify_batch_mixed_sec1", "bppp_reciprocal_agg_verify_batch_mixed_sec1_device",
+                              "bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1", "bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1_device"]
+EXPORTS += AGG_MIXED_WIRE_RLC_EXPORTS
 
 _lib = None
 
@@ -337,6 +342,15 @@ def lib():
         L.bppp_reciprocal_agg_verify_batch_mixed.argtypes = [vp, u8p, sz, sz, sz, vp, sz, sz, vp, vp, sz, sz, sz, vp, vp]
         L.bppp_reciprocal_agg_verify_batch_mixed_device.argtypes = [vp, u8p, sz, sz, sz, vp, sz, sz, vp, vp, sz, sz, sz, vp, vp, vp]
         for name in AGG_MIXED_EXPORTS:
+            getattr(L, name).restype = i32
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_reciprocal_agg_verify_batch_mixed_sec1"):
+        host = [vp, u8p, sz, sz, sz, vp, sz, sz, vp, vp, sz, sz, sz, vp, vp]
+        L.bppp_reciprocal_agg_verify_batch_mixed_sec1.argtypes = host
+        L.bppp_reciprocal_agg_verify_batch_mixed_sec1_device.argtypes = host + [vp]
+        L.bppp_reciprocal_agg_verify_batch_mixed_rlc.argtypes = L.bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1.argtypes = host + [u8p]
+        L.bppp_reciprocal_agg_verify_batch_mixed_rlc_device.argtypes = host + [vp, u8p]
+        L.bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1_device.argtypes = host + [vp, u8p]
+        for name in AGG_MIXED_WIRE_RLC_EXPORTS:
             getattr(L, name).restype = i32
     L.bppp_strerror.argtypes = [i32]
     L.bppp_strerror.restype = C.c_char_p

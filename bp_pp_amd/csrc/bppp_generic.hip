@@ -992,18 +992,23 @@ int bppp_reciprocal_agg_verify_batch_transcript_device(bppp_ctx* c, size_t n, co
     return agg_verify_device_run(c, nullptr, 0, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status, d_reject_count,
                                  nullptr, &dtio);
 }
-// ---- aggregates of MIXED value counts in one batch (agg_mixed_core.h): instance i has ks[i] values in slots laid out by k_max.  Exact
-//      mode, 64-byte points, label transcripts.  The launch sequence is agg_verify_device_impl's on the same plan, with phase 1 and the
-//      variable-base half of C0 on every instance's own k (k_agg_mixed.hip) and the WNLA stage reading l | n out of phase 1's copy;
-//      k_i = 1 runs on these kernels too.  The workspace is the uniform one for k_max with the l | n copies behind it.
-static size_t agg_mixed_ws_bytes(const bppp_ctx* c, size_t n, size_t k_max, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn) {
-    return agg_verify_layout(c, n, k_max, dim_nd, dim_np, rounds).total + align16(n * 32 * (nl + nn));
+// ---- aggregates of MIXED value counts in one batch (agg_mixed_core.h): instance i has ks[i] values in slots laid out by k_max.  Label
+//      transcripts; the final sum exact or in RLC mode (a seed given).  The launch sequence is agg_verify_device_impl's on the same
+//      plan, with phase 1 and the variable-base half of C0 on every instance's own k (k_agg_mixed.hip) and the WNLA stage reading l | n
+//      out of phase 1's copy; k_i = 1 runs on these kernels too.  The workspace is the uniform one for k_max (its RLC buffers included)
+//      with the l | n copies behind it.  The wire (SEC1) forms are with the other verifiers' at the end of this file.
+static size_t agg_mixed_ws_bytes(const bppp_ctx* c, size_t n, size_t k_max, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn,
+                                 bool rlc) {
+    return agg_verify_layout(c, n, k_max, dim_nd, dim_np, rounds, rlc).total + align16(n * 32 * (nl + nn));
 }
+// rlc_seed: as agg_verify_device_impl's.  The RLC kernels read the final scalars, the commitments after the last round and the
+// statuses out of the workspace, never the proof; l | n are read by the stages before them through w.proof_l / proof_n (the copies)
 static int agg_mixed_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, const uint8_t* d_ks, size_t dim_nd,
                                  size_t dim_np, const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn,
-                                 uint8_t* d_acc, int32_t* d_st, uint8_t* d_ws) {
+                                 uint8_t* d_acc, int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed) {
     const GenericPlan plan = plan_generic(GENERIC_FORM_AGGREGATE, n, rounds, generic_knobs_of(c), n, 1, 4 + k);
-    const AggVerifyLayout o = agg_verify_layout(c, n, k, dim_nd, dim_np, rounds);
+    const bool rlc = rlc_seed && wnla_rlc_applies(n);
+    const AggVerifyLayout o = agg_verify_layout(c, n, k, dim_nd, dim_np, rounds, rlc);
     uint8_t* d = d_ws;
     hipStream_t s = c->stream;
     AggMixedWs m;
@@ -1056,19 +1061,22 @@ static int agg_mixed_device_impl(bppp_ctx* c, const uint8_t* label, size_t label
         HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
     }
     GLAUNCH(s, K_AGG_C0_FINISH, k_agg_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    return wnla_verify_stage(c, w, plan, s, beside, nullptr, d, o.rlc);
+    return wnla_verify_stage(c, w, plan, s, beside, rlc ? rlc_seed : nullptr, d, o.rlc);
 }
-// parts of max_batch over one workspace, each with its own slice of ks
+// parts of max_batch over one workspace, each with its own slice of ks; "last_rlc_*" as agg_verify_parts reports them
 static int agg_mixed_parts(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, const uint8_t* d_ks, size_t dim_nd,
                            size_t dim_np, const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
-                           int32_t* d_st, uint8_t* d_ws) {
+                           int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed) {
     const size_t per = agg_part_size(c, n), pb = agg_proof_bytes(k, rounds, nl, nn);
+    unsigned first_super_m = 0, first_chunk = 0;
     for (size_t lo = 0; lo < n; lo += per) {
         const size_t m = n - lo < per ? n - lo : per;
         const int rc = agg_mixed_device_impl(c, label, label_len, m, k, d_ks + lo, dim_nd, dim_np, d_com + 64 * k * lo, d_proofs + pb * lo, rounds,
-                                             nl, nn, d_acc + lo, d_st + lo, d_ws);
+                                             nl, nn, d_acc + lo, d_st + lo, d_ws, rlc_seed);
         if (rc != BPPP_OK) return rc;
+        if (lo == 0) { first_super_m = c->last_rlc_super_m; first_chunk = c->last_rlc_chunk; }
     }
+    if (rlc_seed) { c->last_rlc_super_m = first_super_m; c->last_rlc_chunk = first_chunk; }
     return BPPP_OK;
 }
 // what the two mixed calls decide about their arguments besides the NULL checks of the buffers, on a context of ng | nh generators in
@@ -1083,43 +1091,65 @@ int bppp_reciprocal_agg_mixed_check_args(size_t ng, size_t nh, size_t n, size_t 
         if (ks[i] == 0 || ks[i] > k_max) return BPPP_ERR_INVALID_ARG;
     return BPPP_OK;
 }
-int bppp_reciprocal_agg_verify_batch_mixed_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks,
-                                                  size_t dim_nd, size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds,
-                                                  size_t nl, size_t nn, void* d_accept, void* d_status, void* d_reject_count) {
-    CtxLock lock_(c);
-    if (!c || !label_ok(label, label_len) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
-    int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, (const uint8_t*)d_ks, 1, dim_nd, dim_np, rounds, nl, nn);
-    if (rc != BPPP_OK) return rc;
+// a call over device buffers, arguments checked: asynchronous on the context's stream, the workspace in the grow-only d_gws
+static int agg_mixed_device_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks, size_t dim_nd,
+                                size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn,
+                                void* d_accept, void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
     HIP_TRY(hipSetDevice(c->device));
     if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
     if (n == 0) return BPPP_OK;
     const size_t per = agg_part_size(c, n);
-    rc = agg_verify_prepare(c, per, nullptr);
+    int rc = agg_verify_prepare(c, per, rlc_seed);
     if (rc != BPPP_OK) return rc;
-    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_mixed_ws_bytes(c, per, k_max, dim_nd, dim_np, rounds, nl, nn));
+    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_mixed_ws_bytes(c, per, k_max, dim_nd, dim_np, rounds, nl, nn, rlc_seed != nullptr));
     if (rc != BPPP_OK) return rc;
     rc = agg_mixed_parts(c, label, label_len, n, k_max, (const uint8_t*)d_ks, dim_nd, dim_np, (const uint8_t*)d_commitments,
-                         (const uint8_t*)d_proofs, rounds, nl, nn, (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws);
+                         (const uint8_t*)d_proofs, rounds, nl, nn, (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws, rlc_seed);
     if (rc != BPPP_OK || !d_reject_count) return rc;
     k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
     HIP_TRY(hipGetLastError());
     return BPPP_OK;
 }
-int bppp_reciprocal_agg_verify_batch_mixed(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
-                                           size_t dim_nd, size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds,
-                                           size_t nl, size_t nn, uint8_t* accept, int32_t* status) {
+static int agg_mixed_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks, size_t dim_nd,
+                                  size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn,
+                                  void* d_accept, void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
+    if (!c || !label_ok(label, label_len) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
+    const int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, (const uint8_t*)d_ks, 1, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    return agg_mixed_device_run(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
+                                d_reject_count, rlc_seed);
+}
+int bppp_reciprocal_agg_verify_batch_mixed_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks,
+                                                  size_t dim_nd, size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds,
+                                                  size_t nl, size_t nn, void* d_accept, void* d_status, void* d_reject_count) {
     CtxLock lock_(c);
+    return agg_mixed_device_entry(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
+                                  d_reject_count, nullptr);
+}
+int bppp_reciprocal_agg_verify_batch_mixed_rlc_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                      const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments,
+                                                      const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status,
+                                                      void* d_reject_count, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_mixed_device_entry(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
+                                  d_reject_count, seed);
+}
+static int agg_mixed_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks, size_t dim_nd,
+                               size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn,
+                               uint8_t* accept, int32_t* status, const uint8_t* rlc_seed) {
     if (!c || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
     int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, ks, 0, dim_nd, dim_np, rounds, nl, nn);
     if (rc != BPPP_OK) return rc;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t per = agg_part_size(c, n);
-    rc = agg_verify_prepare(c, per, nullptr);
+    rc = agg_verify_prepare(c, per, rlc_seed);
     if (rc != BPPP_OK) return rc;
     const size_t pb = agg_proof_bytes(k_max, rounds, nl, nn);
     const size_t o_com = 0, o_pr = align16(n * k_max * 64), o_ks = align16(o_pr + n * pb), o_acc = align16(o_ks + n), o_st = align16(o_acc + n),
-                 o_ws = align16(o_st + n * 4), total = o_ws + agg_mixed_ws_bytes(c, per, k_max, dim_nd, dim_np, rounds, nl, nn);
+                 o_ws = align16(o_st + n * 4),
+                 total = o_ws + agg_mixed_ws_bytes(c, per, k_max, dim_nd, dim_np, rounds, nl, nn, rlc_seed != nullptr);
     WnlaBlob blob;
     { const int rc_b = blob.take(c, total); if (rc_b != BPPP_OK) return rc_b; }
     uint8_t* d = blob.d;
@@ -1129,12 +1159,25 @@ int bppp_reciprocal_agg_verify_batch_mixed(bppp_ctx* c, const uint8_t* label, si
     HIP_TRY(hipMemcpyAsync(d + o_pr, proofs, n * pb, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_ks, ks, n, hipMemcpyHostToDevice, s));
     rc = agg_mixed_parts(c, label, label_len, n, k_max, d + o_ks, dim_nd, dim_np, d + o_com, d + o_pr, rounds, nl, nn, d + o_acc,
-                         (int32_t*)(d + o_st), d + o_ws);
+                         (int32_t*)(d + o_st), d + o_ws, rlc_seed);
     if (rc != BPPP_OK) return rc;
     HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return BPPP_OK;
+}
+int bppp_reciprocal_agg_verify_batch_mixed(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
+                                           size_t dim_nd, size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds,
+                                           size_t nl, size_t nn, uint8_t* accept, int32_t* status) {
+    CtxLock lock_(c);
+    return agg_mixed_host_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr);
+}
+int bppp_reciprocal_agg_verify_batch_mixed_rlc(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
+                                               size_t dim_nd, size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds,
+                                               size_t nl, size_t nn, uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_mixed_host_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, seed);
 }
 
 // ---------------------------------------------------------------- generic ArithmeticCircuit (circuit.rs:95-256)
@@ -2207,6 +2250,103 @@ int bppp_reciprocal_agg_verify_batch_rlc_sec1(bppp_ctx* c, const uint8_t* label,
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
     return agg_sec1_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, seed);
+}
+
+// ---- aggregates of mixed value counts: 33-byte slots laid out by k_max, instance i in the uniform wire layout for ks[i] in front of
+//      its slots.  k_wire_expand_mixed (wire_mixed_core.h) once over the whole call on the context's stream, in front of the max_batch
+//      parts; the mixed chain then runs on the expanded slots.  Nothing is forwarded: k_max = 1 runs here too
+// arguments checked, n > 0; d_exp: agg_sec1_exp_bytes(n, k_max) in the wire buffer
+static int agg_mixed_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* d_ks, size_t dim_nd,
+                              size_t dim_np, const uint8_t* d_com33, const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn,
+                              void* d_accept, void* d_status, void* d_reject_count, uint8_t* d_exp, const uint8_t* rlc_seed) {
+    const size_t o_p = align16(n * k_max * 64);
+    WireMixed m;
+    m.com33 = d_com33; m.proofs33 = d_proofs33; m.com64 = d_exp; m.proofs64 = d_exp + o_p; m.ks = d_ks;
+    m.n = n; m.k_max = (u32)k_max; m.rounds = (u32)rounds; m.ns = (u32)(nl + nn);
+    k_wire_expand_mixed<<<(unsigned)((wire_mixed_lanes(m) + 255) / 256), 256, 0, c->stream>>>(m);
+    HIP_TRY(hipGetLastError());
+    return agg_mixed_device_run(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status,
+                                d_reject_count, rlc_seed);
+}
+static int agg_mixed_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks,
+                                      size_t dim_nd, size_t dim_np, const void* d_commitments33, const void* d_proofs33, size_t rounds,
+                                      size_t nl, size_t nn, void* d_accept, void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
+    if (!c || !label_ok(label, label_len) || !d_commitments33 || !d_proofs33 || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
+    int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, (const uint8_t*)d_ks, 1, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (n == 0) {
+        if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
+        return BPPP_OK;
+    }
+    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, agg_sec1_exp_bytes(n, k_max, rounds, nl, nn));
+    if (rc != BPPP_OK) return rc;
+    return agg_mixed_sec1_run(c, label, label_len, n, k_max, (const uint8_t*)d_ks, dim_nd, dim_np, (const uint8_t*)d_commitments33,
+                              (const uint8_t*)d_proofs33, rounds, nl, nn, d_accept, d_status, d_reject_count, c->d_wire, rlc_seed);
+}
+int bppp_reciprocal_agg_verify_batch_mixed_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                       const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments33,
+                                                       const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                                       void* d_status, void* d_reject_count) {
+    CtxLock lock_(c);
+    return agg_mixed_sec1_device_impl(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept,
+                                      d_status, d_reject_count, nullptr);
+}
+int bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                           const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments33,
+                                                           const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                                           void* d_status, void* d_reject_count, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_mixed_sec1_device_impl(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept,
+                                      d_status, d_reject_count, seed);
+}
+// host buffers: ks and the 33-byte slots staged in the wire buffer too, in front of accept, status and the expanded form
+static int agg_mixed_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
+                                    size_t dim_nd, size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds,
+                                    size_t nl, size_t nn, uint8_t* accept, int32_t* status, const uint8_t* rlc_seed) {
+    if (!c || !label_ok(label, label_len) || !commitments33 || !proofs33 || !accept) return BPPP_ERR_INVALID_ARG;
+    int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, ks, 0, dim_nd, dim_np, rounds, nl, nn);
+    if (rc != BPPP_OK) return rc;
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
+    const size_t pb = wire_proof_bytes(4 + 2 * rounds + k_max, nl + nn);
+    const size_t o_c = 0, o_p = align16(n * k_max * 33), o_k = align16(o_p + n * pb), o_a = align16(o_k + n), o_s = align16(o_a + n),
+                 o_e = align16(o_s + n * 4), total = o_e + agg_sec1_exp_bytes(n, k_max, rounds, nl, nn);
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
+    if (rc != BPPP_OK) return rc;
+    WireQuiesce guard{c};
+    uint8_t* d = c->d_wire;
+    hipStream_t s = c->stream;
+    // (the whole slots go up; the expansion reads an instance's first k_i commitments and S(k_i) bytes only)
+    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * k_max * 33, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_k, ks, n, hipMemcpyHostToDevice, s));
+    rc = agg_mixed_sec1_run(c, label, label_len, n, k_max, d + o_k, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, nullptr,
+                            d + o_e, rlc_seed);
+    if (rc != BPPP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPPP_OK;
+}
+int bppp_reciprocal_agg_verify_batch_mixed_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
+                                                size_t dim_nd, size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33,
+                                                size_t rounds, size_t nl, size_t nn, uint8_t* accept, int32_t* status) {
+    CtxLock lock_(c);
+    return agg_mixed_sec1_host_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status,
+                                    nullptr);
+}
+int bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                    const uint8_t* ks, size_t dim_nd, size_t dim_np, const uint8_t* commitments33,
+                                                    const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                                    int32_t* status, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_mixed_sec1_host_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status,
+                                    seed);
 }
 
 // ---- circuit

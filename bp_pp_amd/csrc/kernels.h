@@ -16,6 +16,7 @@
 #include "wnla_rlc_core.h"
 #include "wnla_prove_core.h"
 #include "wire_core.h"
+#include "wire_mixed_core.h"
 #include "draw_core.h"
 
 #define BPPP_BLOCK 64
@@ -142,6 +143,8 @@ __global__ __launch_bounds__(256) void k_sec1_compress(uint8_t* commitments33, u
 // the generic proofs' wire form (k_wire.hip): expand / compress over a layout descriptor
 __global__ __launch_bounds__(256) void k_wire_expand(bppp::WireMap m);
 __global__ __launch_bounds__(256) void k_wire_compress(bppp::WireMap m);
+// the aggregate's mixed-value-count call (k_wire_mixed.hip, wire_mixed_core.h): slots laid out by k_max, every instance on its own k
+__global__ __launch_bounds__(256) void k_wire_expand_mixed(bppp::WireMixed m);
 // the seeded provers' draws (k_draw.hip): n x k scalars in the `rnd` layout, one lane per draw
 __global__ __launch_bounds__(256) void k_draw_scalars(bppp::DrawKey key, bppp::u64 stream_base, bppp::u64 k, bppp::u64 total, uint8_t* out);
 // the u64 prover's stages that touch the transcript run once per distinct sponge position in the wavefront (for_each_position_group

@@ -719,6 +719,57 @@ class AggregatedReciprocalRangeProofProtocol:
                                                                                   rounds, nl, nn, d_accept, d_status,
                                                                                   d_reject_count or None))
 
+    def _verify_mixed_host(self, name: str, point: int, label: bytes, ks, commitments, proofs, rounds: int, nl: int, nn: int, seed=None):
+        ks = _u8(ks, (-1,))
+        B = ks.shape[0]
+        commitments = _u8(commitments, (B, self.k, point))
+        proofs = _u8(proofs, (B, (self.proof_sec1_bytes if point == 33 else self.proof_bytes)(rounds, nl, nn)))
+        acc, st = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        tail = () if seed is None else (_rlc_seed(seed),)
+        _capi.check(_capi.symbol(name)(self._w._ctx, label, len(label), B, self.k, ks.ctypes.data, self.dim_nd, self.dim_np,
+                                       commitments.ctypes.data, proofs.ctypes.data, rounds, nl, nn, acc.ctypes.data, st.ctypes.data, *tail))
+        return acc, st
+
+    def _verify_mixed_device(self, name: str, label: bytes, n: int, d_ks: int, d_commitments: int, d_proofs: int, rounds: int, nl: int,
+                             nn: int, d_accept: int, d_status: int, d_reject_count: int, seed=None) -> None:
+        tail = () if seed is None else (_rlc_seed(seed),)
+        _capi.check(_capi.symbol(name)(self._w._ctx, label, len(label), n, self.k, d_ks, self.dim_nd, self.dim_np, d_commitments, d_proofs,
+                                       rounds, nl, nn, d_accept, d_status, d_reject_count or None, *tail))
+
+    def verify_batch_mixed_rlc(self, label: bytes, ks, commitments, proofs, rounds: int, nl: int, nn: int, seed: bytes):
+        """verify_batch_mixed with the final sum in RLC mode (as verify_batch_rlc): the exact mixed call's accept / status per
+        instance.  seed: 32 bytes the prover cannot predict."""
+        return self._verify_mixed_host("bppp_reciprocal_agg_verify_batch_mixed_rlc", 64, label, ks, commitments, proofs, rounds, nl, nn, seed)
+
+    def verify_batch_mixed_rlc_device(self, label: bytes, n: int, d_ks: int, d_commitments: int, d_proofs: int, rounds: int, nl: int,
+                                      nn: int, d_accept: int, d_status: int, seed: bytes, d_reject_count: int = 0) -> None:
+        """verify_batch_mixed_rlc over device buffers (raw device pointers), asynchronous on the context's stream."""
+        self._verify_mixed_device("bppp_reciprocal_agg_verify_batch_mixed_rlc_device", label, n, d_ks, d_commitments, d_proofs, rounds, nl,
+                                  nn, d_accept, d_status, d_reject_count, seed)
+
+    def verify_batch_mixed_sec1(self, label: bytes, ks, commitments33, proofs33, rounds: int, nl: int, nn: int):
+        """verify_batch_mixed over the wire form: commitments33 [B, k, 33] of which row i's first ks[i] are read, proofs33
+        [B, proof_sec1_bytes] of which row i's first 33 (4 + 2 rounds + ks[i]) + 32 (nl + nn) bytes are read (wire.pack of that row's
+        proof for ks[i]); an undecodable point flags its instance ST_BAD_ENCODING."""
+        return self._verify_mixed_host("bppp_reciprocal_agg_verify_batch_mixed_sec1", 33, label, ks, commitments33, proofs33, rounds, nl, nn)
+
+    def verify_batch_mixed_sec1_device(self, label: bytes, n: int, d_ks: int, d_commitments33: int, d_proofs33: int, rounds: int, nl: int,
+                                       nn: int, d_accept: int, d_status: int, d_reject_count: int = 0) -> None:
+        """verify_batch_mixed_sec1 over device buffers (raw device pointers), asynchronous on the context's stream."""
+        self._verify_mixed_device("bppp_reciprocal_agg_verify_batch_mixed_sec1_device", label, n, d_ks, d_commitments33, d_proofs33, rounds,
+                                  nl, nn, d_accept, d_status, d_reject_count)
+
+    def verify_batch_mixed_rlc_sec1(self, label: bytes, ks, commitments33, proofs33, rounds: int, nl: int, nn: int, seed: bytes):
+        """verify_batch_mixed_rlc over the wire form; a flagged instance is in no weighted sum."""
+        return self._verify_mixed_host("bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1", 33, label, ks, commitments33, proofs33, rounds, nl,
+                                       nn, seed)
+
+    def verify_batch_mixed_rlc_sec1_device(self, label: bytes, n: int, d_ks: int, d_commitments33: int, d_proofs33: int, rounds: int,
+                                           nl: int, nn: int, d_accept: int, d_status: int, seed: bytes, d_reject_count: int = 0) -> None:
+        """verify_batch_mixed_rlc_sec1 over device buffers (raw device pointers), asynchronous on the context's stream."""
+        self._verify_mixed_device("bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1_device", label, n, d_ks, d_commitments33, d_proofs33,
+                                  rounds, nl, nn, d_accept, d_status, d_reject_count, seed)
+
     def proof_sec1_bytes(self, rounds: int, nl: int, nn: int) -> int:
         """Bytes of a proof in the wire form: 33 (4 + 2 rounds + k) + 32 (nl + nn)."""
         return int(_capi.symbol("bppp_reciprocal_agg_proof_sec1_bytes")(self.k, rounds, nl, nn))

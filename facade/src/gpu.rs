@@ -307,6 +307,34 @@ impl U64RangeProofProtocolGpu {
         }
         Ok(acc.iter().map(|a| *a == 1).collect())
     }
+
+    /// `verify_agg_mixed` with the final sum in RLC mode, over the 33-byte SEC1 wire form, or both
+    /// (bppp_reciprocal_agg_verify_batch_mixed_rlc / _sec1 / _rlc_sec1, include/bppp.h).  `seed`: 32 bytes the prover cannot predict
+    /// selects RLC mode; `sec1`: `commitments` is n x k_max x 33 bytes and `proofs` n x (33 (4 + 2 rounds + k_max) + 32 (nl + nn)), of
+    /// which instance i's first 33 (4 + 2 rounds + ks[i]) + 32 (nl + nn) are read.  The verdicts are `verify_agg_mixed`'s.
+    pub fn verify_agg_mixed_with(&self, label: &'static [u8], k_max: usize, ks: &[u8], dim_nd: usize, dim_np: usize, commitments: &[u8], proofs: &[u8], rounds: usize, nl: usize, nn: usize, sec1: bool, seed: Option<&[u8; 32]>) -> Result<Vec<bool>, GpuError> {
+        let n = ks.len();
+        let (point, stride) = if sec1 {
+            (33, unsafe { bppp_reciprocal_agg_proof_sec1_bytes(k_max, rounds, nl, nn) })
+        } else {
+            (64, unsafe { bppp_reciprocal_agg_proof_bytes(k_max, rounds, nl, nn) })
+        };
+        assert!(commitments.len() == n * k_max * point && proofs.len() == n * stride);
+        let (mut acc, mut st) = (vec![0u8; n], vec![0i32; n]);
+        let (l, ll, k, c, p, a, s) = (label.as_ptr(), label.len(), ks.as_ptr(), commitments.as_ptr(), proofs.as_ptr(), acc.as_mut_ptr(), st.as_mut_ptr());
+        check(unsafe {
+            match (sec1, seed) {
+                (false, None) => bppp_reciprocal_agg_verify_batch_mixed(self.ctx, l, ll, n, k_max, k, dim_nd, dim_np, c, p, rounds, nl, nn, a, s),
+                (false, Some(sd)) => bppp_reciprocal_agg_verify_batch_mixed_rlc(self.ctx, l, ll, n, k_max, k, dim_nd, dim_np, c, p, rounds, nl, nn, a, s, sd.as_ptr()),
+                (true, None) => bppp_reciprocal_agg_verify_batch_mixed_sec1(self.ctx, l, ll, n, k_max, k, dim_nd, dim_np, c, p, rounds, nl, nn, a, s),
+                (true, Some(sd)) => bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1(self.ctx, l, ll, n, k_max, k, dim_nd, dim_np, c, p, rounds, nl, nn, a, s, sd.as_ptr()),
+            }
+        })?;
+        if let Some(i) = st.iter().position(|s| s & BPPP_ST_DEGENERATE != 0) {
+            return Err(GpuError::ReferenceWouldPanic { index: i });
+        }
+        Ok(acc.iter().map(|a| *a == 1).collect())
+    }
 }
 
 impl Drop for U64RangeProofProtocolGpu {

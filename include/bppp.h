@@ -718,8 +718,9 @@ BPPP_API int bppp_reciprocal_agg_verify_batch_device(bppp_ctx* ctx, const uint8_
  * size and k_max) and the behaviour after an allocation failure are the uniform call's.  Cost: an instance pays phase 1 and the
  * variable-base half of C0 for its own k_i -- a wavefront for the largest of its 64 -- and the fixed-base half for k_max (docs/design
  * 07 section 7d has the measurements).
- * Exact mode, 64-byte points and label transcripts only.  NOT built: the SEC1 form, the RLC form and the caller-transcript form of
- * the mixed call, a mixed prover, reordering instances by k on the device; and, as above, the single-proof front end and sharded groups. */
+ * Label transcripts only.  Of the SEC1 form, the RLC form and the caller-transcript form of the mixed call, the first two are the
+ * entry points below.  NOT built: the caller-transcript form, a mixed prover, reordering instances by k on the device; and, as
+ * above, the single-proof front end and sharded groups. */
 BPPP_API int bppp_reciprocal_agg_mixed_check_args(size_t ng, size_t nh, size_t n, size_t k_max, const uint8_t* ks, int ks_on_device,
                                                   size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn);
 BPPP_API int bppp_reciprocal_agg_verify_batch_mixed(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
@@ -730,6 +731,48 @@ BPPP_API int bppp_reciprocal_agg_verify_batch_mixed_device(bppp_ctx* ctx, const 
                                                            const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments,
                                                            const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
                                                            void* d_status, void* d_reject_count);
+/* The mixed call in RLC mode and in the WIRE form (both described for the uniform aggregate below); k_max and ks sit where the mixed
+ * call has them, seed comes last.  The argument decisions are the mixed call's (bppp_reciprocal_agg_mixed_check_args; the device forms
+ * check d_ks for NULL only; n = 0 is BPPP_OK and zeroes d_reject_count); the RLC forms also refuse a NULL seed.  Nothing is forwarded.
+ *   _rlc    the final sum in RLC mode, by the rule of bppp_reciprocal_agg_verify_batch_rlc: accept, status and reject count are the
+ *           exact mixed call's; "last_rlc_superchunk" / "last_rlc_chunk" report the first part ((0, 0): fewer than 8 instances).  The
+ *           RLC stage runs behind the final scalars and does not depend on an instance's value count.
+ *   _sec1   33-byte slots laid out by k_max:
+ *             commitments33  n x k_max x 33; instance i uses the first k_i x 33 bytes
+ *             proofs33       n x S(k_max), S(k) = bppp_reciprocal_agg_proof_sec1_bytes(k, rounds, nl, nn); instance i uses the first
+ *                            S(k_i) bytes of its slot in the uniform wire layout for k_i: 4 + 2 rounds + k_i compressed points, then
+ *                            l | n.  Nothing behind those bytes is ever read.
+ *           One launch (k_wire_expand_mixed) expands the whole call into 64-byte slots laid out by k_max in the context's wire buffer,
+ *           on the context's stream in front of the "max_batch" parts; the host forms stage ks and their input there too.  Return code,
+ *           accept, status and reject count are the 64-byte mixed call's on the expanded input; an undecodable point flags its instance
+ *           BPPP_ST_BAD_ENCODING.  A d_ks[i] outside [1, k_max] is expanded as a one-value instance and flagged as in the 64-byte form. */
+BPPP_API int bppp_reciprocal_agg_verify_batch_mixed_rlc(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                        const uint8_t* ks, size_t dim_nd, size_t dim_np, const uint8_t* commitments,
+                                                        const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                                        int32_t* status, const uint8_t seed[32]);
+BPPP_API int bppp_reciprocal_agg_verify_batch_mixed_rlc_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                                               size_t k_max, const void* d_ks, size_t dim_nd, size_t dim_np,
+                                                               const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
+                                                               size_t nn, void* d_accept, void* d_status, void* d_reject_count,
+                                                               const uint8_t seed[32]);
+BPPP_API int bppp_reciprocal_agg_verify_batch_mixed_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                         const uint8_t* ks, size_t dim_nd, size_t dim_np, const uint8_t* commitments33,
+                                                         const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                                         int32_t* status);
+BPPP_API int bppp_reciprocal_agg_verify_batch_mixed_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                                                size_t k_max, const void* d_ks, size_t dim_nd, size_t dim_np,
+                                                                const void* d_commitments33, const void* d_proofs33, size_t rounds,
+                                                                size_t nl, size_t nn, void* d_accept, void* d_status,
+                                                                void* d_reject_count);
+BPPP_API int bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                             const uint8_t* ks, size_t dim_nd, size_t dim_np, const uint8_t* commitments33,
+                                                             const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
+                                                             int32_t* status, const uint8_t seed[32]);
+BPPP_API int bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                                                    size_t k_max, const void* d_ks, size_t dim_nd, size_t dim_np,
+                                                                    const void* d_commitments33, const void* d_proofs33, size_t rounds,
+                                                                    size_t nl, size_t nn, void* d_accept, void* d_status,
+                                                                    void* d_reject_count, const uint8_t seed[32]);
 /* The aggregate in the WIRE form (as bppp_reciprocal_verify_batch_sec1 below): the layout above with every point 33-byte
  * SEC1-compressed in place (02 | 03 by the parity of y, then x; the identity is 33 zero bytes) and the scalars unchanged.
  *   commitments33  n x k x 33, value-major
