@@ -131,6 +131,22 @@ static void launch_wnla_final_scalars(const WnlaWs& w, int lg, unsigned blocks, 
         k_wnla_final_scalars_join<<<blocks, BPPP_BLOCK, 0, s>>>(w, lg);
     } else k_wnla_final_scalars<<<blocks, BPPP_BLOCK, 0, s>>>(w);
 }
+// the device forms' optional counter of rejected instances: zeroed in front of the call (it reads zero after a call of no instances
+// too), counted behind its last verdict; null = the caller did not ask
+static int reset_reject_count(bppp_ctx* c, void* d_reject_count) {
+    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
+    return BPPP_OK;
+}
+static int launch_count_rejects(bppp_ctx* c, const void* d_accept, size_t n, void* d_reject_count) {
+    if (!d_reject_count) return BPPP_OK;
+    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
+    HIP_TRY(hipGetLastError());
+    return BPPP_OK;
+}
+// "last_rlc_*" of an RLC call start at (0, 0), before its first allocation: a call that fails reports nothing stale
+static void rlc_report_reset(bppp_ctx* c, const uint8_t* rlc_seed) {
+    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
+}
 // one part of a multi-part call (recip_verify_device_entry): its stream and its shares of the context's buffers
 // (started / stage: an event recorded behind the part's stage-th milestone -- 1 phase 1, 2 the C0 stage, 3 the rounds -- that the NEXT
 // part's chain waits for, so that the chains run out of step: one part's fixed-base sums under another's one-lane kernels)
@@ -156,6 +172,42 @@ static void wire_add_proof(WireMap& m, const uint8_t* src33, uint8_t* dst64, siz
     wire_map_add(m, true, src33 + 33 * P, b33, dst64 + 64 * P, b64, S);
 }
 static size_t wire_proof_bytes(size_t P, size_t S) { return 33 * P + 32 * S; }
+// THE EXPANSION of a wire-form verify call, stated once per protocol: n instances of k commitments and a proof of P points and S scalars
+// become the 64-byte commitments | the 64-byte proofs (at o_proofs) in the wire buffer -- what the 64-byte verifier then reads
+struct WireExp {
+    size_t n, k, P, S;
+    size_t com33_bytes() const { return n * k * 33; }
+    size_t proofs33_bytes() const { return n * wire_proof_bytes(P, S); }
+    size_t o_proofs() const { return align16(n * k * 64); }
+    size_t bytes() const { return o_proofs() + n * (64 * P + 32 * S); }
+    int launch(const uint8_t* d_com33, const uint8_t* d_proofs33, uint8_t* d_exp, hipStream_t s) const {
+        WireMap m;
+        wire_map_init(m, n);
+        wire_map_add(m, false, d_com33, 33 * k, d_exp, 64 * k, k);
+        wire_add_proof(m, d_proofs33, d_exp + o_proofs(), P, S);
+        return wire_launch(m, true, s);
+    }
+};
+static WireExp recip_wire_exp(size_t n, size_t rounds, size_t nl, size_t nn) { return {n, 1, 5 + 2 * rounds, nl + nn}; }
+static WireExp agg_wire_exp(size_t n, size_t k, size_t rounds, size_t nl, size_t nn) { return {n, k, 4 + 2 * rounds + k, nl + nn}; }
+static WireExp circuit_wire_exp(size_t n, size_t k, size_t rounds, size_t nl, size_t nn) { return {n, k, 4 + 2 * rounds, nl + nn}; }
+// the WNLA call's: the commitment | proof.r | proof.x (c, rho, mu, proof.l and proof.n are scalars, read where they are)
+struct WnlaWireExp {
+    size_t n, rounds;
+    size_t o_r() const { return align16(n * 64); }
+    size_t o_x() const { return o_r() + align16(n * rounds * 64); }
+    size_t bytes() const { return o_x() + align16(n * rounds * 64); }
+    int launch(const uint8_t* d_com33, const uint8_t* d_r33, const uint8_t* d_x33, uint8_t* d_exp, hipStream_t s) const {
+        WireMap m;
+        wire_map_init(m, n);
+        wire_map_add(m, false, d_com33, 33, d_exp, 64, 1);
+        if (rounds) {
+            wire_map_add(m, false, d_r33, 33 * rounds, d_exp + o_r(), 64 * rounds, rounds);
+            wire_map_add(m, false, d_x33, 33 * rounds, d_exp + o_x(), 64 * rounds, rounds);
+        }
+        return wire_launch(m, true, s);
+    }
+};
 // a prover's input points (k per instance) from the caller's host memory to d_dst in the 64-byte form: copied as they are, or (sec1)
 // staged as 33 bytes at the head of the wire buffer, grown to wire_bytes for what the call will put behind them, and expanded on the device
 static int prover_points_in(bppp_ctx* c, bool sec1, const uint8_t* src, uint8_t* d_dst, size_t n, size_t k, size_t wire_bytes, hipStream_t s) {
@@ -168,11 +220,6 @@ static int prover_points_in(bppp_ctx* c, bool sec1, const uint8_t* src, uint8_t*
     wire_map_add(wm, false, c->d_wire, 33 * k, d_dst, 64 * k, k);
     return wire_launch(wm, true, s);
 }
-// a failed host-buffer call leaves nothing running behind it (the staging is reused by the next call); after the final sync it costs nothing
-struct WireQuiesce {
-    bppp_ctx* c = nullptr;
-    ~WireQuiesce() { if (c) quiesce(c); }
-};
 
 // ---- generic WeightNormLinearArgument entry points (host pointers; one device blob per call)
 // (the context's grow-only buffer: no allocator round trip per call.  Whatever way the call ends, nothing of it is still running
@@ -187,6 +234,58 @@ struct WnlaBlob {
         return rc;
     }
     ~WnlaBlob() { if (c) quiesce(c); }
+};
+// THE HOST STAGING of a verify call over host buffers, in the blob or (the wire forms) in the wire buffer:
+//     the inputs as given | accept n | status n x 4 | the caller's states in | their states out | `tail` bytes (workspace or expansion)
+// begin() grows the buffer and queues the copies up on the context's stream; finish() takes the code of what ran between the two and,
+// unless that failed, queues the copies back -- states out, accept, status where the caller asked for it -- and waits for the stream,
+// the call's one sync.  Whatever way the call ends, nothing of it is
+// still running when the staging goes out of scope (it is reused by the next call); behind finish() that costs nothing.
+struct HostIn { const void* src; size_t bytes; };       // (null or empty: room is made, nothing is copied)
+struct HostStage {
+    bppp_ctx* c = nullptr;
+    static constexpr size_t MAX_IN = 8;
+    uint8_t *in[MAX_IN], *accept = nullptr, *tail = nullptr;
+    int32_t* status = nullptr;
+    TranscriptIo tio = {nullptr, 0, nullptr, 0};
+    const TranscriptIo* dtio = nullptr;                 // &tio, or null without caller transcripts
+    // gws_bytes: what the call needs of the device forms' workspace besides, grown behind the staging and in front of the first copy
+    int begin(bppp_ctx* ctx, bool wire, std::initializer_list<HostIn> ins, size_t n, const HostTranscripts* tx, size_t tail_bytes,
+              size_t gws_bytes = 0) {
+        size_t off = 0, o_in[MAX_IN], k = 0;
+        if (ins.size() > MAX_IN) return BPPP_ERR_INVALID_ARG;
+        for (const HostIn& i : ins) o_in[k++] = take_bytes(off, i.bytes);
+        const size_t o_acc = take_bytes(off, n), o_st = take_bytes(off, n * 4), o_ti = take_bytes(off, tx ? tx->n_states * 203 : 0),
+                     o_to = take_bytes(off, tx && tx->states_out ? n * 203 : 0);
+        if (!wire) c = ctx;      // (a blob call quiesces even where the blob fails to grow, as it always did)
+        int rc = wire ? ensure_buffer(ctx, ctx->d_wire, ctx->wire_bytes, off + tail_bytes) : ensure_blob(ctx, off + tail_bytes);
+        if (rc == BPPP_OK && gws_bytes) rc = ensure_buffer(ctx, ctx->d_gws, ctx->gws_bytes, gws_bytes);
+        if (rc != BPPP_OK) return rc;
+        c = ctx;                 // (a wire call quiesces from here on, its buffers grown, as it always did)
+        uint8_t* d = wire ? c->d_wire : c->d_blob;
+        k = 0;
+        for (const HostIn& i : ins) {
+            in[k] = d + o_in[k];
+            if (i.src && i.bytes) HIP_TRY(hipMemcpyAsync(in[k], i.src, i.bytes, hipMemcpyHostToDevice, c->stream));
+            k++;
+        }
+        accept = d + o_acc; status = (int32_t*)(d + o_st); tail = d + off;
+        if (tx) {
+            HIP_TRY(hipMemcpyAsync(d + o_ti, tx->states, tx->n_states * 203, hipMemcpyHostToDevice, c->stream));
+            tio.states = d + o_ti; tio.n_states = tx->n_states; tio.states_out = tx->states_out ? d + o_to : nullptr;
+            dtio = &tio;
+        }
+        return BPPP_OK;
+    }
+    int finish(int rc_run, size_t n, uint8_t* h_accept, int32_t* h_status, const HostTranscripts* tx) {
+        if (rc_run != BPPP_OK) return rc_run;
+        if (tio.states_out) HIP_TRY(hipMemcpyAsync(tx->states_out, tio.states_out, n * 203, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_accept, accept, n, hipMemcpyDeviceToHost, c->stream));
+        if (h_status) HIP_TRY(hipMemcpyAsync(h_status, status, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return BPPP_OK;
+    }
+    ~HostStage() { if (c) quiesce(c); }
 };
 
 // ---- the random-linear-combination mode of the final sum (wnla_rlc_core.h), shared by the three generic verifiers: every one of them
@@ -254,7 +353,7 @@ static int wnla_rlc_final_sum(bppp_ctx* c, const WnlaWs& w, const uint8_t* rlc_s
 // "last_rlc_*" reset before the first allocation (a call that fails reports nothing stale), the projective tables, the bucket stage
 static int wnla_call_prepare(bppp_ctx* c, size_t n, const uint8_t* rlc_seed, bool& rlc) {
     rlc = rlc_seed && wnla_rlc_applies(n);
-    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
+    rlc_report_reset(c, rlc_seed);
     const int rc = ensure_straus_capacity(c, n);
     if (rc != BPPP_OK) return rc;
     return rlc ? wnla_rlc_prepare(c, n) : BPPP_OK;
@@ -569,8 +668,8 @@ int recip_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_le
     if (recip_is_u64_shape(c, dim_nd, dim_np, rounds, nl, nn))
         return verify_device_impl(c, label, label_len, n, d_commitments, d_proofs, d_accept, d_status, nullptr, d_reject_count, rlc_seed, nullptr);
     HIP_TRY(hipSetDevice(c->device));
-    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
-    if (n == 0) return BPPP_OK;
+    rc = reset_reject_count(c, d_reject_count);
+    if (rc != BPPP_OK || n == 0) return rc;
     rc = ensure_straus_capacity(c, n);
     if (rc != BPPP_OK) return rc;
     // A call that leaves the chip under-filled runs as K PARTS on K streams.  One lane per instance gives 2^15 instances of BASELINE
@@ -627,10 +726,7 @@ int recip_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_le
         rc = recip_verify_device_impl(c, label, label_len, n, dim_nd, dim_np, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, rounds, nl,
                                       nn, (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws, nullptr, rlc_seed);
     }
-    if (rc != BPPP_OK || !d_reject_count) return rc;
-    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
-    HIP_TRY(hipGetLastError());
-    return BPPP_OK;
+    return rc != BPPP_OK ? rc : launch_count_rejects(c, d_accept, n, d_reject_count);
 }
 int bppp_reciprocal_verify_batch_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
                                         const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn,
@@ -687,29 +783,13 @@ static int recip_verify_host_impl(bppp_ctx* c, const uint8_t* label, size_t labe
     rc = ensure_straus_capacity(c, n);
     if (rc != BPPP_OK) return rc;
     const size_t proof_bytes = 64 * (5 + 2 * rounds) + 32 * (nl + nn);
-    const size_t o_com = 0, o_pr = align16(n * 64), o_acc = align16(o_pr + n * proof_bytes), o_st = align16(o_acc + n),
-                 o_ti = align16(o_st + n * 4), o_to = align16(o_ti + (tx ? tx->n_states * 203 : 0)),
-                 o_ws = align16(o_to + (tx && tx->states_out ? n * 203 : 0)),
-                 total = o_ws + recip_verify_ws_bytes(c, n, dim_nd, dim_np, rounds, rlc_seed != nullptr);
-    WnlaBlob blob;
-    { const int rc_b = blob.take(c, total); if (rc_b != BPPP_OK) return rc_b; }
-    uint8_t* d = blob.d;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * 64, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_pr, proofs, n * proof_bytes, hipMemcpyHostToDevice, s));
-    TranscriptIo dtio = {nullptr, 0, nullptr, 0};
-    if (tx) {
-        HIP_TRY(hipMemcpyAsync(d + o_ti, tx->states, tx->n_states * 203, hipMemcpyHostToDevice, s));
-        dtio.states = d + o_ti; dtio.n_states = tx->n_states; dtio.states_out = tx->states_out ? d + o_to : nullptr;
-    }
-    rc = recip_verify_device_impl(c, label, label_len, n, dim_nd, dim_np, d + o_com, d + o_pr, rounds, nl, nn, d + o_acc, (int32_t*)(d + o_st),
-                                  d + o_ws, tx ? &dtio : nullptr, rlc_seed);
+    HostStage hs;
+    rc = hs.begin(c, false, {{commitments, n * 64}, {proofs, n * proof_bytes}}, n, tx,
+                  recip_verify_ws_bytes(c, n, dim_nd, dim_np, rounds, rlc_seed != nullptr));
     if (rc != BPPP_OK) return rc;
-    if (dtio.states_out) HIP_TRY(hipMemcpyAsync(tx->states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    rc = recip_verify_device_impl(c, label, label_len, n, dim_nd, dim_np, hs.in[0], hs.in[1], rounds, nl, nn, hs.accept, hs.status, hs.tail,
+                                  hs.dtio, rlc_seed);
+    return hs.finish(rc, n, accept, status, tx);
 }
 
 // ---------------------------------------------------------------- aggregated reciprocal range proof: k values under one proof
@@ -739,33 +819,48 @@ static int agg_shape_check(size_t ng, size_t nh, size_t k, size_t dim_nd, size_t
         return BPPP_ERR_INVALID_ARG;
     return BPPP_OK;
 }
-static int agg_verify_check_args(const bppp_ctx* c, size_t k, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn) {
-    return agg_shape_check((size_t)c->ng, (size_t)c->nh, k, dim_nd, dim_np, rounds, nl, nn);
-}
-// the launch sequence of one call (or of one max_batch part of it), every buffer in device memory; d_ws holds agg_verify_layout().total
+// THE SHAPE OF AN AGGREGATE VERIFY CALL as its entry point was given it, handed down unchanged through the runs, the parts and the chain
+// mixed: the call is one of MIXED value counts (agg_mixed_core.h) -- instance i has ks[i] values in slots laid out by k, its k_max
 // rlc_seed: the final sum in RLC mode -- by the WNLA and circuit verifiers' rule (wnla_rlc_applies), so a part of fewer than 8
 // instances runs the exact sum; everything before the final sum is the exact pipeline in the plan's launch form either way
-static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
-                                  const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
-                                  int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed = nullptr, const TranscriptIo* dtio = nullptr) {
-    const GenericPlan plan = plan_generic(GENERIC_FORM_AGGREGATE, n, rounds, generic_knobs_of(c), n, 1, 4 + k);
-    const bool rlc = rlc_seed && wnla_rlc_applies(n);
-    const AggVerifyLayout o = agg_verify_layout(c, n, k, dim_nd, dim_np, rounds, rlc);
-    uint8_t* d = d_ws;
-    hipStream_t s = c->stream;
-    AggWs r;
-    std::memset(&r, 0, sizeof r);
-    r.N = n; r.k = (int)k; r.nd = (int)dim_nd; r.np = (int)dim_np; r.rounds = (int)rounds; r.nl = (int)nl; r.nn = (int)nn;
-    r.NG = c->ng; r.NH = c->nh; r.proof_bytes = agg_proof_bytes(k, rounds, nl, nn);
+struct AggCall { const uint8_t* label; size_t label_len, k; bool mixed; size_t dim_nd, dim_np, rounds, nl, nn; const uint8_t* rlc_seed; };
+// the workspace of n instances of such a call over the buffers at d, laid out by o, and the caller's device buffers
+static void agg_ws_fill(AggWs& r, const bppp_ctx* c, const AggCall& a, size_t n, uint8_t* d, const AggVerifyLayout& o, const uint8_t* d_com,
+                        const uint8_t* d_proofs, int32_t* d_st) {
+    r.N = n; r.k = (int)a.k; r.nd = (int)a.dim_nd; r.np = (int)a.dim_np; r.rounds = (int)a.rounds; r.nl = (int)a.nl; r.nn = (int)a.nn;
+    r.NG = c->ng; r.NH = c->nh; r.proof_bytes = agg_proof_bytes(a.k, a.rounds, a.nl, a.nn);
     r.commitments = d_com; r.proofs = d_proofs; r.status = d_st; r.tstate = (u32*)(d + o.ts);
     r.sc0 = (u32*)(d + o.sc0); r.pts = (u32*)(d + o.pts); r.acc = (u32*)(d + o.a); r.pfix = (u32*)(d + o.pf); r.inv = (u32*)(d + o.inv);
     r.vsum = (u32*)(d + o.vs);
     r.straus = c->d_straus;
     r.wn_commit = d + o.wc; r.wn_c = d + o.wcv; r.wn_rho = d + o.rho; r.wn_mu = d + o.mu;
     r.fb = fb_table_of(c, n);
-    t_new(r.base, label, (u32)label_len);
+    t_new(r.base, a.label, (u32)a.label_len);
+}
+// the launch sequence of one call (or of one max_batch part of it), every buffer in device memory; d_ws holds agg_ws_bytes()
+// d_ks (a mixed call): phase 1 and the variable-base half of C0 run on every instance's own count (k_agg_mixed.hip; k_i = 1 runs on
+// these kernels too), phase 1 copies l | n behind the workspace and the WNLA stage reads them there.  No caller gives both d_ks and
+// dtio: the _tx kernels are the uniform form's.  The RLC kernels read the final scalars, the commitments after the last round and the
+// statuses out of the workspace, never the proof.
+static int agg_verify_device_impl(bppp_ctx* c, const AggCall& call, size_t n, const uint8_t* d_ks, const uint8_t* d_com, const uint8_t* d_proofs,
+                                  uint8_t* d_acc, int32_t* d_st, uint8_t* d_ws, const TranscriptIo* dtio) {
+    const size_t k = call.k, rounds = call.rounds, nl = call.nl, nn = call.nn;
+    const GenericPlan plan = plan_generic(GENERIC_FORM_AGGREGATE, n, rounds, generic_knobs_of(c), n, 1, 4 + k);
+    const bool rlc = call.rlc_seed && wnla_rlc_applies(n);
+    const AggVerifyLayout o = agg_verify_layout(c, n, k, call.dim_nd, call.dim_np, rounds, rlc);
+    uint8_t* d = d_ws;
+    hipStream_t s = c->stream;
+    AggMixedWs m;                 // (the uniform kernels take its AggWs alone)
+    std::memset(&m, 0, sizeof m);
+    AggWs& r = m.w;
+    agg_ws_fill(r, c, call, n, d, o, d_com, d_proofs, d_st);
     if (dtio) r.tio = *dtio;      // the caller's transcripts: phase 1 starts on them, the WNLA stage (tio, divergent_positions) exports them
     WnlaWs w = wnla_ws_continuing(c, r, 4 + k, nl, nn, d_acc, (u32*)(d + o.ys), (u32*)(d + o.tab), (u32*)(d + o.msc));
+    if (d_ks) {
+        m.ks = d_ks; m.ln = d + o.total;
+        w.proof_l = m.ln; w.proof_n = m.ln + 32 * nl;       // (r and x sit at one offset for every k_i and are read in place)
+        w.stride_l = w.stride_n = 32 * (nl + nn);
+    }
     const unsigned blocks = blocks_of(n);
     int rc;
     // the WNLA stage's table buffer with room for the 4 + k points of C0's variable-base part behind the round points' tables
@@ -784,7 +879,10 @@ static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t labe
         GLAUNCH(a, K_WNLA_TABLES, launch_wnla_tables(w, plan.tab_parts, n, blocks, a));
     }
     const unsigned p1_blocks = G > 1 ? (unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK) : blocks;
-    if (r.tio.states) {      // the caller's transcripts: the _tx kernels, same launch form
+    if (d_ks) {
+        if (G > 1) GLAUNCH(s, K_AGG_PHASE1, k_agg_mixed_phase1_grp<<<p1_blocks, BPPP_BLOCK, 0, s>>>(m, G));
+        else GLAUNCH(s, K_AGG_PHASE1, k_agg_mixed_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(m));
+    } else if (r.tio.states) {      // the caller's transcripts: the _tx kernels, same launch form
         if (G > 1) GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1_grp_tx<<<p1_blocks, BPPP_BLOCK, 0, s>>>(r, G));
         else GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1_tx<<<p1_blocks, BPPP_BLOCK, 0, s>>>(r));
     } else if (G > 1) GLAUNCH(s, K_AGG_PHASE1, k_agg_phase1_grp<<<p1_blocks, BPPP_BLOCK, 0, s>>>(r, G));
@@ -797,23 +895,27 @@ static int agg_verify_device_impl(bppp_ctx* c, const uint8_t* label, size_t labe
     else if (plan.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
     else GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
     GLAUNCH(a, K_AGG_C0_VAR, {
-        if (plan.fast) k_agg_c0_tables<<<blocks, BPPP_BLOCK, 0, a>>>(r);
-        k_agg_c0_var<<<blocks, BPPP_BLOCK, 0, a>>>(r);
+        if (d_ks) {
+            if (plan.fast) k_agg_mixed_c0_tables<<<blocks, BPPP_BLOCK, 0, a>>>(m);
+            k_agg_mixed_c0_var<<<blocks, BPPP_BLOCK, 0, a>>>(m);
+        } else {
+            if (plan.fast) k_agg_c0_tables<<<blocks, BPPP_BLOCK, 0, a>>>(r);
+            k_agg_c0_var<<<blocks, BPPP_BLOCK, 0, a>>>(r);
+        }
     });
     if (beside) {
         HIP_TRY(hipEventRecord(c->ev_join, a));
         HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
     }
     GLAUNCH(s, K_AGG_C0_FINISH, k_agg_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    return wnla_verify_stage(c, w, plan, s, beside, rlc ? rlc_seed : nullptr, d, o.rlc);
+    return wnla_verify_stage(c, w, plan, s, beside, rlc ? call.rlc_seed : nullptr, d, o.rlc);
 }
 // a call of more than max_batch instances runs as consecutive parts on the context's stream over one workspace, as the u64 verifier's
-// (instances are independent); d_ws: agg_verify_layout(min(n, max_batch)).total
+// (instances are independent), each with its own slice of ks where the call is a mixed one; d_ws: agg_ws_bytes(min(n, max_batch))
 static size_t agg_part_size(const bppp_ctx* c, size_t n) { return n < c->max_batch ? n : c->max_batch; }
-static int agg_verify_parts(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
-                            const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
-                            int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed, const TranscriptIo* dtio = nullptr) {
-    const size_t per = agg_part_size(c, n), pb = agg_proof_bytes(k, rounds, nl, nn);
+static int agg_verify_parts(bppp_ctx* c, const AggCall& a, size_t n, const uint8_t* d_ks, const uint8_t* d_com, const uint8_t* d_proofs,
+                            uint8_t* d_acc, int32_t* d_st, uint8_t* d_ws, const TranscriptIo* dtio) {
+    const size_t per = agg_part_size(c, n), pb = agg_proof_bytes(a.k, a.rounds, a.nl, a.nn);
     unsigned first_super_m = 0, first_chunk = 0;
     for (size_t lo = 0; lo < n; lo += per) {
         const size_t m = n - lo < per ? n - lo : per;
@@ -824,122 +926,121 @@ static int agg_verify_parts(bppp_ctx* c, const uint8_t* label, size_t label_len,
             pio.states = dtio->states + (shared ? 0 : 203 * lo); pio.n_states = shared ? 1 : m;
             pio.states_out = dtio->states_out ? dtio->states_out + 203 * lo : nullptr;
         }
-        const int rc = agg_verify_device_impl(c, label, label_len, m, k, dim_nd, dim_np, d_com + 64 * k * lo, d_proofs + pb * lo, rounds, nl, nn,
-                                              d_acc + lo, d_st + lo, d_ws, rlc_seed, dtio ? &pio : nullptr);
+        const int rc = agg_verify_device_impl(c, a, m, d_ks ? d_ks + lo : nullptr, d_com + 64 * a.k * lo, d_proofs + pb * lo, d_acc + lo, d_st + lo,
+                                              d_ws, dtio ? &pio : nullptr);
         if (rc != BPPP_OK) return rc;
         if (lo == 0) { first_super_m = c->last_rlc_super_m; first_chunk = c->last_rlc_chunk; }
     }
     // "last_rlc_*": what the first part used (every part but the last has its size); (0, 0) where it ran the exact sum
-    if (rlc_seed) { c->last_rlc_super_m = first_super_m; c->last_rlc_chunk = first_chunk; }
+    if (a.rlc_seed) { c->last_rlc_super_m = first_super_m; c->last_rlc_chunk = first_chunk; }
     return BPPP_OK;
 }
 // what a call allocates in front of its parts besides its workspace; "last_rlc_*" reset first, so that a failing call reports nothing stale
 static int agg_verify_prepare(bppp_ctx* c, size_t per, const uint8_t* rlc_seed) {
-    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
+    rlc_report_reset(c, rlc_seed);
     const int rc = ensure_straus_capacity(c, per);
     if (rc != BPPP_OK) return rc;
     return rlc_seed && wnla_rlc_applies(per) ? wnla_rlc_prepare(c, per) : BPPP_OK;
 }
-// a call over device buffers, arguments checked and k > 1: asynchronous on the context's stream, the workspace in the grow-only d_gws
-static int agg_verify_device_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
-                                 const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
-                                 void* d_status, void* d_reject_count, const uint8_t* rlc_seed, const TranscriptIo* dtio = nullptr) {
+// the workspace of a call or part: the uniform one for k (k_max), its RLC buffers included, and behind it the l | n copies of a mixed call
+static size_t agg_mixed_ws_bytes(const bppp_ctx* c, size_t n, size_t k_max, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn,
+                                 bool rlc) {
+    return agg_verify_layout(c, n, k_max, dim_nd, dim_np, rounds, rlc).total + align16(n * 32 * (nl + nn));
+}
+static size_t agg_ws_bytes(const bppp_ctx* c, const AggCall& a, size_t n) {
+    const bool rlc = a.rlc_seed != nullptr;
+    return a.mixed ? agg_mixed_ws_bytes(c, n, a.k, a.dim_nd, a.dim_np, a.rounds, a.nl, a.nn, rlc)
+                   : agg_verify_layout(c, n, a.k, a.dim_nd, a.dim_np, a.rounds, rlc).total;
+}
+// a call over device buffers, arguments checked (and k > 1 unless it is a mixed call, which forwards nothing): asynchronous on the
+// context's stream, the workspace in the grow-only d_gws
+static int agg_verify_device_run(bppp_ctx* c, const AggCall& a, size_t n, const void* d_ks, const void* d_commitments, const void* d_proofs,
+                                 void* d_accept, void* d_status, void* d_reject_count, const TranscriptIo* dtio = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
-    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
-    if (n == 0) return BPPP_OK;
+    int rc = reset_reject_count(c, d_reject_count);
+    if (rc != BPPP_OK || n == 0) return rc;
     const size_t per = agg_part_size(c, n);
-    int rc = agg_verify_prepare(c, per, rlc_seed);
+    rc = agg_verify_prepare(c, per, a.rlc_seed);
     if (rc != BPPP_OK) return rc;
-    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_verify_layout(c, per, k, dim_nd, dim_np, rounds, rlc_seed != nullptr).total);
+    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_ws_bytes(c, a, per));
     if (rc != BPPP_OK) return rc;
-    rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, rounds, nl, nn,
-                          (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws, rlc_seed, dtio);
-    if (rc != BPPP_OK || !d_reject_count) return rc;
-    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
-    HIP_TRY(hipGetLastError());
-    return BPPP_OK;
+    rc = agg_verify_parts(c, a, n, (const uint8_t*)d_ks, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, (uint8_t*)d_accept,
+                          (int32_t*)d_status, c->d_gws, dtio);
+    return rc != BPPP_OK ? rc : launch_count_rejects(c, d_accept, n, d_reject_count);
 }
-static int agg_verify_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
-                                   const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn, void* d_accept,
-                                   void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
-    if (!c || !label_ok(label, label_len) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
-    const int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
-    if (rc != BPPP_OK) return rc;
-    if (k == 1)
-        return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
-                                         rlc_seed, d_reject_count);
-    return agg_verify_device_run(c, label, label_len, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
-                                 d_reject_count, rlc_seed);
+// what every aggregate entry point decides first: its buffers (ptrs_ok), the label, the shape and, of a mixed call, ks (host memory:
+// every count in [1, k]; device memory: only that it is given -- an instance outside the range is flagged where it is read)
+static int agg_call_check(const bppp_ctx* c, const AggCall& a, bool ptrs_ok, size_t n, const void* ks, int ks_on_device) {
+    if (!c || !label_ok(a.label, a.label_len) || !ptrs_ok) return BPPP_ERR_INVALID_ARG;
+    if (!a.mixed) return agg_shape_check((size_t)c->ng, (size_t)c->nh, a.k, a.dim_nd, a.dim_np, a.rounds, a.nl, a.nn);
+    return bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, a.k, (const uint8_t*)ks, ks_on_device, a.dim_nd, a.dim_np,
+                                                a.rounds, a.nl, a.nn);
 }
-static int agg_verify_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
-                                const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
-                                int32_t* status, const uint8_t* rlc_seed, const HostTranscripts* tx = nullptr) {
-    // tx (the _transcript form): the callers' transcripts in (1 or n), each instance's advanced transcript out; label null
-    if (!c || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
-    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+// device buffers: a uniform call of k = 1 IS the reciprocal verifier's; d_ks null unless the call is a mixed one
+static int agg_verify_device_entry(bppp_ctx* c, const AggCall& a, size_t n, const void* d_ks, const void* d_commitments, const void* d_proofs,
+                                   void* d_accept, void* d_status, void* d_reject_count) {
+    const int rc = agg_call_check(c, a, d_commitments && d_proofs && d_accept && d_status, n, d_ks, 1);
+    if (rc != BPPP_OK) return rc;
+    if (!a.mixed && a.k == 1)
+        return recip_verify_device_entry(c, a.label, a.label_len, n, a.dim_nd, a.dim_np, d_commitments, d_proofs, a.rounds, a.nl, a.nn, d_accept,
+                                         d_status, a.rlc_seed, d_reject_count);
+    return agg_verify_device_run(c, a, n, d_ks, d_commitments, d_proofs, d_accept, d_status, d_reject_count);
+}
+// host buffers, staged in the blob (ks, of a mixed call, behind the proofs -- the whole slots go up; the kernels read an instance's first
+// k_i commitments and proof_bytes(k_i) bytes only).  tx (the _transcript form, uniform calls only): the callers' transcripts in (1 or n),
+// each instance's advanced transcript out; label null
+static int agg_verify_host_entry(bppp_ctx* c, const AggCall& a, size_t n, const uint8_t* ks, const uint8_t* commitments, const uint8_t* proofs,
+                                 uint8_t* accept, int32_t* status, const HostTranscripts* tx = nullptr) {
+    int rc = agg_call_check(c, a, commitments && proofs && accept, n, ks, 0);
     if (rc != BPPP_OK) return rc;
     if (tx && (!tx->states || (tx->n_states != 1 && tx->n_states != n))) return BPPP_ERR_INVALID_ARG;
-    if (k == 1)
-        return recip_verify_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, tx, rlc_seed);
+    if (!a.mixed && a.k == 1)
+        return recip_verify_host_impl(c, a.label, a.label_len, n, a.dim_nd, a.dim_np, commitments, proofs, a.rounds, a.nl, a.nn, accept, status, tx,
+                                      a.rlc_seed);
     if (n == 0) return BPPP_OK;
     rc = check_host_transcripts(tx, n);
     if (rc != BPPP_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t per = agg_part_size(c, n);
-    rc = agg_verify_prepare(c, per, rlc_seed);
+    rc = agg_verify_prepare(c, per, a.rlc_seed);
     if (rc != BPPP_OK) return rc;
-    const size_t pb = agg_proof_bytes(k, rounds, nl, nn);
-    const size_t o_com = 0, o_pr = align16(n * k * 64), o_acc = align16(o_pr + n * pb), o_st = align16(o_acc + n), o_ti = align16(o_st + n * 4),
-                 o_to = align16(o_ti + (tx ? tx->n_states * 203 : 0)), o_ws = align16(o_to + (tx && tx->states_out ? n * 203 : 0)),
-                 total = o_ws + agg_verify_layout(c, per, k, dim_nd, dim_np, rounds, rlc_seed != nullptr).total;
-    WnlaBlob blob;
-    { const int rc_b = blob.take(c, total); if (rc_b != BPPP_OK) return rc_b; }
-    uint8_t* d = blob.d;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * k * 64, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_pr, proofs, n * pb, hipMemcpyHostToDevice, s));
-    TranscriptIo dtio = {nullptr, 0, nullptr, 0};
-    if (tx) {
-        HIP_TRY(hipMemcpyAsync(d + o_ti, tx->states, tx->n_states * 203, hipMemcpyHostToDevice, s));
-        dtio.states = d + o_ti; dtio.n_states = tx->n_states; dtio.states_out = tx->states_out ? d + o_to : nullptr;
-    }
-    rc = agg_verify_parts(c, label, label_len, n, k, dim_nd, dim_np, d + o_com, d + o_pr, rounds, nl, nn, d + o_acc, (int32_t*)(d + o_st), d + o_ws,
-                          rlc_seed, tx ? &dtio : nullptr);
+    HostStage hs;
+    rc = hs.begin(c, false, {{commitments, n * a.k * 64}, {proofs, n * agg_proof_bytes(a.k, a.rounds, a.nl, a.nn)}, {ks, a.mixed ? n : 0}}, n, tx,
+                  agg_ws_bytes(c, a, per));
     if (rc != BPPP_OK) return rc;
-    if (dtio.states_out) HIP_TRY(hipMemcpyAsync(tx->states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    rc = agg_verify_parts(c, a, n, a.mixed ? hs.in[2] : nullptr, hs.in[0], hs.in[1], hs.accept, hs.status, hs.tail, hs.dtio);
+    return hs.finish(rc, n, accept, status, tx);
 }
 size_t bppp_reciprocal_agg_proof_bytes(size_t k, size_t rounds, size_t nl, size_t nn) { return agg_proof_bytes(k, rounds, nl, nn); }
 int bppp_reciprocal_agg_verify_batch_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
                                             size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
                                             size_t nn, void* d_accept, void* d_status, void* d_reject_count) {
     CtxLock lock_(c);
-    return agg_verify_device_entry(c, label, label_len, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
-                                   d_reject_count, nullptr);
+    return agg_verify_device_entry(c, {label, label_len, k, false, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, nullptr, d_commitments, d_proofs,
+                                   d_accept, d_status, d_reject_count);
 }
 int bppp_reciprocal_agg_verify_batch_rlc_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
                                                 size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
                                                 size_t nn, void* d_accept, void* d_status, void* d_reject_count, const uint8_t seed[32]) {
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
-    return agg_verify_device_entry(c, label, label_len, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
-                                   d_reject_count, seed);
+    return agg_verify_device_entry(c, {label, label_len, k, false, dim_nd, dim_np, rounds, nl, nn, seed}, n, nullptr, d_commitments, d_proofs,
+                                   d_accept, d_status, d_reject_count);
 }
 int bppp_reciprocal_agg_verify_batch(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                                      const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
                                      int32_t* status) {
     CtxLock lock_(c);
-    return agg_verify_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr);
+    return agg_verify_host_entry(c, {label, label_len, k, false, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, nullptr, commitments, proofs,
+                                 accept, status);
 }
 int bppp_reciprocal_agg_verify_batch_rlc(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                                          const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
                                          int32_t* status, const uint8_t seed[32]) {
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
-    return agg_verify_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, seed);
+    return agg_verify_host_entry(c, {label, label_len, k, false, dim_nd, dim_np, rounds, nl, nn, seed}, n, nullptr, commitments, proofs,
+                                 accept, status);
 }
 // ---- the aggregate on the CALLER'S transcripts (`t: &mut Transcript`): the states in (1 shared or n), every instance's advanced
 //      transcript out; an instance flagged BPPP_ST_BAD_ENCODING gets its input state back.  No RLC form, as for the other protocols.
@@ -949,7 +1050,8 @@ int bppp_reciprocal_agg_verify_batch_transcript(bppp_ctx* c, size_t n, const uin
     CtxLock lock_(c);
     if (!states) return BPPP_ERR_INVALID_ARG;
     const HostTranscripts tx = {states, n_states, states_out};
-    return agg_verify_host_impl(c, nullptr, 0, n, k, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr, &tx);
+    return agg_verify_host_entry(c, {nullptr, 0, k, false, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, nullptr, commitments, proofs,
+                                 accept, status, &tx);
 }
 // k = 1 over device buffers: the reciprocal verifier on the caller's device states (the u64 kernels for the u64 shape), one launch chain
 // on the context's stream with the workspace in the grow-only buffer
@@ -963,8 +1065,8 @@ static int recip_verify_transcript_device(bppp_ctx* c, size_t n, const void* d_s
         return verify_device_impl(c, nullptr, 0, n, d_commitments, d_proofs, d_accept, d_status, nullptr, d_reject_count, nullptr, &tx);
     }
     HIP_TRY(hipSetDevice(c->device));
-    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
-    if (n == 0) return BPPP_OK;
+    rc = reset_reject_count(c, d_reject_count);
+    if (rc != BPPP_OK || n == 0) return rc;
     rc = ensure_straus_capacity(c, n);
     if (rc != BPPP_OK) return rc;
     rc = ensure_buffer(c, c->d_gws, c->gws_bytes, recip_verify_ws_bytes(c, n, dim_nd, dim_np, rounds, false));
@@ -972,113 +1074,26 @@ static int recip_verify_transcript_device(bppp_ctx* c, size_t n, const void* d_s
     const TranscriptIo dtio = {(const uint8_t*)d_states, n_states, (uint8_t*)d_states_out, 0};
     rc = recip_verify_device_impl(c, nullptr, 0, n, dim_nd, dim_np, (const uint8_t*)d_commitments, (const uint8_t*)d_proofs, rounds, nl, nn,
                                   (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws, &dtio, nullptr);
-    if (rc != BPPP_OK || !d_reject_count) return rc;
-    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
-    HIP_TRY(hipGetLastError());
-    return BPPP_OK;
+    return rc != BPPP_OK ? rc : launch_count_rejects(c, d_accept, n, d_reject_count);
 }
 // device buffers: the states cannot be read here, so a state merlin cannot be in flags its instance (BPPP_ST_BAD_ENCODING) on the device
 int bppp_reciprocal_agg_verify_batch_transcript_device(bppp_ctx* c, size_t n, const void* d_states, size_t n_states, size_t k, size_t dim_nd,
                                                        size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl,
                                                        size_t nn, void* d_accept, void* d_status, void* d_reject_count, void* d_states_out) {
     CtxLock lock_(c);
-    if (!c || !d_states || (n_states != 1 && n_states != n) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
-    const int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+    const AggCall a = {nullptr, 0, k, false, dim_nd, dim_np, rounds, nl, nn, nullptr};
+    const int rc = agg_call_check(c, a, d_states && (n_states == 1 || n_states == n) && d_commitments && d_proofs && d_accept && d_status, n, nullptr, 1);
     if (rc != BPPP_OK) return rc;
     if (k == 1)
         return recip_verify_transcript_device(c, n, d_states, n_states, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
                                               d_reject_count, d_states_out);
     const TranscriptIo dtio = {(const uint8_t*)d_states, n_states, (uint8_t*)d_states_out, 0};
-    return agg_verify_device_run(c, nullptr, 0, n, k, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status, d_reject_count,
-                                 nullptr, &dtio);
+    return agg_verify_device_run(c, a, n, nullptr, d_commitments, d_proofs, d_accept, d_status, d_reject_count, &dtio);
 }
 // ---- aggregates of MIXED value counts in one batch (agg_mixed_core.h): instance i has ks[i] values in slots laid out by k_max.  Label
-//      transcripts; the final sum exact or in RLC mode (a seed given).  The launch sequence is agg_verify_device_impl's on the same
-//      plan, with phase 1 and the variable-base half of C0 on every instance's own k (k_agg_mixed.hip) and the WNLA stage reading l | n
-//      out of phase 1's copy; k_i = 1 runs on these kernels too.  The workspace is the uniform one for k_max (its RLC buffers included)
-//      with the l | n copies behind it.  The wire (SEC1) forms are with the other verifiers' at the end of this file.
-static size_t agg_mixed_ws_bytes(const bppp_ctx* c, size_t n, size_t k_max, size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn,
-                                 bool rlc) {
-    return agg_verify_layout(c, n, k_max, dim_nd, dim_np, rounds, rlc).total + align16(n * 32 * (nl + nn));
-}
-// rlc_seed: as agg_verify_device_impl's.  The RLC kernels read the final scalars, the commitments after the last round and the
-// statuses out of the workspace, never the proof; l | n are read by the stages before them through w.proof_l / proof_n (the copies)
-static int agg_mixed_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, const uint8_t* d_ks, size_t dim_nd,
-                                 size_t dim_np, const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn,
-                                 uint8_t* d_acc, int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed) {
-    const GenericPlan plan = plan_generic(GENERIC_FORM_AGGREGATE, n, rounds, generic_knobs_of(c), n, 1, 4 + k);
-    const bool rlc = rlc_seed && wnla_rlc_applies(n);
-    const AggVerifyLayout o = agg_verify_layout(c, n, k, dim_nd, dim_np, rounds, rlc);
-    uint8_t* d = d_ws;
-    hipStream_t s = c->stream;
-    AggMixedWs m;
-    std::memset(&m, 0, sizeof m);
-    AggWs& r = m.w;
-    r.N = n; r.k = (int)k; r.nd = (int)dim_nd; r.np = (int)dim_np; r.rounds = (int)rounds; r.nl = (int)nl; r.nn = (int)nn;
-    r.NG = c->ng; r.NH = c->nh; r.proof_bytes = agg_proof_bytes(k, rounds, nl, nn);
-    r.commitments = d_com; r.proofs = d_proofs; r.status = d_st; r.tstate = (u32*)(d + o.ts);
-    r.sc0 = (u32*)(d + o.sc0); r.pts = (u32*)(d + o.pts); r.acc = (u32*)(d + o.a); r.pfix = (u32*)(d + o.pf); r.inv = (u32*)(d + o.inv);
-    r.vsum = (u32*)(d + o.vs);
-    r.straus = c->d_straus;
-    r.wn_commit = d + o.wc; r.wn_c = d + o.wcv; r.wn_rho = d + o.rho; r.wn_mu = d + o.mu;
-    r.fb = fb_table_of(c, n);
-    t_new(r.base, label, (u32)label_len);
-    m.ks = d_ks; m.ln = d + o.total;
-    WnlaWs w = wnla_ws_continuing(c, r, 4 + k, nl, nn, d_acc, (u32*)(d + o.ys), (u32*)(d + o.tab), (u32*)(d + o.msc));
-    w.proof_l = m.ln; w.proof_n = m.ln + 32 * nl;       // (r and x sit at one offset for every k_i and are read in place)
-    w.stride_l = w.stride_n = 32 * (nl + nn);
-    const unsigned blocks = blocks_of(n);
-    int rc;
-    rc = wnla_fast_setup(c, w, plan, 4 + k);
-    if (rc != BPPP_OK) return rc;
-    r.atab = w.atab; r.tscr = w.tscr; r.atab_first = wnla_atab_first(plan, rounds);
-    const bool beside = plan.beside;
-    hipStream_t a = beside ? c->aux_stream : s;
-    const int G = plan.p1_group;
-    c->last_generic_form = plan.code();
-    if (beside) {
-        HIP_TRY(hipEventRecord(c->ev_tab, s));               // (the call's inputs are ready on s)
-        HIP_TRY(hipStreamWaitEvent(a, c->ev_tab, 0));
-        GLAUNCH(a, K_WNLA_TABLES, launch_wnla_tables(w, plan.tab_parts, n, blocks, a));
-    }
-    const unsigned p1_blocks = G > 1 ? (unsigned)(((size_t)G * n + BPPP_BLOCK - 1) / BPPP_BLOCK) : blocks;
-    if (G > 1) GLAUNCH(s, K_AGG_PHASE1, k_agg_mixed_phase1_grp<<<p1_blocks, BPPP_BLOCK, 0, s>>>(m, G));
-    else GLAUNCH(s, K_AGG_PHASE1, k_agg_mixed_phase1<<<blocks, BPPP_BLOCK, 0, s>>>(m));
-    if (beside) {
-        HIP_TRY(hipEventRecord(c->ev_fork, s));
-        HIP_TRY(hipStreamWaitEvent(a, c->ev_fork, 0));
-    }
-    // the uniform kernels over 1 + k_max dim_nd bases: the scalars behind an instance's k_i dim_nd are zero
-    if (plan.fb == GENERIC_FB_ONE_LANE) GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed_l1<<<fb1_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
-    else if (plan.fb == GENERIC_FB_WAVEFRONT) GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed_l64<<<fb64_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
-    else GLAUNCH(s, K_AGG_C0_FIXED, k_agg_c0_fixed<<<fb_blocks_of(n), BPPP_FB_BLOCK, 0, s>>>(r));
-    GLAUNCH(a, K_AGG_C0_VAR, {
-        if (plan.fast) k_agg_mixed_c0_tables<<<blocks, BPPP_BLOCK, 0, a>>>(m);
-        k_agg_mixed_c0_var<<<blocks, BPPP_BLOCK, 0, a>>>(m);
-    });
-    if (beside) {
-        HIP_TRY(hipEventRecord(c->ev_join, a));
-        HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
-    }
-    GLAUNCH(s, K_AGG_C0_FINISH, k_agg_c0_finish<<<blocks, BPPP_BLOCK, 0, s>>>(r));
-    return wnla_verify_stage(c, w, plan, s, beside, rlc ? rlc_seed : nullptr, d, o.rlc);
-}
-// parts of max_batch over one workspace, each with its own slice of ks; "last_rlc_*" as agg_verify_parts reports them
-static int agg_mixed_parts(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, const uint8_t* d_ks, size_t dim_nd,
-                           size_t dim_np, const uint8_t* d_com, const uint8_t* d_proofs, size_t rounds, size_t nl, size_t nn, uint8_t* d_acc,
-                           int32_t* d_st, uint8_t* d_ws, const uint8_t* rlc_seed) {
-    const size_t per = agg_part_size(c, n), pb = agg_proof_bytes(k, rounds, nl, nn);
-    unsigned first_super_m = 0, first_chunk = 0;
-    for (size_t lo = 0; lo < n; lo += per) {
-        const size_t m = n - lo < per ? n - lo : per;
-        const int rc = agg_mixed_device_impl(c, label, label_len, m, k, d_ks + lo, dim_nd, dim_np, d_com + 64 * k * lo, d_proofs + pb * lo, rounds,
-                                             nl, nn, d_acc + lo, d_st + lo, d_ws, rlc_seed);
-        if (rc != BPPP_OK) return rc;
-        if (lo == 0) { first_super_m = c->last_rlc_super_m; first_chunk = c->last_rlc_chunk; }
-    }
-    if (rlc_seed) { c->last_rlc_super_m = first_super_m; c->last_rlc_chunk = first_chunk; }
-    return BPPP_OK;
-}
+//      transcripts; the final sum exact or in RLC mode (a seed given).  The launch chain, the parts and the runs are the uniform
+//      aggregate's on an AggCall that says `mixed` (agg_verify_device_impl and what follows it); only the argument check is the
+//      mixed calls' own, and nothing is forwarded.  The wire (SEC1) forms are with the other verifiers' at the end of this file.
 // what the two mixed calls decide about their arguments besides the NULL checks of the buffers, on a context of ng | nh generators in
 // g_vec || g_vec_ | h_vec || h_vec_; pure, so that it can be asked without a context or a device.  ks_on_device: ks is only checked
 // for NULL (the device form: an instance outside [1, k_max] is flagged where it is read)
@@ -1091,40 +1106,12 @@ int bppp_reciprocal_agg_mixed_check_args(size_t ng, size_t nh, size_t n, size_t 
         if (ks[i] == 0 || ks[i] > k_max) return BPPP_ERR_INVALID_ARG;
     return BPPP_OK;
 }
-// a call over device buffers, arguments checked: asynchronous on the context's stream, the workspace in the grow-only d_gws
-static int agg_mixed_device_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks, size_t dim_nd,
-                                size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn,
-                                void* d_accept, void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
-    HIP_TRY(hipSetDevice(c->device));
-    if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
-    if (n == 0) return BPPP_OK;
-    const size_t per = agg_part_size(c, n);
-    int rc = agg_verify_prepare(c, per, rlc_seed);
-    if (rc != BPPP_OK) return rc;
-    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, agg_mixed_ws_bytes(c, per, k_max, dim_nd, dim_np, rounds, nl, nn, rlc_seed != nullptr));
-    if (rc != BPPP_OK) return rc;
-    rc = agg_mixed_parts(c, label, label_len, n, k_max, (const uint8_t*)d_ks, dim_nd, dim_np, (const uint8_t*)d_commitments,
-                         (const uint8_t*)d_proofs, rounds, nl, nn, (uint8_t*)d_accept, (int32_t*)d_status, c->d_gws, rlc_seed);
-    if (rc != BPPP_OK || !d_reject_count) return rc;
-    k_count_rejects<<<(unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, 0, c->stream>>>((const uint8_t*)d_accept, n, (int*)d_reject_count);
-    HIP_TRY(hipGetLastError());
-    return BPPP_OK;
-}
-static int agg_mixed_device_entry(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks, size_t dim_nd,
-                                  size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds, size_t nl, size_t nn,
-                                  void* d_accept, void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
-    if (!c || !label_ok(label, label_len) || !d_commitments || !d_proofs || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
-    const int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, (const uint8_t*)d_ks, 1, dim_nd, dim_np, rounds, nl, nn);
-    if (rc != BPPP_OK) return rc;
-    return agg_mixed_device_run(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
-                                d_reject_count, rlc_seed);
-}
 int bppp_reciprocal_agg_verify_batch_mixed_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks,
                                                   size_t dim_nd, size_t dim_np, const void* d_commitments, const void* d_proofs, size_t rounds,
                                                   size_t nl, size_t nn, void* d_accept, void* d_status, void* d_reject_count) {
     CtxLock lock_(c);
-    return agg_mixed_device_entry(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
-                                  d_reject_count, nullptr);
+    return agg_verify_device_entry(c, {label, label_len, k_max, true, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, d_ks, d_commitments, d_proofs,
+                                   d_accept, d_status, d_reject_count);
 }
 int bppp_reciprocal_agg_verify_batch_mixed_rlc_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
                                                       const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments,
@@ -1132,52 +1119,23 @@ int bppp_reciprocal_agg_verify_batch_mixed_rlc_device(bppp_ctx* c, const uint8_t
                                                       void* d_reject_count, const uint8_t seed[32]) {
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
-    return agg_mixed_device_entry(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments, d_proofs, rounds, nl, nn, d_accept, d_status,
-                                  d_reject_count, seed);
-}
-static int agg_mixed_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks, size_t dim_nd,
-                               size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds, size_t nl, size_t nn,
-                               uint8_t* accept, int32_t* status, const uint8_t* rlc_seed) {
-    if (!c || !label_ok(label, label_len) || !commitments || !proofs || !accept) return BPPP_ERR_INVALID_ARG;
-    int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, ks, 0, dim_nd, dim_np, rounds, nl, nn);
-    if (rc != BPPP_OK) return rc;
-    if (n == 0) return BPPP_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t per = agg_part_size(c, n);
-    rc = agg_verify_prepare(c, per, rlc_seed);
-    if (rc != BPPP_OK) return rc;
-    const size_t pb = agg_proof_bytes(k_max, rounds, nl, nn);
-    const size_t o_com = 0, o_pr = align16(n * k_max * 64), o_ks = align16(o_pr + n * pb), o_acc = align16(o_ks + n), o_st = align16(o_acc + n),
-                 o_ws = align16(o_st + n * 4),
-                 total = o_ws + agg_mixed_ws_bytes(c, per, k_max, dim_nd, dim_np, rounds, nl, nn, rlc_seed != nullptr);
-    WnlaBlob blob;
-    { const int rc_b = blob.take(c, total); if (rc_b != BPPP_OK) return rc_b; }
-    uint8_t* d = blob.d;
-    hipStream_t s = c->stream;
-    // (the whole slots go up; the kernels read an instance's first k_i commitments and proof_bytes(k_i) bytes only)
-    HIP_TRY(hipMemcpyAsync(d + o_com, commitments, n * k_max * 64, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_pr, proofs, n * pb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_ks, ks, n, hipMemcpyHostToDevice, s));
-    rc = agg_mixed_parts(c, label, label_len, n, k_max, d + o_ks, dim_nd, dim_np, d + o_com, d + o_pr, rounds, nl, nn, d + o_acc,
-                         (int32_t*)(d + o_st), d + o_ws, rlc_seed);
-    if (rc != BPPP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(accept, d + o_acc, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_st, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    return agg_verify_device_entry(c, {label, label_len, k_max, true, dim_nd, dim_np, rounds, nl, nn, seed}, n, d_ks, d_commitments, d_proofs,
+                                   d_accept, d_status, d_reject_count);
 }
 int bppp_reciprocal_agg_verify_batch_mixed(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
                                            size_t dim_nd, size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds,
                                            size_t nl, size_t nn, uint8_t* accept, int32_t* status) {
     CtxLock lock_(c);
-    return agg_mixed_host_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, nullptr);
+    return agg_verify_host_entry(c, {label, label_len, k_max, true, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, ks, commitments, proofs,
+                                 accept, status);
 }
 int bppp_reciprocal_agg_verify_batch_mixed_rlc(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
                                                size_t dim_nd, size_t dim_np, const uint8_t* commitments, const uint8_t* proofs, size_t rounds,
                                                size_t nl, size_t nn, uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
-    return agg_mixed_host_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, commitments, proofs, rounds, nl, nn, accept, status, seed);
+    return agg_verify_host_entry(c, {label, label_len, k_max, true, dim_nd, dim_np, rounds, nl, nn, seed}, n, ks, commitments, proofs,
+                                 accept, status);
 }
 
 // ---------------------------------------------------------------- generic ArithmeticCircuit (circuit.rs:95-256)
@@ -1982,23 +1940,16 @@ int bppp_reciprocal_prove_batch_transcript(bppp_ctx* c, size_t n, const uint8_t*
 // provers decompress their input commitments the same way and compress their proofs on the device (k_wire_compress) before the copy
 // back.  The host-buffer forms stage the 33-byte bytes in the same buffer, in front of the expanded form.
 // ---- reciprocal
-static size_t recip_sec1_exp_bytes(size_t n, size_t rounds, size_t nl, size_t nn) {
-    return align16(n * 64) + n * (64 * (5 + 2 * rounds) + 32 * (nl + nn));
-}
-// arguments checked; d_exp: recip_sec1_exp_bytes in the wire buffer
+// arguments checked; d_exp: recip_wire_exp().bytes() in the wire buffer
 static int recip_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np, const uint8_t* d_com33,
                           const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status, uint8_t* d_exp,
                           const uint8_t* rlc_seed, void* d_reject_count = nullptr) {
-    const size_t P = 5 + 2 * rounds, S = nl + nn, o_p = align16(n * 64);
-    WireMap m;
-    wire_map_init(m, n);
-    wire_map_add(m, false, d_com33, 33, d_exp, 64, 1);
-    wire_add_proof(m, d_proofs33, d_exp + o_p, P, S);
+    const WireExp e = recip_wire_exp(n, rounds, nl, nn);
     // on c->stream: a call split into parts forks them from c->stream behind this (ev_twin_fork in recip_verify_device_entry)
-    int rc = wire_launch(m, true, c->stream);
+    const int rc = e.launch(d_com33, d_proofs33, d_exp, c->stream);
     if (rc != BPPP_OK) return rc;
-    return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, rlc_seed,
-                                     d_reject_count);
+    return recip_verify_device_entry(c, label, label_len, n, dim_nd, dim_np, d_exp, d_exp + e.o_proofs(), rounds, nl, nn, d_accept, d_status,
+                                     rlc_seed, d_reject_count);
 }
 // rlc_seed (the *_rlc_sec1 entry points of all three verifiers): the expansion is the same launch; what runs behind it is the 64-byte
 // RLC twin's pipeline on the expanded bytes, so a flagged instance is kept out of the weighted sums exactly as there
@@ -2012,13 +1963,12 @@ static int recip_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t labe
     if (n == 0) {      // (nothing to verify at either shape; the counter, where one is given, reads zero as after any other call)
         if (!d_reject_count) return BPPP_OK;
         HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
-        return BPPP_OK;
+        return reset_reject_count(c, d_reject_count);
     }
     if (recip_is_u64_shape(c, dim_nd, dim_np, rounds, nl, nn))      // the u64 wire form is the same 33 + 525 bytes: its own expand kernel
         return verify_sec1_device_impl(c, label, label_len, n, d_commitments33, d_proofs33, d_accept, d_status, nullptr, d_reject_count, rlc_seed);
     HIP_TRY(hipSetDevice(c->device));
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, recip_sec1_exp_bytes(n, rounds, nl, nn));
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, recip_wire_exp(n, rounds, nl, nn).bytes());
     if (rc != BPPP_OK) return rc;
     return recip_sec1_run(c, label, label_len, n, dim_nd, dim_np, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, rounds, nl, nn,
                           d_accept, d_status, c->d_wire, rlc_seed, d_reject_count);
@@ -2047,22 +1997,12 @@ static int recip_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_
         return rlc_seed ? bppp_u64_verify_batch_rlc_sec1(c, label, label_len, n, commitments33, proofs33, accept, status, rlc_seed)
                         : bppp_u64_verify_batch_sec1(c, label, label_len, n, commitments33, proofs33, accept, status);
     HIP_TRY(hipSetDevice(c->device));
-    const size_t pb = wire_proof_bytes(5 + 2 * rounds, nl + nn);
-    const size_t o_c = 0, o_p = align16(n * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_e = align16(o_s + n * 4),
-                 total = o_e + recip_sec1_exp_bytes(n, rounds, nl, nn);
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
+    const WireExp e = recip_wire_exp(n, rounds, nl, nn);
+    HostStage hs;
+    rc = hs.begin(c, true, {{commitments33, e.com33_bytes()}, {proofs33, e.proofs33_bytes()}}, n, nullptr, e.bytes());
     if (rc != BPPP_OK) return rc;
-    WireQuiesce guard{c};
-    uint8_t* d = c->d_wire;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * 33, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
-    rc = recip_sec1_run(c, label, label_len, n, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, d + o_e, rlc_seed);
-    if (rc != BPPP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    rc = recip_sec1_run(c, label, label_len, n, dim_nd, dim_np, hs.in[0], hs.in[1], rounds, nl, nn, hs.accept, hs.status, hs.tail, rlc_seed);
+    return hs.finish(rc, n, accept, status, nullptr);
 }
 int bppp_reciprocal_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t dim_nd, size_t dim_np,
                                       const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
@@ -2096,83 +2036,63 @@ int recip_verify_sec1_transcript_host(bppp_ctx* c, size_t n, const uint8_t* stat
     HIP_TRY(hipSetDevice(c->device));
     rc = ensure_straus_capacity(c, n);
     if (rc != BPPP_OK) return rc;
-    const size_t P = 5 + 2 * rounds, S = nl + nn, pb = wire_proof_bytes(P, S), e_p = align16(n * 64);
-    const size_t o_c = 0, o_p = align16(n * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_ti = align16(o_s + n * 4),
-                 o_to = align16(o_ti + n_states * 203), o_e = align16(o_to + (states_out ? n * 203 : 0)),
-                 total = o_e + recip_sec1_exp_bytes(n, rounds, nl, nn);
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
+    const WireExp e = recip_wire_exp(n, rounds, nl, nn);
+    HostStage hs;
+    rc = hs.begin(c, true, {{commitments33, e.com33_bytes()}, {proofs33, e.proofs33_bytes()}}, n, &tx, e.bytes(),
+                  recip_verify_ws_bytes(c, n, dim_nd, dim_np, rounds, false));
     if (rc != BPPP_OK) return rc;
-    rc = ensure_buffer(c, c->d_gws, c->gws_bytes, recip_verify_ws_bytes(c, n, dim_nd, dim_np, rounds, false));
+    rc = e.launch(hs.in[0], hs.in[1], hs.tail, c->stream);
     if (rc != BPPP_OK) return rc;
-    WireQuiesce guard{c};
-    uint8_t* d = c->d_wire;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * 33, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_ti, states, n_states * 203, hipMemcpyHostToDevice, s));
-    WireMap m;
-    wire_map_init(m, n);
-    wire_map_add(m, false, d + o_c, 33, d + o_e, 64, 1);
-    wire_add_proof(m, d + o_p, d + o_e + e_p, P, S);
-    rc = wire_launch(m, true, s);
-    if (rc != BPPP_OK) return rc;
-    const TranscriptIo dtio = {d + o_ti, n_states, states_out ? d + o_to : nullptr, 0};
-    rc = recip_verify_device_impl(c, nullptr, 0, n, dim_nd, dim_np, d + o_e, d + o_e + e_p, rounds, nl, nn, d + o_a, (int32_t*)(d + o_s),
-                                  c->d_gws, &dtio, nullptr);
-    if (rc != BPPP_OK) return rc;
-    if (states_out) HIP_TRY(hipMemcpyAsync(states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    rc = recip_verify_device_impl(c, nullptr, 0, n, dim_nd, dim_np, hs.tail, hs.tail + e.o_proofs(), rounds, nl, nn, hs.accept, hs.status,
+                                  c->d_gws, hs.dtio, nullptr);
+    return hs.finish(rc, n, accept, status, &tx);
 }
 
 // ---- aggregate: n x k commitments and the proof c_l c_r c_o c_s | r | x | R_0 .. R_{k-1} | l | n, 4 + 2 rounds + k points in front of
 //      the scalars.  One expansion over the whole call on the context's stream, in front of the max_batch parts; k = 1 is the
-//      reciprocal wire form and goes to its entry points
-static size_t agg_sec1_exp_bytes(size_t n, size_t k, size_t rounds, size_t nl, size_t nn) {
-    return align16(n * k * 64) + n * agg_proof_bytes(k, rounds, nl, nn);
-}
-// arguments checked, k > 1; d_exp: agg_sec1_exp_bytes in the wire buffer
-static int agg_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
-                        const uint8_t* d_com33, const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept, void* d_status,
-                        void* d_reject_count, uint8_t* d_exp, const uint8_t* rlc_seed, const TranscriptIo* dtio = nullptr) {
-    const size_t o_p = align16(n * k * 64);
-    WireMap m;
-    wire_map_init(m, n);
-    wire_map_add(m, false, d_com33, 33 * k, d_exp, 64 * k, k);
-    wire_add_proof(m, d_proofs33, d_exp + o_p, 4 + 2 * rounds + k, nl + nn);
-    const int rc = wire_launch(m, true, c->stream);
-    if (rc != BPPP_OK) return rc;
-    return agg_verify_device_run(c, label, label_len, n, k, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status,
-                                 d_reject_count, rlc_seed, dtio);
-}
-static int agg_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
-                                const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
-                                void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
-    if (!c || !label_ok(label, label_len) || !d_commitments33 || !d_proofs33 || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
-    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
-    if (rc != BPPP_OK) return rc;
-    if (k == 1)
-        return recip_sec1_device_impl(c, label, label_len, n, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status,
-                                      rlc_seed, d_reject_count);
-    HIP_TRY(hipSetDevice(c->device));
-    if (n == 0) {
-        if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
-        return BPPP_OK;
+//      reciprocal wire form and goes to its entry points.
+//      Aggregates of MIXED value counts (d_ks / ks given): 33-byte slots laid out by k_max, instance i in the uniform wire layout for
+//      ks[i] in front of its slots, expanded by k_wire_expand_mixed (wire_mixed_core.h); the mixed chain then runs on the expanded
+//      slots.  Nothing is forwarded: k_max = 1 runs here too
+// arguments checked; d_exp: agg_wire_exp(n, k).bytes() in the wire buffer
+static int agg_sec1_run(bppp_ctx* c, const AggCall& a, size_t n, const uint8_t* d_ks, const uint8_t* d_com33, const uint8_t* d_proofs33,
+                        void* d_accept, void* d_status, void* d_reject_count, uint8_t* d_exp, const TranscriptIo* dtio = nullptr) {
+    const WireExp e = agg_wire_exp(n, a.k, a.rounds, a.nl, a.nn);
+    if (a.mixed) {
+        WireMixed m;
+        m.com33 = d_com33; m.proofs33 = d_proofs33; m.com64 = d_exp; m.proofs64 = d_exp + e.o_proofs(); m.ks = d_ks;
+        m.n = n; m.k_max = (u32)a.k; m.rounds = (u32)a.rounds; m.ns = (u32)(a.nl + a.nn);
+        k_wire_expand_mixed<<<(unsigned)((wire_mixed_lanes(m) + 255) / 256), 256, 0, c->stream>>>(m);
+        HIP_TRY(hipGetLastError());
+    } else {
+        const int rc = e.launch(d_com33, d_proofs33, d_exp, c->stream);
+        if (rc != BPPP_OK) return rc;
     }
-    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, agg_sec1_exp_bytes(n, k, rounds, nl, nn));
+    return agg_verify_device_run(c, a, n, d_ks, d_exp, d_exp + e.o_proofs(), d_accept, d_status, d_reject_count, dtio);
+}
+// device buffers.  "last_rlc_*" are reset here, in front of agg_verify_prepare's own reset: the wire buffer's growth comes first and can
+// fail, and such a call reports (0, 0) too
+static int agg_sec1_device_entry(bppp_ctx* c, const AggCall& a, size_t n, const void* d_ks, const void* d_commitments33, const void* d_proofs33,
+                                 void* d_accept, void* d_status, void* d_reject_count) {
+    int rc = agg_call_check(c, a, d_commitments33 && d_proofs33 && d_accept && d_status, n, d_ks, 1);
     if (rc != BPPP_OK) return rc;
-    return agg_sec1_run(c, label, label_len, n, k, dim_nd, dim_np, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, rounds, nl, nn,
-                        d_accept, d_status, d_reject_count, c->d_wire, rlc_seed);
+    if (!a.mixed && a.k == 1)
+        return recip_sec1_device_impl(c, a.label, a.label_len, n, a.dim_nd, a.dim_np, d_commitments33, d_proofs33, a.rounds, a.nl, a.nn, d_accept,
+                                      d_status, a.rlc_seed, d_reject_count);
+    HIP_TRY(hipSetDevice(c->device));
+    if (n == 0) return reset_reject_count(c, d_reject_count);
+    rlc_report_reset(c, a.rlc_seed);
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, agg_wire_exp(n, a.k, a.rounds, a.nl, a.nn).bytes());
+    if (rc != BPPP_OK) return rc;
+    return agg_sec1_run(c, a, n, (const uint8_t*)d_ks, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, d_accept, d_status,
+                        d_reject_count, c->d_wire);
 }
 int bppp_reciprocal_agg_verify_batch_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
                                                  size_t dim_np, const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl,
                                                  size_t nn, void* d_accept, void* d_status, void* d_reject_count) {
     CtxLock lock_(c);
-    return agg_sec1_device_impl(c, label, label_len, n, k, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status,
-                                d_reject_count, nullptr);
+    return agg_sec1_device_entry(c, {label, label_len, k, false, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, nullptr, d_commitments33, d_proofs33,
+                                 d_accept, d_status, d_reject_count);
 }
 int bppp_reciprocal_agg_verify_batch_rlc_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
                                                      size_t dim_np, const void* d_commitments33, const void* d_proofs33, size_t rounds,
@@ -2180,60 +2100,60 @@ int bppp_reciprocal_agg_verify_batch_rlc_sec1_device(bppp_ctx* c, const uint8_t*
                                                      const uint8_t seed[32]) {
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
-    return agg_sec1_device_impl(c, label, label_len, n, k, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept, d_status,
-                                d_reject_count, seed);
+    return agg_sec1_device_entry(c, {label, label_len, k, false, dim_nd, dim_np, rounds, nl, nn, seed}, n, nullptr, d_commitments33, d_proofs33,
+                                 d_accept, d_status, d_reject_count);
 }
-// host buffers: the 33-byte input staged in the wire buffer too, in front of accept, status and the expanded form
-static int agg_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
-                              const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
-                              int32_t* status, const uint8_t* rlc_seed, const HostTranscripts* tx = nullptr) {
-    // tx (the _transcript_sec1 form): as agg_verify_host_impl's; the states staged in the wire buffer with the rest
-    if (!c || !label_ok(label, label_len) || !commitments33 || !proofs33 || !accept) return BPPP_ERR_INVALID_ARG;
-    int rc = agg_verify_check_args(c, k, dim_nd, dim_np, rounds, nl, nn);
+int bppp_reciprocal_agg_verify_batch_mixed_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                       const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments33,
+                                                       const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                                       void* d_status, void* d_reject_count) {
+    CtxLock lock_(c);
+    return agg_sec1_device_entry(c, {label, label_len, k_max, true, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, d_ks, d_commitments33, d_proofs33,
+                                 d_accept, d_status, d_reject_count);
+}
+int bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                           const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments33,
+                                                           const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
+                                                           void* d_status, void* d_reject_count, const uint8_t seed[32]) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_sec1_device_entry(c, {label, label_len, k_max, true, dim_nd, dim_np, rounds, nl, nn, seed}, n, d_ks, d_commitments33, d_proofs33,
+                                 d_accept, d_status, d_reject_count);
+}
+// host buffers: the 33-byte input (ks too, of a mixed call, whose whole slots go up: the expansion reads an instance's first k_i
+// commitments and S(k_i) bytes only) staged in the wire buffer, in front of accept, status, the states and the expanded form
+// tx (the _transcript_sec1 form, uniform calls only): as agg_verify_host_entry's
+static int agg_sec1_host_entry(bppp_ctx* c, const AggCall& a, size_t n, const uint8_t* ks, const uint8_t* commitments33, const uint8_t* proofs33,
+                               uint8_t* accept, int32_t* status, const HostTranscripts* tx = nullptr) {
+    int rc = agg_call_check(c, a, commitments33 && proofs33 && accept, n, ks, 0);
     if (rc != BPPP_OK) return rc;
     if (tx && (!tx->states || (tx->n_states != 1 && tx->n_states != n))) return BPPP_ERR_INVALID_ARG;
-    if (k == 1) {
+    if (!a.mixed && a.k == 1) {
         if (tx)
-            return recip_verify_sec1_transcript_host(c, n, tx->states, tx->n_states, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept,
-                                                     status, tx->states_out);
-        return recip_sec1_host_impl(c, label, label_len, n, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, rlc_seed);
+            return recip_verify_sec1_transcript_host(c, n, tx->states, tx->n_states, a.dim_nd, a.dim_np, commitments33, proofs33, a.rounds, a.nl, a.nn,
+                                                     accept, status, tx->states_out);
+        return recip_sec1_host_impl(c, a.label, a.label_len, n, a.dim_nd, a.dim_np, commitments33, proofs33, a.rounds, a.nl, a.nn, accept, status,
+                                    a.rlc_seed);
     }
     if (n == 0) return BPPP_OK;
     rc = check_host_transcripts(tx, n);
     if (rc != BPPP_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
-    const size_t pb = wire_proof_bytes(4 + 2 * rounds + k, nl + nn);
-    const size_t o_c = 0, o_p = align16(n * k * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_ti = align16(o_s + n * 4),
-                 o_to = align16(o_ti + (tx ? tx->n_states * 203 : 0)), o_e = align16(o_to + (tx && tx->states_out ? n * 203 : 0)),
-                 total = o_e + agg_sec1_exp_bytes(n, k, rounds, nl, nn);
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
+    rlc_report_reset(c, a.rlc_seed);      // (as agg_sec1_device_entry's)
+    const WireExp e = agg_wire_exp(n, a.k, a.rounds, a.nl, a.nn);
+    HostStage hs;
+    rc = hs.begin(c, true, {{commitments33, e.com33_bytes()}, {proofs33, e.proofs33_bytes()}, {ks, a.mixed ? n : 0}}, n, tx, e.bytes());
     if (rc != BPPP_OK) return rc;
-    WireQuiesce guard{c};
-    uint8_t* d = c->d_wire;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * k * 33, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
-    TranscriptIo dtio = {nullptr, 0, nullptr, 0};
-    if (tx) {
-        HIP_TRY(hipMemcpyAsync(d + o_ti, tx->states, tx->n_states * 203, hipMemcpyHostToDevice, s));
-        dtio.states = d + o_ti; dtio.n_states = tx->n_states; dtio.states_out = tx->states_out ? d + o_to : nullptr;
-    }
-    rc = agg_sec1_run(c, label, label_len, n, k, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, nullptr, d + o_e, rlc_seed,
-                      tx ? &dtio : nullptr);
-    if (rc != BPPP_OK) return rc;
-    if (dtio.states_out) HIP_TRY(hipMemcpyAsync(tx->states_out, d + o_to, n * 203, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    rc = agg_sec1_run(c, a, n, a.mixed ? hs.in[2] : nullptr, hs.in[0], hs.in[1], hs.accept, hs.status, nullptr, hs.tail, hs.dtio);
+    return hs.finish(rc, n, accept, status, tx);
 }
 size_t bppp_reciprocal_agg_proof_sec1_bytes(size_t k, size_t rounds, size_t nl, size_t nn) { return wire_proof_bytes(4 + 2 * rounds + k, nl + nn); }
 int bppp_reciprocal_agg_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd, size_t dim_np,
                                           const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn,
                                           uint8_t* accept, int32_t* status) {
     CtxLock lock_(c);
-    return agg_sec1_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, nullptr);
+    return agg_sec1_host_entry(c, {label, label_len, k, false, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, nullptr, commitments33, proofs33,
+                               accept, status);
 }
 // the wire form on the caller's transcripts (host buffers): the expansion in front is the label form's
 int bppp_reciprocal_agg_verify_batch_transcript_sec1(bppp_ctx* c, size_t n, const uint8_t* states, size_t n_states, size_t k, size_t dim_nd,
@@ -2242,102 +2162,23 @@ int bppp_reciprocal_agg_verify_batch_transcript_sec1(bppp_ctx* c, size_t n, cons
     CtxLock lock_(c);
     if (!states) return BPPP_ERR_INVALID_ARG;
     const HostTranscripts tx = {states, n_states, states_out};
-    return agg_sec1_host_impl(c, nullptr, 0, n, k, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, nullptr, &tx);
+    return agg_sec1_host_entry(c, {nullptr, 0, k, false, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, nullptr, commitments33, proofs33,
+                               accept, status, &tx);
 }
 int bppp_reciprocal_agg_verify_batch_rlc_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, size_t dim_nd,
                                               size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl,
                                               size_t nn, uint8_t* accept, int32_t* status, const uint8_t seed[32]) {
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
-    return agg_sec1_host_impl(c, label, label_len, n, k, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status, seed);
-}
-
-// ---- aggregates of mixed value counts: 33-byte slots laid out by k_max, instance i in the uniform wire layout for ks[i] in front of
-//      its slots.  k_wire_expand_mixed (wire_mixed_core.h) once over the whole call on the context's stream, in front of the max_batch
-//      parts; the mixed chain then runs on the expanded slots.  Nothing is forwarded: k_max = 1 runs here too
-// arguments checked, n > 0; d_exp: agg_sec1_exp_bytes(n, k_max) in the wire buffer
-static int agg_mixed_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* d_ks, size_t dim_nd,
-                              size_t dim_np, const uint8_t* d_com33, const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn,
-                              void* d_accept, void* d_status, void* d_reject_count, uint8_t* d_exp, const uint8_t* rlc_seed) {
-    const size_t o_p = align16(n * k_max * 64);
-    WireMixed m;
-    m.com33 = d_com33; m.proofs33 = d_proofs33; m.com64 = d_exp; m.proofs64 = d_exp + o_p; m.ks = d_ks;
-    m.n = n; m.k_max = (u32)k_max; m.rounds = (u32)rounds; m.ns = (u32)(nl + nn);
-    k_wire_expand_mixed<<<(unsigned)((wire_mixed_lanes(m) + 255) / 256), 256, 0, c->stream>>>(m);
-    HIP_TRY(hipGetLastError());
-    return agg_mixed_device_run(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status,
-                                d_reject_count, rlc_seed);
-}
-static int agg_mixed_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const void* d_ks,
-                                      size_t dim_nd, size_t dim_np, const void* d_commitments33, const void* d_proofs33, size_t rounds,
-                                      size_t nl, size_t nn, void* d_accept, void* d_status, void* d_reject_count, const uint8_t* rlc_seed) {
-    if (!c || !label_ok(label, label_len) || !d_commitments33 || !d_proofs33 || !d_accept || !d_status) return BPPP_ERR_INVALID_ARG;
-    int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, (const uint8_t*)d_ks, 1, dim_nd, dim_np, rounds, nl, nn);
-    if (rc != BPPP_OK) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (n == 0) {
-        if (d_reject_count) HIP_TRY(hipMemsetAsync(d_reject_count, 0, sizeof(int), c->stream));
-        return BPPP_OK;
-    }
-    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, agg_sec1_exp_bytes(n, k_max, rounds, nl, nn));
-    if (rc != BPPP_OK) return rc;
-    return agg_mixed_sec1_run(c, label, label_len, n, k_max, (const uint8_t*)d_ks, dim_nd, dim_np, (const uint8_t*)d_commitments33,
-                              (const uint8_t*)d_proofs33, rounds, nl, nn, d_accept, d_status, d_reject_count, c->d_wire, rlc_seed);
-}
-int bppp_reciprocal_agg_verify_batch_mixed_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
-                                                       const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments33,
-                                                       const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
-                                                       void* d_status, void* d_reject_count) {
-    CtxLock lock_(c);
-    return agg_mixed_sec1_device_impl(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept,
-                                      d_status, d_reject_count, nullptr);
-}
-int bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
-                                                           const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_commitments33,
-                                                           const void* d_proofs33, size_t rounds, size_t nl, size_t nn, void* d_accept,
-                                                           void* d_status, void* d_reject_count, const uint8_t seed[32]) {
-    CtxLock lock_(c);
-    if (!seed) return BPPP_ERR_INVALID_ARG;
-    return agg_mixed_sec1_device_impl(c, label, label_len, n, k_max, d_ks, dim_nd, dim_np, d_commitments33, d_proofs33, rounds, nl, nn, d_accept,
-                                      d_status, d_reject_count, seed);
-}
-// host buffers: ks and the 33-byte slots staged in the wire buffer too, in front of accept, status and the expanded form
-static int agg_mixed_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
-                                    size_t dim_nd, size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds,
-                                    size_t nl, size_t nn, uint8_t* accept, int32_t* status, const uint8_t* rlc_seed) {
-    if (!c || !label_ok(label, label_len) || !commitments33 || !proofs33 || !accept) return BPPP_ERR_INVALID_ARG;
-    int rc = bppp_reciprocal_agg_mixed_check_args((size_t)c->ng, (size_t)c->nh, n, k_max, ks, 0, dim_nd, dim_np, rounds, nl, nn);
-    if (rc != BPPP_OK) return rc;
-    if (n == 0) return BPPP_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if (rlc_seed) { c->last_rlc_super_m = 0; c->last_rlc_chunk = 0; }
-    const size_t pb = wire_proof_bytes(4 + 2 * rounds + k_max, nl + nn);
-    const size_t o_c = 0, o_p = align16(n * k_max * 33), o_k = align16(o_p + n * pb), o_a = align16(o_k + n), o_s = align16(o_a + n),
-                 o_e = align16(o_s + n * 4), total = o_e + agg_sec1_exp_bytes(n, k_max, rounds, nl, nn);
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
-    if (rc != BPPP_OK) return rc;
-    WireQuiesce guard{c};
-    uint8_t* d = c->d_wire;
-    hipStream_t s = c->stream;
-    // (the whole slots go up; the expansion reads an instance's first k_i commitments and S(k_i) bytes only)
-    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * k_max * 33, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_k, ks, n, hipMemcpyHostToDevice, s));
-    rc = agg_mixed_sec1_run(c, label, label_len, n, k_max, d + o_k, dim_nd, dim_np, d + o_c, d + o_p, rounds, nl, nn, d + o_a, d + o_s, nullptr,
-                            d + o_e, rlc_seed);
-    if (rc != BPPP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    return agg_sec1_host_entry(c, {label, label_len, k, false, dim_nd, dim_np, rounds, nl, nn, seed}, n, nullptr, commitments33, proofs33,
+                               accept, status);
 }
 int bppp_reciprocal_agg_verify_batch_mixed_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
                                                 size_t dim_nd, size_t dim_np, const uint8_t* commitments33, const uint8_t* proofs33,
                                                 size_t rounds, size_t nl, size_t nn, uint8_t* accept, int32_t* status) {
     CtxLock lock_(c);
-    return agg_mixed_sec1_host_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status,
-                                    nullptr);
+    return agg_sec1_host_entry(c, {label, label_len, k_max, true, dim_nd, dim_np, rounds, nl, nn, nullptr}, n, ks, commitments33, proofs33,
+                               accept, status);
 }
 int bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
                                                     const uint8_t* ks, size_t dim_nd, size_t dim_np, const uint8_t* commitments33,
@@ -2345,25 +2186,20 @@ int bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1(bppp_ctx* c, const uint8_t* 
                                                     int32_t* status, const uint8_t seed[32]) {
     CtxLock lock_(c);
     if (!seed) return BPPP_ERR_INVALID_ARG;
-    return agg_mixed_sec1_host_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, commitments33, proofs33, rounds, nl, nn, accept, status,
-                                    seed);
+    return agg_sec1_host_entry(c, {label, label_len, k_max, true, dim_nd, dim_np, rounds, nl, nn, seed}, n, ks, commitments33, proofs33,
+                               accept, status);
 }
 
 // ---- circuit
-static size_t circuit_sec1_exp_bytes(size_t n, size_t k, size_t rounds, size_t nl, size_t nn) {
-    return align16(n * k * 64) + n * (64 * (4 + 2 * rounds) + 32 * (nl + nn));
-}
+// arguments checked; d_exp: circuit_wire_exp().bytes() in the wire buffer
 static int circuit_sec1_run(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n, const uint8_t* d_com33,
                             const uint8_t* d_proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* d_accept, int32_t* d_status, uint8_t* d_exp,
                             const uint8_t* rlc_seed) {
-    const size_t k = (size_t)q->cd.k, P = 4 + 2 * rounds, S = nl + nn, o_p = align16(n * k * 64);
-    WireMap m;
-    wire_map_init(m, n);
-    wire_map_add(m, false, d_com33, 33 * k, d_exp, 64 * k, k);
-    wire_add_proof(m, d_proofs33, d_exp + o_p, P, S);
-    int rc = wire_launch(m, true, c->stream);
+    const WireExp e = circuit_wire_exp(n, (size_t)q->cd.k, rounds, nl, nn);
+    const int rc = e.launch(d_com33, d_proofs33, d_exp, c->stream);
     if (rc != BPPP_OK) return rc;
-    return circuit_verify_host_impl(c, q, label, label_len, n, d_exp, d_exp + o_p, rounds, nl, nn, d_accept, d_status, nullptr, true, rlc_seed);
+    return circuit_verify_host_impl(c, q, label, label_len, n, d_exp, d_exp + e.o_proofs(), rounds, nl, nn, d_accept, d_status, nullptr, true,
+                                    rlc_seed);
 }
 static int circuit_sec1_device_impl(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
                                     const void* d_commitments33, const void* d_proofs33, size_t rounds, size_t nl, size_t nn,
@@ -2372,7 +2208,7 @@ static int circuit_sec1_device_impl(bppp_ctx* c, const bppp_circuit* q, const ui
     if (rc != BPPP_OK) return rc;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, circuit_sec1_exp_bytes(n, (size_t)q->cd.k, rounds, nl, nn));
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, circuit_wire_exp(n, (size_t)q->cd.k, rounds, nl, nn).bytes());
     if (rc != BPPP_OK) return rc;
     return circuit_sec1_run(c, q, label, label_len, n, (const uint8_t*)d_commitments33, (const uint8_t*)d_proofs33, rounds, nl, nn,
                             (uint8_t*)d_accept, (int32_t*)d_status, c->d_wire, rlc_seed);
@@ -2397,22 +2233,12 @@ static int circuit_sec1_host_impl(bppp_ctx* c, const bppp_circuit* q, const uint
     if (rc != BPPP_OK) return rc;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t k = (size_t)q->cd.k, pb = wire_proof_bytes(4 + 2 * rounds, nl + nn);
-    const size_t o_c = 0, o_p = align16(n * k * 33), o_a = align16(o_p + n * pb), o_s = align16(o_a + n), o_e = align16(o_s + n * 4),
-                 total = o_e + circuit_sec1_exp_bytes(n, k, rounds, nl, nn);
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, total);
+    const WireExp e = circuit_wire_exp(n, (size_t)q->cd.k, rounds, nl, nn);
+    HostStage hs;
+    rc = hs.begin(c, true, {{commitments33, e.com33_bytes()}, {proofs33, e.proofs33_bytes()}}, n, nullptr, e.bytes());
     if (rc != BPPP_OK) return rc;
-    WireQuiesce guard{c};
-    uint8_t* d = c->d_wire;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d + o_c, commitments33, n * k * 33, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_p, proofs33, n * pb, hipMemcpyHostToDevice, s));
-    rc = circuit_sec1_run(c, q, label, label_len, n, d + o_c, d + o_p, rounds, nl, nn, d + o_a, (int32_t*)(d + o_s), d + o_e, rlc_seed);
-    if (rc != BPPP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    rc = circuit_sec1_run(c, q, label, label_len, n, hs.in[0], hs.in[1], rounds, nl, nn, hs.accept, hs.status, hs.tail, rlc_seed);
+    return hs.finish(rc, n, accept, status, nullptr);
 }
 int bppp_circuit_verify_batch_sec1(bppp_ctx* c, const bppp_circuit* q, const uint8_t* label, size_t label_len, size_t n,
                                    const uint8_t* commitments33, const uint8_t* proofs33, size_t rounds, size_t nl, size_t nn, uint8_t* accept,
@@ -2429,22 +2255,15 @@ int bppp_circuit_verify_batch_rlc_sec1(bppp_ctx* c, const bppp_circuit* q, const
 }
 
 // ---- WeightNormLinearArgument (the commitment and proof.r / proof.x are points; proof.l / proof.n scalars, taken as they are)
-static size_t wnla_sec1_exp_bytes(size_t n, size_t rounds) { return align16(n * 64) + 2 * align16(n * rounds * 64); }
+// arguments checked; d_exp: WnlaWireExp::bytes() in the wire buffer
 static int wnla_sec1_run(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* d_com33, const uint8_t* d_c,
                          const uint8_t* d_rho, const uint8_t* d_mu, size_t rounds, const uint8_t* d_r33, const uint8_t* d_x33, const uint8_t* d_l,
                          size_t nl, const uint8_t* d_n, size_t nn, uint8_t* d_accept, int32_t* d_status, uint8_t* d_exp,
                          const uint8_t* rlc_seed) {
-    const size_t o_r = align16(n * 64), o_x = o_r + align16(n * rounds * 64);
-    WireMap m;
-    wire_map_init(m, n);
-    wire_map_add(m, false, d_com33, 33, d_exp, 64, 1);
-    if (rounds) {
-        wire_map_add(m, false, d_r33, 33 * rounds, d_exp + o_r, 64 * rounds, rounds);
-        wire_map_add(m, false, d_x33, 33 * rounds, d_exp + o_x, 64 * rounds, rounds);
-    }
-    int rc = wire_launch(m, true, c->stream);
+    const WnlaWireExp e = {n, rounds};
+    const int rc = e.launch(d_com33, d_r33, d_x33, d_exp, c->stream);
     if (rc != BPPP_OK) return rc;
-    return wnla_run(c, false, label, label_len, n, d_exp, d_c, d_rho, d_mu, rounds, d_exp + o_r, d_exp + o_x, d_l, nl, d_n, nn, nullptr,
+    return wnla_run(c, false, label, label_len, n, d_exp, d_c, d_rho, d_mu, rounds, d_exp + e.o_r(), d_exp + e.o_x(), d_l, nl, d_n, nn, nullptr,
                     d_accept, d_status, nullptr, true, rlc_seed);
 }
 static int wnla_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const void* d_commitments33,
@@ -2457,7 +2276,7 @@ static int wnla_sec1_device_impl(bppp_ctx* c, const uint8_t* label, size_t label
     if (!wnla_shape_ok(rounds, nl, nn)) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, wnla_sec1_exp_bytes(n, rounds));
+    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, WnlaWireExp{n, rounds}.bytes());
     if (rc != BPPP_OK) return rc;
     return wnla_sec1_run(c, label, label_len, n, (const uint8_t*)d_commitments33, (const uint8_t*)d_c, (const uint8_t*)d_rho, (const uint8_t*)d_mu,
                          rounds, (const uint8_t*)d_proof_r33, (const uint8_t*)d_proof_x33, (const uint8_t*)d_proof_l, nl, (const uint8_t*)d_proof_n,
@@ -2489,35 +2308,14 @@ static int wnla_sec1_host_impl(bppp_ctx* c, const uint8_t* label, size_t label_l
     if (!wnla_shape_ok(rounds, nl, nn)) return BPPP_ERR_INVALID_ARG;
     if (n == 0) return BPPP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t NH = (size_t)c->nh;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align16(off + bytes); return o; };
-    const size_t o_com = take(n * 33), o_c = take(n * NH * 32), o_rho = take(n * 32), o_mu = take(n * 32), o_r = take(n * rounds * 33),
-                 o_x = take(n * rounds * 33), o_l = take(n * nl * 32), o_n = take(n * nn * 32), o_a = take(n), o_s = take(n * 4),
-                 o_e = take(wnla_sec1_exp_bytes(n, rounds));
-    rc = ensure_buffer(c, c->d_wire, c->wire_bytes, off);
+    HostStage hs;       // (proof.r / proof.x of no rounds and l / n of length 0 may be null: room of 0 bytes, no copy)
+    rc = hs.begin(c, true, {{commitments33, n * 33}, {cvec, n * (size_t)c->nh * 32}, {rho, n * 32}, {mu, n * 32}, {proof_r33, n * rounds * 33},
+                            {proof_x33, n * rounds * 33}, {proof_l, n * nl * 32}, {proof_n, n * nn * 32}}, n, nullptr, WnlaWireExp{n, rounds}.bytes());
     if (rc != BPPP_OK) return rc;
-    WireQuiesce guard{c};
-    uint8_t* d = c->d_wire;
-    hipStream_t s = c->stream;
-    auto up = [&](size_t o, const uint8_t* src, size_t bytes) -> hipError_t {
-        return (src && bytes) ? hipMemcpyAsync(d + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    HIP_TRY(up(o_com, commitments33, n * 33));
-    HIP_TRY(up(o_c, cvec, n * NH * 32));
-    HIP_TRY(up(o_rho, rho, n * 32));
-    HIP_TRY(up(o_mu, mu, n * 32));
-    HIP_TRY(up(o_r, proof_r33, n * rounds * 33));
-    HIP_TRY(up(o_x, proof_x33, n * rounds * 33));
-    HIP_TRY(up(o_l, proof_l, n * nl * 32));
-    HIP_TRY(up(o_n, proof_n, n * nn * 32));
-    rc = wnla_sec1_run(c, label, label_len, n, d + o_com, d + o_c, d + o_rho, d + o_mu, rounds, d + o_r, d + o_x, d + o_l, nl, d + o_n, nn,
-                       d + o_a, (int32_t*)(d + o_s), d + o_e, rlc_seed);
-    if (rc != BPPP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(accept, d + o_a, n, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d + o_s, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BPPP_OK;
+    uint8_t* const* in = hs.in;
+    rc = wnla_sec1_run(c, label, label_len, n, in[0], in[1], in[2], in[3], rounds, in[4], in[5], in[6], nl, in[7], nn, hs.accept, hs.status, hs.tail,
+                       rlc_seed);
+    return hs.finish(rc, n, accept, status, nullptr);
 }
 int bppp_wnla_verify_batch_sec1(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, const uint8_t* commitments33,
                                 const uint8_t* cvec, const uint8_t* rho, const uint8_t* mu, size_t rounds, const uint8_t* proof_r33,

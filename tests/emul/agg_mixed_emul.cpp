@@ -1,6 +1,6 @@
 // TEST-ONLY host emulation of the mixed-value-count aggregate verifier's device code (bp_pp_amd/csrc/agg_mixed_core.h, then the uniform
 // fixed-base half, finish and WNLA stage): the exact __host__ __device__ functions the kernels of k_agg_mixed.hip call, compiled with
-// g++ and run one "thread" after the other in the order of agg_mixed_device_impl.  A translation unit of its own beside agg_emul.cpp
+// g++ and run one "thread" after the other in the order of agg_verify_device_impl's mixed form.  A translation unit of its own beside agg_emul.cpp
 // (tests/emul/build_agg_mixed.py builds it); the fixed-base table it takes is the one bppp_emul.cpp's emul_fb_build makes.
 #include <cstdlib>
 #include <cstring>

@@ -1,5 +1,5 @@
 // TEST-ONLY device runner of the product's own k_wire_expand_mixed: bp_pp_amd/csrc/k_wire_mixed.hip included as it is, and one C
-// function that launches the kernel over device pointers as agg_mixed_sec1_run does (tests/emul/build_wire_mixed.py builds it with
+// function that launches the kernel over device pointers as agg_sec1_run does for a mixed call (tests/emul/build_wire_mixed.py builds it with
 // hipcc for gfx950; tests/test_gpu_agg_mixed_wire_expand.py checks the bytes it leaves).
 #include "../../bp_pp_amd/csrc/k_wire_mixed.hip"
 

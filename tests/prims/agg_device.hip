@@ -10,7 +10,7 @@
 
 #define PRIMS_API extern "C" __attribute__((visibility("default")))
 
-// the grids of bppp_generic.hip, where they are static: blocks_of (line 19), fb_blocks_of (20), fb64_blocks_of (113), fb1_blocks_of (114)
+// the grids of bppp_generic.hip, where they are static functions of these names: blocks_of, fb_blocks_of, fb64_blocks_of, fb1_blocks_of
 static unsigned blocks_of(size_t n) { return (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK); }
 static unsigned fb_blocks_of(size_t n) { return (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK); }
 static unsigned fb64_blocks_of(size_t n) { return (unsigned)((n * 64 + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK); }
@@ -34,7 +34,7 @@ struct DevBuf {      // one device allocation, freed when the launcher returns
 };
 }  // namespace
 
-// The launch sequence of agg_verify_device_impl (bppp_generic.hip:773-790) on the null stream, the form word in place of the plan.
+// The launch sequence of agg_verify_device_impl (bppp_generic.hip; its uniform form, without the caller's transcripts) on the null stream, the form word in place of the plan.
 // Returns the first HIP error (hipErrorInvalidValue for arguments out of range: nothing is launched then).
 PRIMS_API int prims_run_agg_verify_device(const int64_t* dims, const void* const* in, void* const* io) {
     aggp::VerifyShape s;
@@ -74,7 +74,7 @@ PRIMS_API int prims_run_agg_verify_device(const int64_t* dims, const void* const
     return (int)e;
 }
 
-// k_aprove_witness, k_aprove_stage_r1, k_aprove_msm, k_aprove_stage_r2 with agg_prove_part's grids (bppp_generic.hip:2147-2156: blocks_of(n)
+// k_aprove_witness, k_aprove_stage_r1, k_aprove_msm, k_aprove_stage_r2 with agg_prove_part's grids (bppp_generic.hip: blocks_of(n)
 // blocks of BPPP_BLOCK; the msm fb_blocks_of(n k) blocks of BPPP_FB_BLOCK).  Returns the first HIP error (hipErrorInvalidValue for arguments out of range).
 PRIMS_API int prims_run_agg_prove_device(const int64_t* dims, const void* const* in, void* const* io) {
     aggp::ProveShape s;

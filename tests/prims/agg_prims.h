@@ -53,7 +53,7 @@ struct VerifyShape {
     int G, fb;
     bool tables;
 };
-// the bounds of agg_verify_check_args (bppp_generic.hip) and of this launcher: every index the kernels form stays inside a buffer
+// the bounds of agg_shape_check (bppp_generic.hip) and of this launcher: every index the kernels form stays inside a buffer
 inline bool verify_shape(VerifyShape& s, const int64_t* d) {
     for (int i = 0; i < AGGV_NDIMS; i++)
         if (d[i] < 0 || d[i] > (1 << 20)) return false;
@@ -83,7 +83,7 @@ inline size_t verify_atab_entries(const VerifyShape& s) { return (4 + s.k) * 16 
 inline size_t verify_tscr_words(const VerifyShape& s) { return (size_t)BPPP_TSCR_PER_POINT * (4 + s.k) * 10 * s.N; }
 inline size_t verify_straus_slots(const VerifyShape& s) { return s.N * 5 * BPPP_STRAUS_ENTRIES; }
 
-// the workspace as agg_verify_device_impl fills it (bppp_generic.hip:744-761), over the caller's buffers; the tables of the 4 + k points
+// the workspace as agg_ws_fill of bppp_generic.hip fills it, over the caller's buffers; the tables of the 4 + k points
 // start at entry 0 (no round points in front of them)
 inline bppp::AggWs verify_ws(const VerifyShape& s, const uint8_t* label, const void* table, const void* com, const void* proofs, void* const* io,
                              bppp::apt_packed* atab, bppp::u32* tscr, bppp::pt_slot* straus) {
@@ -172,7 +172,7 @@ inline void prove_sizes(const ProveShape& s, size_t io_bytes[AGGP_NBUFS]) {
     io_bytes[P_CP_VPTS] = rows * 64; io_bytes[P_PROOF_R] = rows * 64;
 }
 inline size_t prove_table_bytes(const ProveShape& s) { return (1 + s.NG + s.NH) * bppp::fb_per_base(4) * sizeof(bppp::apt_packed); }
-// the workspace as agg_prove_part fills it (bppp_generic.hip:2113-2124) as far as the four stages read it
+// the workspace as agg_prove_part of bppp_generic.hip fills it as far as the four stages read it
 inline bppp::AggProveWs prove_ws(const ProveShape& s, const uint8_t* label, const void* table, void* const* io) {
     using bppp::u32;
     bppp::AggProveWs a;

@@ -9,7 +9,7 @@
 
 #define PRIMS_API extern "C" __attribute__((visibility("default")))
 
-// the grids of bppp_generic.hip, where they are static: blocks_of (line 19), fb_blocks_of (20), fb64_blocks_of (113)
+// the grids of bppp_generic.hip, where they are static functions of these names: blocks_of, fb_blocks_of, fb64_blocks_of
 static unsigned blocks_of(size_t n) { return (unsigned)((n + BPPP_BLOCK - 1) / BPPP_BLOCK); }
 static unsigned fb_blocks_of(size_t n) { return (unsigned)((n * BPPP_FB_LANES + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK); }
 static unsigned fb64_blocks_of(size_t n) { return (unsigned)((n * 64 + BPPP_FB_BLOCK - 1) / BPPP_FB_BLOCK); }

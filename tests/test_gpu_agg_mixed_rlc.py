@@ -222,3 +222,65 @@ def test_a_null_seed_is_refused_on_a_live_context(verifiers):
             assert f(SEEDS[0]) == _capi.OK, suffix
         v.synchronize()
         assert (acc == exp_acc).all() and (dA.cpu().numpy() == exp_acc).all(), suffix
+
+
+def _one_or_two_values(wire):
+    """The rows of the (3, 4, 4) batch with one or two values, in slots laid out by k_max = 2 on that context's generators (an
+    instance is verified by its own count whatever the slots): (case, ks, commitments, proofs, accept, flagged) by the oracle."""
+    if wire:
+        case_max, ks, C, Q, _, _, exp_acc, exp_flag, _, _ = MW.wire_batch((3, 4, 4))
+    else:
+        case_max, ks, C, Q, exp_acc, exp_flag, _ = M.batch((3, 4, 4))
+    case = M.setup_on(case_max, 2)
+    idx = np.flatnonzero(ks <= 2)
+    assert set(ks[idx].tolist()) == {1, 2} and 0 < int(exp_acc[idx].sum()) < len(idx) and exp_flag[idx].any()
+    width = MW.sec1_bytes(case_max, 2) if wire else case["proof_bytes"]
+    return case, ks[idx].copy(), np.ascontiguousarray(C[idx, :2]), np.ascontiguousarray(Q[idx, :width]), exp_acc[idx], exp_flag[idx]
+
+
+@pytest.mark.parametrize("form", ["host", "device", "sec1", "rlc"])
+def test_allocation_failure_at_every_position_is_nomem_and_the_context_recovers(form):
+    """After tests/test_gpu_agg_rlc.py, for the mixed family: a call larger than any before it -- 64 rows more each time, so that the
+    projective tables, the bucket buffers and the workspace or staging all grow -- with the first, then the second, then the third ...
+    device allocation failing, for as long as the call still fails.  Each failure is ERR_NOMEM, leaves no stale "last_rlc_*", and the
+    next call is served with the oracle's rows.  How many positions a form has is printed, not pinned."""
+    import torch
+    if torch.cuda.device_count() == 0:
+        pytest.fail("needs a GPU")
+    from bp_pp_amd._capi import ERR_NOMEM, BpppError
+    case, ks, Cn, Qn, exp_acc, exp_flag = _one_or_two_values(form == "sec1")
+    args = shape_of(case)
+    call = {"host": lambda v, k, c, q: v.verify_batch_mixed(case["label"], k, c, q, *args),
+            "device": lambda v, k, c, q: device_call(v, case, k, c, q, "verify_batch_mixed_device")[:2],
+            "sec1": lambda v, k, c, q: v.verify_batch_mixed_sec1(case["label"], k, c, q, *args),
+            "rlc": lambda v, k, c, q: v.verify_batch_mixed_rlc(case["label"], k, c, q, *args, SEEDS[0])}[form]
+    rlc = form == "rlc"
+    v = make((2, 4, 4), case)
+    try:
+        acc, st = call(v, ks, Cn, Qn)
+        assert_rows(acc, st, exp_acc, exp_flag, (form, "before"))
+        assert not rlc or _used(v) == (256, CHUNK)
+        positions = 0
+        for fault in range(1, 9):
+            big = np.arange(64 * (fault + 1) + 7) % len(ks)
+            v.set_option("inject_alloc_fault", fault)
+            try:
+                acc, st = call(v, ks[big], Cn[big], Qn[big])
+            except BpppError as e:
+                assert e.code == ERR_NOMEM, (form, fault, e.code)
+                acc = None
+            v.set_option("inject_alloc_fault", 0)
+            if acc is not None:                           # fewer allocations than `fault`: the call was served
+                assert_rows(acc, st, exp_acc[big], exp_flag[big], (form, fault, "served"))
+                break
+            positions += 1
+            assert not rlc or _used(v) == (0, 0), (form, fault)      # nothing stale after the failure
+            acc, st = call(v, ks, Cn, Qn)                 # the next call is served
+            assert_rows(acc, st, exp_acc, exp_flag, (form, fault, "after"))
+            assert not rlc or _used(v) == (256, CHUNK), (form, fault)
+        else:
+            pytest.fail("%s: a call still fails with the 9th allocation as the failing one" % form)
+        print("allocation-fault positions of the mixed %s form: %d" % (form, positions))
+        assert positions >= 1, form                       # the call grew something
+    finally:
+        v.close()
