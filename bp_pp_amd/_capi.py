@@ -90,6 +90,11 @@ AGG_MIXED_WIRE_RLC_EXPORTS = ["bppp_reciprocal_agg_verify_batch_mixed_rlc", "bpp
                               "bppp_reciprocal_agg_verify_batch_mixed_sec1", "bppp_reciprocal_agg_verify_batch_mixed_sec1_device",
                               "bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1", "bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1_device"]
 EXPORTS += AGG_MIXED_WIRE_RLC_EXPORTS
+# the prover from integers for mixed value counts (include/bppp.h: "The aggregate prover for MIXED value counts")
+AGG_MIXED_PROVE_EXPORTS = ["bppp_reciprocal_agg_prove_mixed_check_args", "bppp_reciprocal_agg_prove_values_batch_mixed",
+                           "bppp_reciprocal_agg_prove_values_batch_mixed_seeded", "bppp_reciprocal_agg_prove_values_batch_mixed_device",
+                           "bppp_reciprocal_agg_prove_values_batch_mixed_seeded_device"]
+EXPORTS += AGG_MIXED_PROVE_EXPORTS
 
 _lib = None
 
@@ -351,6 +356,16 @@ def lib():
         L.bppp_reciprocal_agg_verify_batch_mixed_rlc_device.argtypes = host + [vp, u8p]
         L.bppp_reciprocal_agg_verify_batch_mixed_rlc_sec1_device.argtypes = host + [vp, u8p]
         for name in AGG_MIXED_WIRE_RLC_EXPORTS:
+            getattr(L, name).restype = i32
+    # the mixed prover from integers: the uniform prover's lists with (k) -> (k_max, ks)
+    if "BPPP_LIB" not in os.environ or hasattr(L, "bppp_reciprocal_agg_prove_values_batch_mixed"):
+        u64 = C.c_uint64
+        L.bppp_reciprocal_agg_prove_mixed_check_args.argtypes = [sz, sz, sz, sz, vp, i32, sz, sz]
+        L.bppp_reciprocal_agg_prove_values_batch_mixed.argtypes = [vp, u8p, sz, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_mixed_seeded.argtypes = [vp, u8p, sz, sz, sz, vp, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_mixed_device.argtypes = [vp, u8p, sz, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.bppp_reciprocal_agg_prove_values_batch_mixed_seeded_device.argtypes = [vp, u8p, sz, sz, sz, vp, sz, sz, vp, vp, u8p, u64, vp, vp, vp]
+        for name in AGG_MIXED_PROVE_EXPORTS:
             getattr(L, name).restype = i32
     L.bppp_strerror.argtypes = [i32]
     L.bppp_strerror.restype = C.c_char_p

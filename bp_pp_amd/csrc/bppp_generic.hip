@@ -2744,5 +2744,195 @@ int bppp_reciprocal_agg_prove_values_batch_transcript_device(bppp_ctx* c, size_t
                           (uint8_t*)d_proofs, (uint8_t*)d_commitments, (int32_t*)d_status, true, false, &tx);
 }
 
+// ---- the prover from integers for MIXED value counts (agg_prove_mixed_core.h): instance i has ks[i] values in slots laid out by k_max.
+//      Label transcripts, 64-byte outputs.  The blob, the shape data and the parts are agg_prove_part's for k = k_max (agg_prove_layout,
+//      agg_prove_shape_get, agg_prove_part_size) with a part's slice of ks behind them; the fixed-base sums, stage D and the WNLA prover
+//      are the uniform launches; nothing is forwarded (k_max = 1 runs here too).
+int bppp_reciprocal_agg_prove_mixed_check_args(size_t ng, size_t nh, size_t n, size_t k_max, const uint8_t* ks, int ks_on_device, size_t dim_nd,
+                                               size_t dim_np) {
+    return agg_prove_mixed_args_ok(ng, nh, n, k_max, ks, ks_on_device != 0, dim_nd, dim_np) ? BPPP_OK : BPPP_ERR_INVALID_ARG;
+}
+// one part of m instances.  ks: this part's slice -- a host pointer in the host forms (uploaded behind the part's layout), else a device one
+static int agg_prove_mixed_part(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t m, size_t k, size_t nd, size_t np,
+                                const AggProveShapeDev& shp, const uint8_t* ks, const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd,
+                                const uint8_t* seed, uint64_t stream, uint8_t* proofs, uint8_t* commitments, int32_t* status, bool device_io,
+                                const WnlaProveShape& sh0, size_t proof_bytes) {
+    const size_t n = m, nm = k * nd, nv = nd + 1, rows = n * k, n_rnd = agg_prove_draws(k, nd);
+    WnlaProveShape sh = sh0;
+    sh.n = n;
+    const AggProveLayout o = agg_prove_layout(c, n, k, nd, np, sh, proof_bytes);
+    uint8_t* d = c->d_blob;
+    hipStream_t s = c->stream;
+    int rc = BPPP_OK;
+    if (!device_io) {
+        HIP_TRY(hipMemcpyAsync(d + o.total, ks, n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d + o.x, x, rows * 32, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d + o.s, sblind, rows * 32, hipMemcpyHostToDevice, s));
+    }
+    DrawWipe wipe = {seed ? d + o.rnd : nullptr, n * n_rnd * 32, s};
+    if (seed) { const int rc_d = draw_enqueue(s, seed, stream, n, n_rnd, d + o.rnd); if (rc_d != BPPP_OK) return rc_d; }
+    else if (!device_io) HIP_TRY(hipMemcpyAsync(d + o.rnd, rnd, n * n_rnd * 32, hipMemcpyHostToDevice, s));
+    AggProveMixedWs am;
+    std::memset(&am, 0, sizeof am);
+    am.ks = device_io ? ks : d + o.total;
+    AggProveWs& a = am.a;
+    a.N = n; a.k = (int)k; a.nd = (int)nd; a.np = (int)np; a.NG = c->ng; a.NH = c->nh; a.n_rnd = (int)n_rnd;
+    recip_witness_shape(a.rw, nd, np);
+    a.x = device_io ? x : d + o.x; a.s = device_io ? sblind : d + o.s; a.rnd = (device_io && !seed) ? rnd : d + o.rnd;
+    a.digits = d + o.dig; a.m = d + o.m; a.status = (int32_t*)(d + o.st); a.row_status = (int32_t*)(d + o.rst); a.vsc = (u32*)(d + o.vsc);
+    a.commitments = d + o.com; a.tstate = (u32*)(d + o.ts); a.inst_vals = (u32*)(d + o.inst); a.scr = (u32*)(d + o.scr);
+    a.rsc = (u32*)(d + o.rsc); a.rpb = (u32*)(d + o.rpb); a.vsum = (u32*)(d + o.vsum);
+    a.cp_v = d + o.cpv; a.cp_sv = d + o.cpsv; a.cp_wr = d + o.cpwr; a.cp_vpts = d + o.cpvp; a.proof_R = d + o.prR;
+    a.fb = fb_table_of(c, rows);
+    { const int rc_ct = ct_setup(c, a.fb_ct, a.ct, rows); if (rc_ct != BPPP_OK) return rc_ct; }
+    t_new(a.base, label, (u32)label_len);
+    // the value commitments over N k_max rows (the rows behind an instance's k_i carry zero scalars: the identity)
+    RecipCommitWs cw;
+    std::memset(&cw, 0, sizeof cw);
+    cw.N = rows; cw.NG = c->ng; cw.x = a.x; cw.s = a.s; cw.status = a.row_status; cw.msc = a.vsc; cw.pbuf = (u32*)(d + o.vpb); cw.out = d + o.com;
+    cw.fb = a.fb; cw.fb_ct = a.fb_ct; cw.ct = a.ct;
+    CircuitProveMixedWs pm;
+    std::memset(&pm, 0, sizeof pm);
+    pm.ks = am.ks; pm.k_max = (int)k;
+    CircuitProveWs& p = pm.p;
+    p.base = a.base;
+    CircuitDev& cd = p.cd;
+    cd.nm = (int)nm; cd.no = (int)np; cd.k = (int)k; cd.nl = (int)(k * nv); cd.nv = (int)nv; cd.nw = (int)(2 * nm + np); cd.f_l = 1; cd.f_m = 0;
+    cd.a_l = (const u32*)(shp.d + shp.al); cd.a_m = (const u32*)(shp.d + shp.am); cd.inst_vals = a.inst_vals;
+    p.N = n; p.NG = c->ng; p.NH = c->nh; p.n_rnd = (int)(18 + nv + nm); p.rnd_stride = n_rnd * 32; p.part = (const int*)(shp.d + shp.part);
+    p.transcript_preloaded = 1;
+    p.v_pts = a.cp_vpts; p.v = a.cp_v; p.s_v = a.cp_sv; p.w_l = a.digits; p.w_r = a.cp_wr; p.w_o = a.m; p.rnd = a.rnd + 32 * k;
+    p.proof_head = d + o.head; p.status = a.status; p.tstate = a.tstate;
+    circuit_prove_carve(p, d, o.c);
+    p.fb = fb_table_of(c, n);
+    { const int rc_ct = ct_setup(c, p.fb_ct, p.ct, n); if (rc_ct != BPPP_OK) return rc_ct; }
+    WnlaProveWs w;
+    rc = wnla_prove_fill_behind(c, w, sh, d, o.w, p);
+    if (rc != BPPP_OK) return rc;
+    const unsigned blocks = blocks_of(n), fb_blocks = fb_blocks_of(n), row_blocks = blocks_of(rows), row_fb_blocks = fb_blocks_of(rows);
+    GLAUNCH(s, K_APMIX_WITNESS, k_aprove_mixed_witness<<<blocks, BPPP_BLOCK, 0, s>>>(am));
+    GLAUNCH(s, K_APMIX_COMMIT, {
+        k_rprove_commit<<<row_fb_blocks, BPPP_FB_BLOCK, 0, s>>>(cw);
+        k_rprove_commit_store<<<row_blocks, BPPP_BLOCK, 0, s>>>(cw);
+    });
+    GLAUNCH(s, K_APMIX_POLES, {
+        k_aprove_mixed_stage_r1<<<blocks, BPPP_BLOCK, 0, s>>>(am);
+        k_aprove_msm<<<row_fb_blocks, BPPP_FB_BLOCK, 0, s>>>(a);
+        k_aprove_mixed_stage_r2<<<blocks, BPPP_BLOCK, 0, s>>>(am);
+    });
+    HIP_TRY(hipMemsetAsync(p.msc, 0, 3 * (size_t)c->nbases * 8 * n * 4, s));     // every fill writes k_i nd entries: zeros behind them
+    GLAUNCH(s, K_APMIX_STAGE_A, {
+        k_aprove_mixed_stage_a<<<blocks, BPPP_BLOCK, 0, s>>>(pm);
+        for (int set = 0; set < 3; set++) k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, set, 0);
+    });
+    // stage B once per value count the call may hold (k_aggprove_mixed.hip: the lanes of that count run, the others leave at once)
+    GLAUNCH(s, K_APMIX_STAGE_B, {
+        for (int kk = 1; kk <= (int)k; kk++) k_aprove_mixed_stage_b<<<blocks, BPPP_BLOCK, 0, s>>>(pm, kk);
+    });
+    if (c->timing) GLAUNCH(s, K_APMIX_COLLECT, k_aprove_mixed_collect<<<blocks, BPPP_BLOCK, 0, s>>>(pm));      // (same values again: its time alone)
+    GLAUNCH(s, K_APMIX_TAIL, {
+        k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 0);
+        k_aprove_mixed_stage_c<<<blocks, BPPP_BLOCK, 0, s>>>(pm);
+        k_cprove_msm<<<fb_blocks, BPPP_FB_BLOCK, 0, s>>>(p, 0, 1);
+        k_cprove_stage_d<<<blocks, BPPP_BLOCK, 0, s>>>(p);
+        wnla_prove_launch(w, s);
+    });
+    HIP_TRY(hipGetLastError());
+    // the proofs and the commitments put together on the device: an instance's k_i poles and commitments, zero bytes behind what it
+    // uses and in every flagged instance
+    ProofAssembleMixedWs as;
+    std::memset(&as, 0, sizeof as);
+    as.ks = am.ks; as.k_max = (int)k; as.vseg = 3;
+    as.w.N = n; as.w.proof_bytes = proof_bytes; as.w.nseg = 6; as.w.status = p.status; as.w.out = device_io ? proofs : d + o.pout;
+    as.w.src[0] = p.proof_head; as.w.bytes[0] = 256;
+    as.w.src[1] = w.proof_r; as.w.bytes[1] = (u32)(sh.rounds * 64);
+    as.w.src[2] = w.proof_x; as.w.bytes[2] = (u32)(sh.rounds * 64);
+    as.w.src[3] = a.proof_R; as.w.bytes[3] = (u32)(k * 64);
+    as.w.src[4] = w.proof_l; as.w.bytes[4] = (u32)(sh.nl_f * 32);
+    as.w.src[5] = w.proof_n; as.w.bytes[5] = (u32)(sh.nn_f * 32);
+    ProofAssembleMixedWs ac;
+    std::memset(&ac, 0, sizeof ac);
+    ac.ks = am.ks; ac.k_max = (int)k; ac.vseg = 0;
+    ac.w.N = n; ac.w.proof_bytes = k * 64; ac.w.nseg = 1; ac.w.status = p.status; ac.w.out = device_io ? commitments : d + o.cout;
+    ac.w.src[0] = d + o.com; ac.w.bytes[0] = (u32)(k * 64);
+    const size_t words = n * (proof_bytes / 4), cwords = n * (k * 16);
+    if ((words + 255) / 256 > 0xFFFFFFFFu) return BPPP_ERR_INVALID_ARG;
+    GLAUNCH(s, K_APMIX_ASSEMBLE, {
+        k_aprove_mixed_assemble<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(as);
+        k_aprove_mixed_assemble<<<(unsigned)((cwords + 255) / 256), 256, 0, s>>>(ac);
+    });
+    HIP_TRY(hipGetLastError());
+    if (!device_io) {
+        HIP_TRY(hipMemcpyAsync(proofs, d + o.pout, n * proof_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(commitments, d + o.cout, rows * 64, hipMemcpyDeviceToHost, s));
+    }
+    if (status) HIP_TRY(hipMemcpyAsync(status, p.status, n * 4, device_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    HIP_TRY(wipe.now());      // the draws cleared behind the last kernel that reads them
+    return BPPP_OK;
+}
+static int agg_prove_mixed_impl(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k, const uint8_t* ks, size_t nd, size_t np,
+                                const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd, const uint8_t* seed, uint64_t stream_base,
+                                uint8_t* proofs, uint8_t* commitments, int32_t* status, bool device_io) {
+    if (!c || !label_ok(label, label_len) || !x || !sblind || (!rnd && !seed) || !proofs || !commitments) return BPPP_ERR_INVALID_ARG;
+    if (!agg_prove_mixed_args_ok((size_t)c->ng, (size_t)c->nh, n, k, ks, device_io, nd, np)) return BPPP_ERR_INVALID_ARG;
+    const size_t n_rnd = agg_prove_draws(k, nd);
+    if (seed && !draw_args_ok(seed, stream_base, n, n_rnd)) return BPPP_ERR_INVALID_ARG;
+    if (n == 0) return BPPP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    AggProveShapeDev shp;
+    { const int rc_s = agg_prove_shape_get(c, k, nd, np, shp); if (rc_s != BPPP_OK) return rc_s; }
+    WnlaProveShape sh = {0, (size_t)c->nh, (size_t)c->ng, 0, 0, 0};
+    wnla_proof_shape(sh.nl, sh.nn, sh.rounds, sh.nl_f, sh.nn_f);
+    const size_t proof_bytes = agg_proof_bytes(k, sh.rounds, sh.nl_f, sh.nn_f);
+    const size_t per = agg_prove_part_size(c, n, k, nd);
+    sh.n = per;
+    WnlaBlob blob;      // host forms: nothing of the call still runs when it returns, whichever way it leaves
+    const size_t blob_bytes = agg_prove_layout(c, per, k, nd, np, sh, proof_bytes).total + align16(per);      // (+ a part's ks)
+    if (device_io) { const int rc_b = ensure_blob(c, blob_bytes); if (rc_b != BPPP_OK) return rc_b; }
+    else { const int rc_b = blob.take(c, blob_bytes); if (rc_b != BPPP_OK) return rc_b; }
+    for (size_t lo = 0; lo < n; lo += per) {
+        const size_t m = n - lo < per ? n - lo : per;
+        const int rc = agg_prove_mixed_part(c, label, label_len, m, k, nd, np, shp, ks + lo, x + lo * k * 32, sblind + lo * k * 32,
+                                            rnd ? rnd + lo * n_rnd * 32 : nullptr, seed, stream_base + lo, proofs + lo * proof_bytes,
+                                            commitments + lo * k * 64, status ? status + lo : nullptr, device_io, sh, proof_bytes);
+        if (rc != BPPP_OK) return rc;
+    }
+    if (!device_io) HIP_TRY(hipStreamSynchronize(c->stream));
+    return BPPP_OK;
+}
+int bppp_reciprocal_agg_prove_values_batch_mixed(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max, const uint8_t* ks,
+                                                 size_t dim_nd, size_t dim_np, const uint8_t* x, const uint8_t* sblind, const uint8_t* rnd,
+                                                 uint8_t* proofs, uint8_t* commitments, int32_t* status) {
+    CtxLock lock_(c);
+    if (!rnd) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_mixed_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, x, sblind, rnd, nullptr, 0, proofs, commitments, status, false);
+}
+int bppp_reciprocal_agg_prove_values_batch_mixed_seeded(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                        const uint8_t* ks, size_t dim_nd, size_t dim_np, const uint8_t* x, const uint8_t* sblind,
+                                                        const uint8_t seed[32], uint64_t stream_base, uint8_t* proofs, uint8_t* commitments,
+                                                        int32_t* status) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_mixed_impl(c, label, label_len, n, k_max, ks, dim_nd, dim_np, x, sblind, nullptr, seed, stream_base, proofs, commitments,
+                                status, false);
+}
+int bppp_reciprocal_agg_prove_values_batch_mixed_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                        const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_x, const void* d_s,
+                                                        const void* d_rnd, void* d_proofs, void* d_commitments, void* d_status) {
+    CtxLock lock_(c);
+    if (!d_rnd) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_mixed_impl(c, label, label_len, n, k_max, (const uint8_t*)d_ks, dim_nd, dim_np, (const uint8_t*)d_x, (const uint8_t*)d_s,
+                                (const uint8_t*)d_rnd, nullptr, 0, (uint8_t*)d_proofs, (uint8_t*)d_commitments, (int32_t*)d_status, true);
+}
+int bppp_reciprocal_agg_prove_values_batch_mixed_seeded_device(bppp_ctx* c, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                               const void* d_ks, size_t dim_nd, size_t dim_np, const void* d_x, const void* d_s,
+                                                               const uint8_t seed[32], uint64_t stream_base, void* d_proofs,
+                                                               void* d_commitments, void* d_status) {
+    CtxLock lock_(c);
+    if (!seed) return BPPP_ERR_INVALID_ARG;
+    return agg_prove_mixed_impl(c, label, label_len, n, k_max, (const uint8_t*)d_ks, dim_nd, dim_np, (const uint8_t*)d_x, (const uint8_t*)d_s,
+                                nullptr, seed, stream_base, (uint8_t*)d_proofs, (uint8_t*)d_commitments, (int32_t*)d_status, true);
+}
+
 }  // extern "C"
 #undef GLAUNCH

@@ -47,6 +47,8 @@ enum KernelId {
     // aggregated reciprocal prover (bppp_reciprocal_agg_prove_values_batch*): witness | value commitments | r1, pole commitments, r2 |
     // stage A and its sums | stage B | the closed-form collect alone (a rerun, only when timing is on) | everything behind stage B
     K_APROVE_WITNESS, K_APROVE_COMMIT, K_APROVE_POLES, K_APROVE_STAGE_A, K_APROVE_STAGE_B, K_APROVE_COLLECT, K_APROVE_TAIL,
+    // the same for mixed value counts (bppp_reciprocal_agg_prove_values_batch_mixed*), cut the same way; the two assembly launches last
+    K_APMIX_WITNESS, K_APMIX_COMMIT, K_APMIX_POLES, K_APMIX_STAGE_A, K_APMIX_STAGE_B, K_APMIX_COLLECT, K_APMIX_TAIL, K_APMIX_ASSEMBLE,
     K_COUNT
 };
 static const char* const kKernelNames[K_COUNT] = {
@@ -58,7 +60,9 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_circuit_phase1", "k_circuit_c0_fixed", "k_circuit_c0_var", "k_circuit_c0_finish", "k_verify_shared_inv",
     "k_rprove_witness", "k_rprove_commit", "k_rprove_chain",
     "k_agg_phase1", "k_agg_c0_fixed", "k_agg_c0_var", "k_agg_c0_finish",
-    "k_aprove_witness", "k_aprove_commit", "k_aprove_poles", "k_aprove_stage_a", "k_aprove_stage_b", "k_aprove_collect", "k_aprove_tail"};
+    "k_aprove_witness", "k_aprove_commit", "k_aprove_poles", "k_aprove_stage_a", "k_aprove_stage_b", "k_aprove_collect", "k_aprove_tail",
+    "k_aprove_mixed_witness", "k_aprove_mixed_commit", "k_aprove_mixed_poles", "k_aprove_mixed_stage_a", "k_aprove_mixed_stage_b",
+    "k_aprove_mixed_collect", "k_aprove_mixed_tail", "k_aprove_mixed_assemble"};
 
 static inline size_t align16(size_t x) { return (x + 15) / 16 * 16; }
 // a transcript label as the ABI takes it: a null pointer only with length 0, and no longer than merlin can frame (its length prefix is a

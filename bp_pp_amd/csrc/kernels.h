@@ -11,6 +11,7 @@
 #include "agg_mixed_core.h"
 #include "recip_prove_core.h"
 #include "agg_prove_core.h"
+#include "agg_prove_mixed_core.h"
 #include "bucket_core.h"
 #include "rlc_core.h"
 #include "wnla_rlc_core.h"
@@ -271,6 +272,16 @@ __global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_collect(bppp::CircuitProv
 __global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_r1_tx(bppp::AggProveWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_stage_b_tx(bppp::CircuitProveWs w);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_export_states(bppp::TranscriptIo io, bppp::strobe base, const bppp::u32* tstate, size_t N, const int32_t* status);
+// the same for mixed value counts (k_aggprove_mixed.hip, agg_prove_mixed_core.h): what depends on an instance's own k; the sums, stage D and
+// the WNLA prover are the kernels above
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_mixed_witness(bppp::AggProveMixedWs m);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_mixed_stage_r1(bppp::AggProveMixedWs m);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_mixed_stage_r2(bppp::AggProveMixedWs m);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_mixed_stage_a(bppp::CircuitProveMixedWs m);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_mixed_stage_b(bppp::CircuitProveMixedWs m, int k);      // the lanes of value count k
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_mixed_collect(bppp::CircuitProveMixedWs m);
+__global__ __launch_bounds__(BPPP_BLOCK) void k_aprove_mixed_stage_c(bppp::CircuitProveMixedWs m);
+__global__ __launch_bounds__(256) void k_aprove_mixed_assemble(bppp::ProofAssembleMixedWs m);
 __global__ __launch_bounds__(BPPP_BLOCK) void k_bkt_prepare(bppp::BucketWs w);
 __global__ __launch_bounds__(256) void k_bkt_accumulate(bppp::BucketWs w);
 __global__ __launch_bounds__(256) void k_bkt_scalars(bppp::BucketWs w);

@@ -676,6 +676,54 @@ class AggregatedReciprocalRangeProofProtocol:
                                                                                          self.dim_nd, self.dim_np, d_x, d_s, seed, stream_base,
                                                                                          d_proofs, d_commitments, d_status or None))
 
+    def _prove_mixed_host(self, name: str, label: bytes, ks, x, s, draws):
+        ks = _u8(ks, (-1,))
+        B = ks.shape[0]
+        x, s = _u8(x, (B, self.k, 32)), _u8(s, (B, self.k, 32))
+        shape = self.proof_shape()
+        proofs, com, st = np.zeros((B, self.proof_bytes(*shape)), np.uint8), np.zeros((B, self.k, 64), np.uint8), np.zeros(B, np.int32)
+        _capi.check(_capi.symbol(name)(self._w._ctx, label, len(label), B, self.k, ks.ctypes.data, self.dim_nd, self.dim_np, x.ctypes.data,
+                                       s.ctypes.data, *draws(B), proofs.ctypes.data, com.ctypes.data, st.ctypes.data))
+        return proofs, com, st, shape
+
+    def prove_values_batch_mixed(self, label: bytes, ks, x, s, rnd):
+        """Instances of different value counts in one call; the constructor's k is k_max and every array is laid out by it.  ks [B]
+        (1 <= ks[i] <= k), x / s [B, k, 32] of which row i's first ks[i] are read, rnd [B, prove_draws(), 32] of which row i's first
+        bppp_reciprocal_agg_prove_draws(ks[i], dim_nd) are read -> (proofs [B, proof_bytes(k)], commitments [B, k, 64], status [B],
+        (rounds, nl, nn)): row i's first proof_bytes(ks[i]) bytes and ks[i] commitments are prove_values_batch's with k = ks[i] on this
+        context, everything behind them zero -- the input of verify_batch_mixed."""
+        D = self.prove_draws()
+        keep = []                 # (the array the pointer is taken of lives until the call returns)
+
+        def draws(B):
+            keep.append(_u8(rnd, (B, D, 32)))
+            return (keep[0].ctypes.data,)
+        return self._prove_mixed_host("bppp_reciprocal_agg_prove_values_batch_mixed", label, ks, x, s, draws)
+
+    def prove_values_batch_mixed_seeded(self, label: bytes, ks, x, s, seed: bytes, stream_base: int):
+        """prove_values_batch_mixed with instance i's draws taken from ChaCha20 stream stream_base + i of `seed` on the device."""
+        from .range_proof import _seed_args
+        return self._prove_mixed_host("bppp_reciprocal_agg_prove_values_batch_mixed_seeded", label, ks, x, s,
+                                      lambda B: _seed_args(seed, stream_base, B))
+
+    def prove_values_batch_mixed_device(self, label: bytes, n: int, d_ks: int, d_x: int, d_s: int, d_rnd: int, d_proofs: int,
+                                        d_commitments: int, d_status: int = 0) -> None:
+        """prove_values_batch_mixed over device buffers (raw device addresses, layouts as above; d_ks: n bytes; d_status 0 = none);
+        asynchronous on the context's stream.  A d_ks[i] outside [1, k] flags instance i ST_BAD_ENCODING and zeroes its outputs."""
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_mixed_device")(self._w._ctx, label, len(label), n, self.k, d_ks,
+                                                                                        self.dim_nd, self.dim_np, d_x, d_s, d_rnd, d_proofs,
+                                                                                        d_commitments, d_status or None))
+
+    def prove_values_batch_mixed_seeded_device(self, label: bytes, n: int, d_ks: int, d_x: int, d_s: int, seed: bytes, stream_base: int,
+                                               d_proofs: int, d_commitments: int, d_status: int = 0) -> None:
+        """prove_values_batch_mixed_seeded over device buffers (raw device addresses); asynchronous on the context's stream."""
+        from .range_proof import _seed_args
+        seed, stream_base = _seed_args(seed, stream_base, n)
+        _capi.check(_capi.symbol("bppp_reciprocal_agg_prove_values_batch_mixed_seeded_device")(self._w._ctx, label, len(label), n, self.k,
+                                                                                               d_ks, self.dim_nd, self.dim_np, d_x, d_s, seed,
+                                                                                               stream_base, d_proofs, d_commitments,
+                                                                                               d_status or None))
+
     def verify_batch(self, label: bytes, commitments, proofs, rounds: int, nl: int, nn: int):
         """commitments [B, k, 64] (value-major), proofs [B, proof_bytes] -> (accept [B], status [B])."""
         commitments = _u8(commitments, (-1, self.k, 64))

@@ -335,6 +335,39 @@ impl U64RangeProofProtocolGpu {
         }
         Ok(acc.iter().map(|a| *a == 1).collect())
     }
+
+    /// The prover's side of `verify_agg_mixed` (bppp_reciprocal_agg_prove_values_batch_mixed, include/bppp.h): instance i proves its
+    /// first `ks[i]` values under one proof, 1 <= ks[i] <= k_max, k_max dim_nd <= 16 on these generators.  `xs` / `ss` hold k_max
+    /// scalars per instance (those behind ks[i] are never read); the k_max + 18 + (dim_nd + 1) + k_max dim_nd draws per instance are
+    /// made HERE, as in prove_values -- an instance uses the first ks[i] + 18 + (dim_nd + 1) + ks[i] dim_nd of its row, in the
+    /// reference's order for ks[i] values.  Returns (proofs, commitments) laid out by k_max, zero behind what an instance uses: what
+    /// `verify_agg_mixed` takes.
+    pub fn prove_agg_mixed<R: RngCore + CryptoRng>(&self, label: &'static [u8], k_max: usize, ks: &[u8], dim_nd: usize, dim_np: usize, xs: &[Scalar], ss: &[Scalar], rng: &mut R) -> Result<(Vec<u8>, Vec<u8>), GpuError> {
+        let n = ks.len();
+        assert!(xs.len() == n * k_max && ss.len() == n * k_max);
+        let draws = unsafe { bppp_reciprocal_agg_prove_draws(k_max, dim_nd) };
+        let mut rnd = Vec::with_capacity(n * draws * 32);
+        for _ in 0..n * draws {
+            put_scalar(&mut rnd, &Scalar::generate_biased(&mut *rng));
+        }
+        let (mut xb, mut sb) = (Vec::with_capacity(n * k_max * 32), Vec::with_capacity(n * k_max * 32));
+        xs.iter().for_each(|x| put_scalar(&mut xb, x));
+        ss.iter().for_each(|s| put_scalar(&mut sb, s));
+        let (mut rounds, mut nl, mut nn) = (0usize, 0usize, 0usize);
+        unsafe { bppp_wnla_proof_shape(32, 16, &mut rounds, &mut nl, &mut nn) };
+        let stride = unsafe { bppp_reciprocal_agg_proof_bytes(k_max, rounds, nl, nn) };
+        let (mut proofs, mut coms, mut st) = (vec![0u8; stride * n], vec![0u8; 64 * k_max * n], vec![0i32; n]);
+        check(unsafe {
+            bppp_reciprocal_agg_prove_values_batch_mixed(self.ctx, label.as_ptr(), label.len(), n, k_max, ks.as_ptr(), dim_nd, dim_np, xb.as_ptr(), sb.as_ptr(), rnd.as_ptr(), proofs.as_mut_ptr(), coms.as_mut_ptr(), st.as_mut_ptr())
+        })?;
+        if let Some(i) = st.iter().position(|s| *s & BPPP_ST_OUT_OF_RANGE != 0) {
+            return Err(GpuError::ValueOutOfRange { index: i });
+        }
+        if let Some(i) = st.iter().position(|s| *s != 0) {
+            return Err(GpuError::ReferenceWouldPanic { index: i });
+        }
+        Ok((proofs, coms))
+    }
 }
 
 impl Drop for U64RangeProofProtocolGpu {

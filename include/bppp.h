@@ -719,8 +719,9 @@ BPPP_API int bppp_reciprocal_agg_verify_batch_device(bppp_ctx* ctx, const uint8_
  * variable-base half of C0 for its own k_i -- a wavefront for the largest of its 64 -- and the fixed-base half for k_max (docs/design
  * 07 section 7d has the measurements).
  * Label transcripts only.  Of the SEC1 form, the RLC form and the caller-transcript form of the mixed call, the first two are the
- * entry points below.  NOT built: the caller-transcript form, a mixed prover, reordering instances by k on the device; and, as
- * above, the single-proof front end and sharded groups. */
+ * entry points below.  NOT built: the caller-transcript form and reordering instances by k on the device; and, as
+ * above, the single-proof front end and sharded groups.  What makes this call's input in one pass, a mixed prover, is further below:
+ * bppp_reciprocal_agg_prove_values_batch_mixed*. */
 BPPP_API int bppp_reciprocal_agg_mixed_check_args(size_t ng, size_t nh, size_t n, size_t k_max, const uint8_t* ks, int ks_on_device,
                                                   size_t dim_nd, size_t dim_np, size_t rounds, size_t nl, size_t nn);
 BPPP_API int bppp_reciprocal_agg_verify_batch_mixed(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
@@ -1063,6 +1064,55 @@ BPPP_API int bppp_reciprocal_agg_prove_values_batch_seeded_sec1(bppp_ctx* ctx, c
                                                                 size_t dim_nd, size_t dim_np, const uint8_t* x, const uint8_t* s,
                                                                 const uint8_t seed[32], uint64_t stream_base, uint8_t* proofs33,
                                                                 uint8_t* commitments33, int32_t* status /* n or NULL */);
+/* The aggregate prover for MIXED value counts in ONE batch: the prover's side of bppp_reciprocal_agg_verify_batch_mixed -- instance i
+ * has k_i = ks[i] values, 1 <= k_i <= k_max, and every buffer is laid out by k_max, exactly as that verifier reads them, so the output
+ * of one call is a valid input of it (bp_pp_amd/csrc/agg_prove_mixed_core.h).  The argument lists are the calls' above with k replaced by
+ * (k_max, ks).
+ *   x, s         n x k_max x 32: instance i's first k_i are read
+ *   rnd          n x D(k_max) x 32, D(k) = bppp_reciprocal_agg_prove_draws(k, dim_nd): instance i uses its first D(k_i) rows in the
+ *                uniform order for k_i: rb_0 .. rb_{k_i-1} | 18 | dim_nd + 1 | k_i dim_nd.  The seeded forms draw instance i from stream
+ *                stream_base + i (draw j is block j of the stream, so the first D(k_i) draws are the uniform seeded call's); the stream
+ *                range is checked for D(k_max) draws
+ *   proofs       n x bppp_reciprocal_agg_proof_bytes(k_max, rounds, nl, nn)
+ *   commitments  n x k_max x 64
+ * The first k_i x 64 bytes of instance i's commitment slot and the first bppp_reciprocal_agg_proof_bytes(k_i, ...) bytes of its proof
+ * slot are byte for byte what bppp_reciprocal_agg_prove_values_batch with k = k_i on this context gives the instance's first k_i
+ * values and blindings and its first D(k_i) draws; every other byte of both slots is written as zero.  Unused x, s and rnd slots are
+ * never read (0xFF bytes there flag nothing).
+ * BPPP_ERR_INVALID_ARG, before anything touches the GPU: the conditions of the uniform prover with k = k_max; a NULL ks; in the host
+ * forms a ks[i] outside [1, k_max].  n = 0 is BPPP_OK.  bppp_reciprocal_agg_prove_mixed_check_args is that decision as a pure function
+ * of the context's sizes (ng = |g_vec || g_vec_|, nh = |h_vec || h_vec_|; ks_on_device: ks only checked for NULL).  The device forms
+ * cannot read d_ks: an instance whose count is out of range is flagged BPPP_ST_BAD_ENCODING, its proof and commitments are zeroed; it
+ * runs on harmless values as a one-value instance, reads nothing of its x and s slots and touches no other instance.
+ * status: the uniform prover's, per instance, over the k_i values it uses; a flagged instance gets an all-zero proof slot and
+ * commitment slot.  "max_batch" parts are of "max_batch" / (k_max dim_nd) instances, each on its own slice of ks; "ct_prover" is
+ * honoured (the value count is public, nothing else new depends on an input); the _device forms are asynchronous as above.
+ * k_i = 1 instances run on the aggregate's kernels and k_max = 1 runs here too -- nothing is forwarded inside a mixed call, as in the
+ * mixed verifier; the bytes are the reciprocal prover's all the same.  Cost: the two fixed-base sums over the values and the circuit
+ * prover's sums run over k_max rows and ranges for every instance (zero scalars there); a wavefront takes the witness, r1, r2 and
+ * stages A, B, C for the largest of its 64 counts, r1's transcript part and stage B once per count present in it (docs/design 07
+ * section 7e).
+ * NOT built for the mixed prover: the caller-transcript form, the SEC1 output form, sharded groups and the single-proof front end. */
+BPPP_API int bppp_reciprocal_agg_prove_mixed_check_args(size_t ng, size_t nh, size_t n, size_t k_max, const uint8_t* ks, int ks_on_device,
+                                                        size_t dim_nd, size_t dim_np);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_mixed(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n, size_t k_max,
+                                                          const uint8_t* ks, size_t dim_nd, size_t dim_np, const uint8_t* x,
+                                                          const uint8_t* s, const uint8_t* rnd, uint8_t* proofs, uint8_t* commitments,
+                                                          int32_t* status /* n or NULL */);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_mixed_seeded(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                                                 size_t k_max, const uint8_t* ks, size_t dim_nd, size_t dim_np,
+                                                                 const uint8_t* x, const uint8_t* s, const uint8_t seed[32],
+                                                                 uint64_t stream_base, uint8_t* proofs, uint8_t* commitments,
+                                                                 int32_t* status /* n or NULL */);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_mixed_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                                                 size_t k_max, const void* d_ks, size_t dim_nd, size_t dim_np,
+                                                                 const void* d_x, const void* d_s, const void* d_rnd, void* d_proofs,
+                                                                 void* d_commitments, void* d_status);
+BPPP_API int bppp_reciprocal_agg_prove_values_batch_mixed_seeded_device(bppp_ctx* ctx, const uint8_t* label, size_t label_len, size_t n,
+                                                                        size_t k_max, const void* d_ks, size_t dim_nd, size_t dim_np,
+                                                                        const void* d_x, const void* d_s, const uint8_t seed[32],
+                                                                        uint64_t stream_base, void* d_proofs, void* d_commitments,
+                                                                        void* d_status);
 
 /* Profiling aid for bench.py: when enabled, every kernel launch of the verify pipeline is bracketed by HIP events on
  * the context's stream; bppp_ctx_get_timings returns accumulated milliseconds and launch counts per kernel since the
